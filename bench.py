@@ -11,7 +11,10 @@ momentum predictor, set_BC, rhs, 10 Jacobi sweeps, velocity correction, set_BC, 
 sweeps (+post_process_f), set_BC -- and, for N > 1, the per-step halo exchange.  Inputs are
 generated on the device by set_init_F (-ic 1), so they are resident in HBM when timing starts.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "measurement" for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md "measurement" for every field).  A plain run sets up, warms up, times the
+K steps and prints the headline (metric, value, unit, ms_per_step, dtype, config); --full adds every other record of the
+line after it (Jacobi kernel timings and `roofline`, in-situ kernel profile, single-GPU 8192^2 leg, sustained, worst-case,
+FMA-build and 1024^2 residual records, CPU baseline).  --dump-outputs DIR writes the fields the last timed step left.
 """
 import argparse
 import ctypes
@@ -52,12 +55,20 @@ def parse():
     ap.add_argument("-ic", type=int, default=1, choices=[1, 2, 3])
     ap.add_argument("--jacobi-sweeps-timed", type=int, default=200)
     ap.add_argument("--jacobi-iters", type=int, default=10, help="sweeps per step (reference: 10, 2dvof.py:521)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry: the Jacobi kernel timings and "
+                         "`roofline`, the in-situ kernel profile, the single-GPU 8192^2 leg, the sustained / worst-case / "
+                         "FMA-build / 1024^2 residual records and the CPU baseline (the --no-* options below trim this).  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write F, u, v, p as the timed path left them to DIR/<name>.npy "
+                         "(see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-scaling-reference", action="store_true",
-                    help="skip the single-GPU 8192^2 leg (strong_scaling_reference_n1); used for the rocprofv3 "
+                    help="--full: skip the single-GPU 8192^2 leg (strong_scaling_reference_n1); used for the rocprofv3 "
                          "profiles, whose per-kernel averages must come from one grid size")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1: skip the sustained 1000-step record and the 1024^2 residual-terminated solve "
+                    help="--full, N = 1: skip the sustained 1000-step record and the 1024^2 residual-terminated solve "
                          "(the rocprofv3 profiles: one workload per trace)")
     ap.add_argument("--sustained-steps", type=int, default=1000)
     ap.add_argument("--profile-steps", type=int, default=350,
@@ -344,6 +355,25 @@ def _batch_form(form):
     if choice == 1 or (choice < 0 and tm_steps > 0):
         return "k_tm batch graphs (k_transport + the next step's k_momentum as one kernel)"
     return "chain batch graphs (every kernel as launches on row blocks)" if halves else "one-chain batch graphs"
+
+
+DUMP_SAMPLE_CELLS = 1 << 20     # per field: 4 x 8 MB in fp64
+
+
+def dump_outputs(out_dir, fields):
+    """--dump-outputs: each field as the timed path left it after its last step -- what Engine.get (StripSolver.gather on
+    the N > 1 path) hands a caller, (nx + 2) x (ny + 2) with the ghost frame, in the run's precision -- as
+    out_dir/<name>.npy.  A field of more than DUMP_SAMPLE_CELLS cells is written as a fixed sample instead: the values at
+    DUMP_SAMPLE_CELLS flat indices drawn with seed 0 (sorted), the same indices for every field and every run of that grid."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    for name, x in fields.items():
+        if x.size > DUMP_SAMPLE_CELLS:
+            if idx is None:
+                idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_SAMPLE_CELLS, replace=False))
+            x = np.ascontiguousarray(x).reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
 
 
 def timed_steps(eng, warmup, steps):
@@ -731,96 +761,13 @@ def main():
             digests["istep"] = int(eng.istep)
             digests["shape"] = list(got["F"].shape)
         del got
-    # Jacobi kernels.
-    # (1) the north-star kernel: k_jacobi, one sweep per launch, 3 array passes, HBM-bound.  Timed
-    #     live with one HIP event pair on the stream the kernels are launched on, around
-    #     --jacobi-sweeps-timed back-to-back launches (vof_time_jacobi).  Agrees with rocprofv3.
-    # (2) what the step actually runs: k_jacobi_tb, `tb` sweeps fused per launch.  Its
-    #     duration depends on the clock state: sustained back-to-back launches (event pair, same
-    #     call) run ~20 % slower than the two launches interleaved in a real step, so the in-step
-    #     cost is also derived from wall-clock step times with and without the pressure sweeps.
-    comp_rows = min(nx, eng.row_hi - 1) - max(1, eng.row_lo + 1) + 1
-    sweep_bytes = 3 * esz * comp_rows * ny          # read p, read rhs, write p' per computed cell
-    tb = int(eng.get_param("jacobi_tb"))
-    nt = max(2 * tb, a.jacobi_sweeps_timed // (2 * tb) * 2 * tb)
-    eng.set_param("solve_pairs", 0)            # (this record is k_jacobi_tb's: five sweeps per launch, not the pair kernel's ten)
-    ms_sweep_tb = eng.time_jacobi(nt)
-    eng.set_param("jacobi_tb", 1)
-    ms_sweep_1 = eng.time_jacobi(max(2, a.jacobi_sweeps_timed // 2 * 2))
-    eng.set_param("jacobi_tb", tb)
+    if a.dump_outputs:
+        # (before the Jacobi timing of --full moves p: the fields as the last timed step left them)
+        fields = {f: solver.gather(f) if dist_path else eng.get(f) for f in ("F", "u", "v", "p")}   # (every rank takes part in a gather)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, fields)
+        del fields
     violations = eng.get_counter("courant_violations") - (warm_violations if not dist_path else 0)
-    achieved_1 = sweep_bytes / (ms_sweep_1 * 1e-3) / 1e9
-    traffic, traffic_note = load_pmc_traffic(nx, ny, a.dtype) if not dist_path else ({}, "N > 1")
-    fused = {"kernel": "k_jacobi_tb", "sweeps_per_launch": tb, "bound": "hbm (actual traffic: lead-in rows + tile overlap)",
-             "us_per_launch_back_to_back": 1e3 * ms_sweep_tb * tb, "us_per_sweep_back_to_back": 1e3 * ms_sweep_tb,
-             "hbm_traffic_bytes_per_launch": traffic.get("tb")}
-    if not dist_path and a.jacobi_iters > 0 and a.jacobi_iters % tb == 0:
-        # in-step cost: (step with sweeps - step without sweeps) / launches, both graph-replayed
-        from vof2d.engine import Engine as _E, make_desc as _md
-        e0 = _E(api, _md(api, nx, ny, a.dtype, "f32", device=local, jacobi_iters=0, dt=dt))
-        e0.set_init_F(a.ic)
-        ms0 = 1e3 * timed_steps(e0, a.warmup, a.steps) / a.steps
-        e0.close()
-        launches = a.jacobi_iters // tb
-        us_in_step = (1e3 * elapsed / a.steps - ms0) * 1e3 / launches
-        fused.update({"us_per_launch_in_step": us_in_step, "us_per_sweep_in_step": us_in_step / tb,
-                      "ms_per_step_without_sweeps": ms0,
-                      "algorithmic_GBs_in_step": sweep_bytes * tb / (us_in_step * 1e-6) / 1e9,
-                      "frac_of_peak_on_its_3_passes": sweep_bytes / (us_in_step * 1e-6) / 1e9 / HBM_PEAK_GBS})
-    # The N > 1 runs strong-scale 8192^2; give the single-GPU figure for that grid too, so the
-    # scaling series has its own N = 1 point: in the N = 1 line (default workload only), and --
-    # measured in the same job, on rank 0's GPU, after the timed region -- in every N > 1 line.
-    ref8192 = None
-    speedup = None
-    if rank == 0 and not a.no_scaling_reference and ((not dist_path and not a.nx) or (world > 1 and nx == ny)):
-        try:
-            if api is None:
-                from vof2d._lib import hip_api
-                api = hip_api()
-            nref = 8192 if not dist_path else nx
-            ref8192 = single_gpu_reference(api, nref, a.dtype, a.ic, local, a.jacobi_iters, stable_dt(nref))
-            if dist_path:
-                speedup = (nx * ny * a.steps / elapsed) / ref8192["value"]
-        except Exception as exc:   # e.g. not enough free HBM
-            ref8192 = {"error": str(exc)}
-    # the kernels of the step under the built-in profiler (one HIP event pair per dispatch, on the stream the kernels are
-    # launched on), on a fresh run of the same workload, steps 11 .. 10 + --profile-steps: long enough to contain the
-    # regime in which the tiny-value front of the pressure iteration crosses the grid.  (`eng` has just had its p
-    # advanced by the back-to-back Jacobi launches above, which is not a state the solver passes through.)
-    prof, prof_note, nprof = {}, None, max(1, a.profile_steps)
-    prof_run = {}
-    if not dist_path:
-        try:
-            from vof2d.engine import Engine as _E, make_desc as _md
-            e1 = _E(api, _md(api, nx, ny, a.dtype, "f32", device=local, jacobi_iters=a.jacobi_iters, dt=dt))
-            try:
-                e1.set_init_F(a.ic)
-                e1.step(10)
-                prof = e1.profile_steps(nprof)
-                # ... and the launches of the form the handle keeps (k_tm / k_jacobi_pair on a large fp64 grid), the same
-                # steps of the same run: the handle is warmed (which decides the form) and put back to the initial state
-                kept_tm = form_state[1] == 1 or (form_state[1] < 0 and form_state[2] > 0)
-                if kept_tm:
-                    e1.set_param("fuse_tm", 1)     # (the form the timed handle runs)
-                    warm_handle(e1, a.ic, nx, ny, a.dtype)
-                    e1.step(10)
-                    prof_run = e1.profile_steps(nprof)
-            finally:
-                e1.close()
-        except Exception as exc:      # e.g. not enough free HBM for a second engine: the line survives without the breakdown
-            prof, prof_note = {}, "in-situ profile failed: %s" % (exc,)
-    kernels_us = {k: round(v[0], 2) for k, v in prof.items()}
-    cells = nx * ny
-    step_kernels = {k: {"launches_per_step": round(v[1] / float(nprof), 2), "algorithmic_passes": KERNEL_PASSES[k],
-                        "algorithmic_bytes_per_launch": KERNEL_PASSES[k] * esz * cells, "us_per_launch_dispatch": round(v[0], 2),
-                        "frac_of_peak": KERNEL_PASSES[k] * esz * cells / (v[0] * 1e-6) / 1e9 / HBM_PEAK_GBS}
-                    for k, v in prof.items() if k in KERNEL_PASSES and v[0] > 0}
-
-    run_kernels = {k: {"launches_per_step": round(v[1] / float(nprof), 3), "algorithmic_passes": KERNEL_PASSES[k],
-                       "algorithmic_bytes_per_launch": KERNEL_PASSES[k] * esz * cells, "us_per_launch_dispatch": round(v[0], 2),
-                       "frac_of_peak": KERNEL_PASSES[k] * esz * cells / (v[0] * 1e-6) / 1e9 / HBM_PEAK_GBS}
-                   for k, v in prof_run.items() if k in KERNEL_PASSES and v[0] > 0}
-
     # which schedule actually ran: the 19-pass one-kernel transport needs a full domain, or mode 4 with
     # EVERY timed step replayed from the captured exchange graph (an RCCL that cannot capture, or
     # VOF2D_XCHG_GRAPH=0, silently runs mode 4 as eager mode 1 with the two-kernel transport)
@@ -839,29 +786,118 @@ def main():
     ARRAYS_PER_STEP = ARRAYS_PER_STEP_FULL if one_kernel_transport else ARRAYS_PER_STEP_STRIP
     if dist_path and world > 1 and a.overlap == 5:
         ARRAYS_PER_STEP = 11        # k_jacobi_pair 3 + k_tm 8 per middle step (the head and the tail of a call: once per call)
-    # What the step AS THE HANDLE RAN IT has to move, by SURVEY 8d's rule applied to its own kernel list (every distinct
-    # array a kernel reads or writes, once, times its launches per step, from the in-situ profile of the kept form):
-    # 8 x 15/16 (k_tm) + 10 x 1/16 (the last k_tm of a 16-step batch, which also stores u and v: the batches chain, no plain
-    # k_momentum / k_transport is left) + 3 (k_jacobi_pair: ten sweeps) = 11.1 passes where the pair kernels run,
-    # 6 + 2 x 3 + 7 = 19 for the four-kernel schedule.  Three
-    # step fractions stand side by side in `config`: on this list, on the 19 passes of the four-kernel schedule every
-    # earlier round quoted, and on the HBM traffic the counters saw.
-    own_kernels = run_kernels if "k_tm" in run_kernels else step_kernels
-    own_passes = sum(v["launches_per_step"] * v["algorithmic_passes"] for v in own_kernels.values()) if own_kernels else float(ARRAYS_PER_STEP)
-    step_s = elapsed / a.steps
-    traffic_all, traffic_all_note = ({}, "N > 1")
-    if not dist_path:
-        traffic_all, traffic_all_note = load_pmc_traffic(nx, ny, a.dtype, os.path.join(ROOT, "profiles", "tm_pmc.json" if "k_tm" in run_kernels else "jacobi_pmc.json"))
-    fam = {"k_tm": "tm", "k_tm_uv": "tm_uv", "k_jacobi_pair": "pair", "k_jacobi_tb": "tb", "k_momentum": "momentum", "k_transport": "transport", "k_jacobi": "single"}
-    step_traffic = None
-    if own_kernels and all(fam.get(k) in traffic_all for k in own_kernels):
-        step_traffic = sum(v["launches_per_step"] * traffic_all[fam[k]] for k, v in own_kernels.items())
-    fractions = {
-        "own_kernel_list": own_passes * esz * cells / step_s / 1e9 / HBM_PEAK_GBS,
-        "reference_schedule_19_passes": ARRAYS_PER_STEP * esz * cells / step_s / 1e9 / HBM_PEAK_GBS,
-        "counter_traffic": (step_traffic / step_s / 1e9 / HBM_PEAK_GBS) if step_traffic else None,
-        "counter_traffic_note": traffic_all_note if step_traffic else ("no committed PMC passes for every kernel of the step (%s)" % traffic_all_note),
-    }
+    if a.full:
+        # Jacobi kernels.
+        # (1) the north-star kernel: k_jacobi, one sweep per launch, 3 array passes, HBM-bound.  Timed
+        #     live with one HIP event pair on the stream the kernels are launched on, around
+        #     --jacobi-sweeps-timed back-to-back launches (vof_time_jacobi).  Agrees with rocprofv3.
+        # (2) what the step actually runs: k_jacobi_tb, `tb` sweeps fused per launch.  Its
+        #     duration depends on the clock state: sustained back-to-back launches (event pair, same
+        #     call) run ~20 % slower than the two launches interleaved in a real step, so the in-step
+        #     cost is also derived from wall-clock step times with and without the pressure sweeps.
+        comp_rows = min(nx, eng.row_hi - 1) - max(1, eng.row_lo + 1) + 1
+        sweep_bytes = 3 * esz * comp_rows * ny          # read p, read rhs, write p' per computed cell
+        tb = int(eng.get_param("jacobi_tb"))
+        nt = max(2 * tb, a.jacobi_sweeps_timed // (2 * tb) * 2 * tb)
+        eng.set_param("solve_pairs", 0)            # (this record is k_jacobi_tb's: five sweeps per launch, not the pair kernel's ten)
+        ms_sweep_tb = eng.time_jacobi(nt)
+        eng.set_param("jacobi_tb", 1)
+        ms_sweep_1 = eng.time_jacobi(max(2, a.jacobi_sweeps_timed // 2 * 2))
+        eng.set_param("jacobi_tb", tb)
+        achieved_1 = sweep_bytes / (ms_sweep_1 * 1e-3) / 1e9
+        traffic, traffic_note = load_pmc_traffic(nx, ny, a.dtype) if not dist_path else ({}, "N > 1")
+        fused = {"kernel": "k_jacobi_tb", "sweeps_per_launch": tb, "bound": "hbm (actual traffic: lead-in rows + tile overlap)",
+                 "us_per_launch_back_to_back": 1e3 * ms_sweep_tb * tb, "us_per_sweep_back_to_back": 1e3 * ms_sweep_tb,
+                 "hbm_traffic_bytes_per_launch": traffic.get("tb")}
+        if not dist_path and a.jacobi_iters > 0 and a.jacobi_iters % tb == 0:
+            # in-step cost: (step with sweeps - step without sweeps) / launches, both graph-replayed
+            from vof2d.engine import Engine as _E, make_desc as _md
+            e0 = _E(api, _md(api, nx, ny, a.dtype, "f32", device=local, jacobi_iters=0, dt=dt))
+            e0.set_init_F(a.ic)
+            ms0 = 1e3 * timed_steps(e0, a.warmup, a.steps) / a.steps
+            e0.close()
+            launches = a.jacobi_iters // tb
+            us_in_step = (1e3 * elapsed / a.steps - ms0) * 1e3 / launches
+            fused.update({"us_per_launch_in_step": us_in_step, "us_per_sweep_in_step": us_in_step / tb,
+                          "ms_per_step_without_sweeps": ms0,
+                          "algorithmic_GBs_in_step": sweep_bytes * tb / (us_in_step * 1e-6) / 1e9,
+                          "frac_of_peak_on_its_3_passes": sweep_bytes / (us_in_step * 1e-6) / 1e9 / HBM_PEAK_GBS})
+        # The N > 1 runs strong-scale 8192^2; give the single-GPU figure for that grid too, so the
+        # scaling series has its own N = 1 point: in the N = 1 line (default workload only), and --
+        # measured in the same job, on rank 0's GPU, after the timed region -- in every N > 1 line.
+        ref8192 = None
+        speedup = None
+        if rank == 0 and not a.no_scaling_reference and ((not dist_path and not a.nx) or (world > 1 and nx == ny)):
+            try:
+                if api is None:
+                    from vof2d._lib import hip_api
+                    api = hip_api()
+                nref = 8192 if not dist_path else nx
+                ref8192 = single_gpu_reference(api, nref, a.dtype, a.ic, local, a.jacobi_iters, stable_dt(nref))
+                if dist_path:
+                    speedup = (nx * ny * a.steps / elapsed) / ref8192["value"]
+            except Exception as exc:   # e.g. not enough free HBM
+                ref8192 = {"error": str(exc)}
+        # the kernels of the step under the built-in profiler (one HIP event pair per dispatch, on the stream the kernels are
+        # launched on), on a fresh run of the same workload, steps 11 .. 10 + --profile-steps: long enough to contain the
+        # regime in which the tiny-value front of the pressure iteration crosses the grid.  (`eng` has just had its p
+        # advanced by the back-to-back Jacobi launches above, which is not a state the solver passes through.)
+        prof, prof_note, nprof = {}, None, max(1, a.profile_steps)
+        prof_run = {}
+        if not dist_path:
+            try:
+                from vof2d.engine import Engine as _E, make_desc as _md
+                e1 = _E(api, _md(api, nx, ny, a.dtype, "f32", device=local, jacobi_iters=a.jacobi_iters, dt=dt))
+                try:
+                    e1.set_init_F(a.ic)
+                    e1.step(10)
+                    prof = e1.profile_steps(nprof)
+                    # ... and the launches of the form the handle keeps (k_tm / k_jacobi_pair on a large fp64 grid), the same
+                    # steps of the same run: the handle is warmed (which decides the form) and put back to the initial state
+                    kept_tm = form_state[1] == 1 or (form_state[1] < 0 and form_state[2] > 0)
+                    if kept_tm:
+                        e1.set_param("fuse_tm", 1)     # (the form the timed handle runs)
+                        warm_handle(e1, a.ic, nx, ny, a.dtype)
+                        e1.step(10)
+                        prof_run = e1.profile_steps(nprof)
+                finally:
+                    e1.close()
+            except Exception as exc:      # e.g. not enough free HBM for a second engine: the line survives without the breakdown
+                prof, prof_note = {}, "in-situ profile failed: %s" % (exc,)
+        kernels_us = {k: round(v[0], 2) for k, v in prof.items()}
+        cells = nx * ny
+        step_kernels = {k: {"launches_per_step": round(v[1] / float(nprof), 2), "algorithmic_passes": KERNEL_PASSES[k],
+                            "algorithmic_bytes_per_launch": KERNEL_PASSES[k] * esz * cells, "us_per_launch_dispatch": round(v[0], 2),
+                            "frac_of_peak": KERNEL_PASSES[k] * esz * cells / (v[0] * 1e-6) / 1e9 / HBM_PEAK_GBS}
+                        for k, v in prof.items() if k in KERNEL_PASSES and v[0] > 0}
+
+        run_kernels = {k: {"launches_per_step": round(v[1] / float(nprof), 3), "algorithmic_passes": KERNEL_PASSES[k],
+                           "algorithmic_bytes_per_launch": KERNEL_PASSES[k] * esz * cells, "us_per_launch_dispatch": round(v[0], 2),
+                           "frac_of_peak": KERNEL_PASSES[k] * esz * cells / (v[0] * 1e-6) / 1e9 / HBM_PEAK_GBS}
+                       for k, v in prof_run.items() if k in KERNEL_PASSES and v[0] > 0}
+        # What the step AS THE HANDLE RAN IT has to move, by SURVEY 8d's rule applied to its own kernel list (every distinct
+        # array a kernel reads or writes, once, times its launches per step, from the in-situ profile of the kept form):
+        # 8 x 15/16 (k_tm) + 10 x 1/16 (the last k_tm of a 16-step batch, which also stores u and v: the batches chain, no plain
+        # k_momentum / k_transport is left) + 3 (k_jacobi_pair: ten sweeps) = 11.1 passes where the pair kernels run,
+        # 6 + 2 x 3 + 7 = 19 for the four-kernel schedule.  Three
+        # step fractions stand side by side in `config`: on this list, on the 19 passes of the four-kernel schedule every
+        # earlier round quoted, and on the HBM traffic the counters saw.
+        own_kernels = run_kernels if "k_tm" in run_kernels else step_kernels
+        own_passes = sum(v["launches_per_step"] * v["algorithmic_passes"] for v in own_kernels.values()) if own_kernels else float(ARRAYS_PER_STEP)
+        step_s = elapsed / a.steps
+        traffic_all, traffic_all_note = ({}, "N > 1")
+        if not dist_path:
+            traffic_all, traffic_all_note = load_pmc_traffic(nx, ny, a.dtype, os.path.join(ROOT, "profiles", "tm_pmc.json" if "k_tm" in run_kernels else "jacobi_pmc.json"))
+        fam = {"k_tm": "tm", "k_tm_uv": "tm_uv", "k_jacobi_pair": "pair", "k_jacobi_tb": "tb", "k_momentum": "momentum", "k_transport": "transport", "k_jacobi": "single"}
+        step_traffic = None
+        if own_kernels and all(fam.get(k) in traffic_all for k in own_kernels):
+            step_traffic = sum(v["launches_per_step"] * traffic_all[fam[k]] for k, v in own_kernels.items())
+        fractions = {
+            "own_kernel_list": own_passes * esz * cells / step_s / 1e9 / HBM_PEAK_GBS,
+            "reference_schedule_19_passes": ARRAYS_PER_STEP * esz * cells / step_s / 1e9 / HBM_PEAK_GBS,
+            "counter_traffic": (step_traffic / step_s / 1e9 / HBM_PEAK_GBS) if step_traffic else None,
+            "counter_traffic_note": traffic_all_note if step_traffic else ("no committed PMC passes for every kernel of the step (%s)" % traffic_all_note),
+        }
     if rank == 0 and dist_path:
         # which carrier moved the halos, BEFORE the line (a reader of the log sees it even if the line is lost)
         print("[bench] carrier: %s exchange, overlap mode %s%s, %s" % (
@@ -895,11 +931,6 @@ def main():
                 # the one-GPU rehearsal of the N > 1 path (--same-device): every rank on device 0, halos over gloo through host
                 # memory -- the line's rate is of N processes sharing one GPU and says nothing about scaling
                 "same_device_rehearsal": bool(a.same_device) if dist_path else None,
-                "arrays_per_cell_update": round(own_passes, 3),
-                "bytes_per_cell_update_algorithmic": round(own_passes * esz, 2),
-                "arrays_per_cell_update_four_kernel_schedule": ARRAYS_PER_STEP,
-                "step_kernel_list": {k: {"launches_per_step": v["launches_per_step"], "passes": v["algorithmic_passes"]} for k, v in own_kernels.items()} or None,
-                "step_frac_of_peak": fractions,
                 "tm_choice": form_state[1] if not dist_path else None,      # 1 / 0: the rule of vof_step chose k_tm / the chains; -1: the rule does not apply here
                 "gas_share": form_state[3] if not dist_path else None,      # what the rule saw: the share of exact-zero cells of F
                 # two-chain: every kernel of a step as two launches (rows above / below a moving boundary) on two
@@ -908,63 +939,71 @@ def main():
                 "step_schedule": _batch_form(form_state[:3]) if not dist_path else "strips",
                 "handle_warm_steps": HANDLE_WARM_STEPS if not dist_path else None,
                 "handle_warm_ms": round(handle_warm_ms, 2) if not dist_path else None},
-            # `roofline` = the Poisson Jacobi kernel THE STEP RUNS, k_jacobi_tb (five sweeps per launch): algorithmic bytes =
-            # 3 arrays x sizeof(T) x cells per launch (read p, read rhs, write p after five sweeps; SURVEY 8d's 24 B rule
-            # per launch), duration = its average dispatch over the in-situ profile above (HIP events on the launch
-            # stream, steps 11 .. 10 + --profile-steps of a fresh run, the tiny-value front included); `traffic` = HBM
-            # bytes per launch from the committed rocprofv3 --pmc passes (profiles/jacobi_pmc.json).  The single-sweep
-            # kernel of the north star's wording (k_jacobi, not launched by the step) is `north_star_single_sweep`.
-            "roofline": roofline_record(step_kernels, traffic, traffic_note, nprof, prof_note, sweep_bytes, fused, tb, {
-                "kernel": "k_jacobi", "bound": "hbm", "achieved": achieved_1, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved_1 / HBM_PEAK_GBS, "traffic": traffic.get("single"), "us_per_launch": 1e3 * ms_sweep_1,
-                "algorithmic_bytes_per_launch": sweep_bytes, "launches_timed": max(2, a.jacobi_sweeps_timed // 2 * 2),
-                "note": "one sweep per launch, back-to-back launches between one HIP event pair (vof_time_jacobi); used by "
-                        "the step only for sweep counts that are not a multiple of five and for the residual checks"}),
-            "jacobi_fused": fused,
-            "step_kernels_as_run": run_kernels or None,
-            # the kernels the step itself runs, same counting rule (built-in profiler: dispatch start ->
-            # stop; reads a few us high behind a long-tailed predecessor -- rocprofv3, profiles/, is the reference)
-            "step_kernels": step_kernels,
-            "strong_scaling_reference_n1": ref8192,
             "fields_sha256": digests,
-            "speedup_same_grid": speedup,
-            "step_hbm_gbs_algorithmic": own_passes * esz * nx * ny * a.steps / elapsed / 1e9,
-            "step_frac_of_peak_algorithmic": fractions["own_kernel_list"],
-            "step_frac_of_peak_on_the_four_kernel_schedule": fractions["reference_schedule_19_passes"],
-            "step_frac_of_peak_counter_traffic": fractions["counter_traffic"],
-            "kernels_us_dispatch_start_to_stop": kernels_us,
             "courant_violations": violations,
         }
-        if "k_tm" in run_kernels:
-            traffic_tm, note_tm = load_pmc_traffic(nx, ny, a.dtype, os.path.join(ROOT, "profiles", "tm_pmc.json"))
-            out["roofline"] = roofline_of_the_kept_form(run_kernels, out["roofline"], traffic_tm, note_tm, nprof, esz, cells)
-        if not dist_path and not a.no_extras:
-            try:
-                out["sustained"] = sustained_record(api, nx, ny, a.dtype, a.ic, local, a.jacobi_iters, dt, a.sustained_steps)
-                out["config"]["sustained_ms_per_step"] = round(out["sustained"]["ms_per_step"], 4)     # (in `config` too: the driver's record keeps that object)
-                out["config"]["sustained_steps"] = out["sustained"]["steps"]
-            except Exception as exc:
-                out["sustained"] = {"error": str(exc)}
-            if a.ic == 1:
+        if a.full:
+            out["config"].update({
+                "arrays_per_cell_update": round(own_passes, 3),
+                "bytes_per_cell_update_algorithmic": round(own_passes * esz, 2),
+                "arrays_per_cell_update_four_kernel_schedule": ARRAYS_PER_STEP,
+                "step_kernel_list": {k: {"launches_per_step": v["launches_per_step"], "passes": v["algorithmic_passes"]} for k, v in own_kernels.items()} or None,
+                "step_frac_of_peak": fractions})
+            out.update({
+                # `roofline` = the Poisson Jacobi kernel THE STEP RUNS, k_jacobi_tb (five sweeps per launch): algorithmic bytes =
+                # 3 arrays x sizeof(T) x cells per launch (read p, read rhs, write p after five sweeps; SURVEY 8d's 24 B rule
+                # per launch), duration = its average dispatch over the in-situ profile above (HIP events on the launch
+                # stream, steps 11 .. 10 + --profile-steps of a fresh run, the tiny-value front included); `traffic` = HBM
+                # bytes per launch from the committed rocprofv3 --pmc passes (profiles/jacobi_pmc.json).  The single-sweep
+                # kernel of the north star's wording (k_jacobi, not launched by the step) is `north_star_single_sweep`.
+                "roofline": roofline_record(step_kernels, traffic, traffic_note, nprof, prof_note, sweep_bytes, fused, tb, {
+                    "kernel": "k_jacobi", "bound": "hbm", "achieved": achieved_1, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved_1 / HBM_PEAK_GBS, "traffic": traffic.get("single"), "us_per_launch": 1e3 * ms_sweep_1,
+                    "algorithmic_bytes_per_launch": sweep_bytes, "launches_timed": max(2, a.jacobi_sweeps_timed // 2 * 2),
+                    "note": "one sweep per launch, back-to-back launches between one HIP event pair (vof_time_jacobi); used by "
+                            "the step only for sweep counts that are not a multiple of five and for the residual checks"}),
+                "jacobi_fused": fused,
+                "step_kernels_as_run": run_kernels or None,
+                # the kernels the step itself runs, same counting rule (built-in profiler: dispatch start ->
+                # stop; reads a few us high behind a long-tailed predecessor -- rocprofv3, profiles/, is the reference)
+                "step_kernels": step_kernels,
+                "strong_scaling_reference_n1": ref8192,
+                "speedup_same_grid": speedup,
+                "step_hbm_gbs_algorithmic": own_passes * esz * nx * ny * a.steps / elapsed / 1e9,
+                "step_frac_of_peak_algorithmic": fractions["own_kernel_list"],
+                "step_frac_of_peak_on_the_four_kernel_schedule": fractions["reference_schedule_19_passes"],
+                "step_frac_of_peak_counter_traffic": fractions["counter_traffic"],
+                "kernels_us_dispatch_start_to_stop": kernels_us})
+            if "k_tm" in run_kernels:
+                traffic_tm, note_tm = load_pmc_traffic(nx, ny, a.dtype, os.path.join(ROOT, "profiles", "tm_pmc.json"))
+                out["roofline"] = roofline_of_the_kept_form(run_kernels, out["roofline"], traffic_tm, note_tm, nprof, esz, cells)
+            if not dist_path and not a.no_extras:
                 try:
-                    wc = worst_case_record(api, nx, ny, a.dtype, local, a.jacobi_iters, dt, a.steps)
-                    wc["slowdown_vs_the_headline_workload"] = wc["ms_per_step"] / (1e3 * elapsed / a.steps)
-                    out["config"]["worst_case"] = wc
+                    out["sustained"] = sustained_record(api, nx, ny, a.dtype, a.ic, local, a.jacobi_iters, dt, a.sustained_steps)
+                    out["config"]["sustained_ms_per_step"] = round(out["sustained"]["ms_per_step"], 4)     # (in `config` too: the driver's record keeps that object)
+                    out["config"]["sustained_steps"] = out["sustained"]["steps"]
                 except Exception as exc:
-                    out["config"]["worst_case"] = {"error": str(exc)}
-            try:   # what bit-faithful arithmetic costs: the same workload on the FMA-contracted build (own process)
-                out["fast_build"] = run_fast_leg(a)
-                if "value" in out["fast_build"]:
-                    out["fast_build"]["speedup_over_parity_build"] = out["fast_build"]["value"] / out["value"]
-            except Exception as exc:
-                out["fast_build"] = {"error": str(exc)}
-            if not a.nx:      # default workload only
-                try:
-                    out["residual_solve_1024"] = residual_solve_1024(api, local)
+                    out["sustained"] = {"error": str(exc)}
+                if a.ic == 1:
+                    try:
+                        wc = worst_case_record(api, nx, ny, a.dtype, local, a.jacobi_iters, dt, a.steps)
+                        wc["slowdown_vs_the_headline_workload"] = wc["ms_per_step"] / (1e3 * elapsed / a.steps)
+                        out["config"]["worst_case"] = wc
+                    except Exception as exc:
+                        out["config"]["worst_case"] = {"error": str(exc)}
+                try:   # what bit-faithful arithmetic costs: the same workload on the FMA-contracted build (own process)
+                    out["fast_build"] = run_fast_leg(a)
+                    if "value" in out["fast_build"]:
+                        out["fast_build"]["speedup_over_parity_build"] = out["fast_build"]["value"] / out["value"]
                 except Exception as exc:
-                    out["residual_solve_1024"] = {"error": str(exc)}
-        if not dist_path and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(nx, ny, a.dtype, a.ic, a.cpu_seconds)
+                    out["fast_build"] = {"error": str(exc)}
+                if not a.nx:      # default workload only
+                    try:
+                        out["residual_solve_1024"] = residual_solve_1024(api, local)
+                    except Exception as exc:
+                        out["residual_solve_1024"] = {"error": str(exc)}
+            if not dist_path and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(nx, ny, a.dtype, a.ic, a.cpu_seconds)
         print(json.dumps(out), flush=True)
     if dist_path and native_ok:
         solver.barrier()

@@ -52,6 +52,7 @@ and changes nothing else.
 """
 import argparse
 import ast
+import glob
 import hashlib
 import inspect
 import itertools
@@ -505,8 +506,29 @@ def main():
     prec = "f32" if a.f32 else "f64"
     path = a.out or os.path.join(HERE, ("ref_ic%d_200_%s.npz" % (a.ic, prec)) if a.grid is None else
                                  ("ref_ic%d_%dx%d_%s%s.npz" % (a.ic, nx, ny, prec, "_vis" if a.vis else "")))
-    np.savez_compressed(path, **out)
+    save(path, out)
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+def save(path, out, limit=1 << 20):
+    """np.savez_compressed(path, **out) -- unless the file would exceed `limit` (a committed file stays within 1 MiB):
+    then u, v, p of every recorded step after the first go to split/<name>-<step>.npz beside it, one file per step
+    (tests/util.py load_golden merges them back)."""
+    name = os.path.basename(path)[:-4]
+    split = os.path.join(os.path.dirname(path), "split")
+    for old in glob.glob(os.path.join(split, name + "-*.npz")):
+        os.remove(old)
+    np.savez_compressed(path, **out)
+    if os.path.getsize(path) <= limit:
+        return
+    steps = sorted({int(k[2:]) for k in out if k[:2] in ("u_", "v_", "p_") and k[2:].isdigit()})
+    rest, parts = dict(out), {}
+    for st in steps[1:]:
+        parts[st] = {k: rest.pop(k) for k in ("u_%d" % st, "v_%d" % st, "p_%d" % st) if k in rest}
+    os.makedirs(split, exist_ok=True)
+    np.savez_compressed(path, **rest)
+    for st, arrays in parts.items():
+        np.savez_compressed(os.path.join(split, "%s-%d.npz" % (name, st)), **arrays)
 
 
 if __name__ == "__main__":

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +14,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "512", "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--nx", "512", "--steps", "6", "--warmup", "2",
                         "--jacobi-sweeps-timed", "20", "--cpu-seconds", "0.5", "--sustained-steps", "200", "--profile-steps", "14"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -62,7 +63,7 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 @pytest.mark.gpu
 def test_bench_default_workload_reports_the_1024_residual_solve():
     """BASELINE configs[1] as a bench leg (small step counts elsewhere to keep it short)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2",
                         "--jacobi-sweeps-timed", "20", "--no-cpu-baseline", "--no-scaling-reference",
                         "--sustained-steps", "100", "--profile-steps", "12"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -84,6 +85,59 @@ def test_bench_defaults_time_a_window_of_at_least_200_steps():
     finally:
         sys.argv = argv
     assert a.steps >= 200 and a.warmup >= 2 and a.profile_steps >= 300 and a.gpus == 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_prints_the_headline_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """Without --full the line is the headline alone; --dump-outputs writes F, u, v, p as the last timed step left them:
+    the same from run to run, and equal to a new handle's fields after warm-up + timed steps."""
+    from vof2d._lib import hip_api
+    from vof2d.engine import Engine, make_desc
+    nx, steps, warmup = 512, 6, 2
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", str(nx), "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append([l for l in r.stdout.splitlines() if l.strip()])
+        assert len(lines[-1]) == 1, r.stdout
+    d = json.loads(lines[0][0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"} <= set(d)
+    assert not {"roofline", "cpu_baseline", "sustained", "step_kernels", "strong_scaling_reference_n1"} & set(d)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "cell-updates/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - nx * nx * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-6 * d["value"]
+    api = hip_api()
+    e = Engine(api, make_desc(api, nx, nx, "f64", "f32", device=0, dt=d["config"]["dt"]))
+    e.set_init_F(1)
+    e.step(warmup + steps)
+    for f in ("F", "u", "v", "p"):
+        x, y = np.load(str(tmp_path / "a" / (f + ".npy"))), np.load(str(tmp_path / "b" / (f + ".npy")))
+        assert x.dtype == np.float64 and x.shape == (nx + 2, nx + 2)
+        assert np.array_equal(x, y), "field %s differs between two runs with the same arguments" % f
+        assert np.array_equal(x, e.get(f)), "field %s is not what the timed steps computed" % f
+    e.close()
+
+
+def test_dump_outputs_samples_a_large_field_the_same_way_every_time(tmp_path):
+    """A field of more than DUMP_SAMPLE_CELLS cells is written as the values at fixed seeded indices; the default workload's
+    four fields (4096^2 fp64) stay within 64 MB; a small field is written whole."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert 4 * bench.DUMP_SAMPLE_CELLS * 8 <= 64 << 20
+    n = 1100
+    big = {"F": np.arange((n + 2) ** 2, dtype=np.float64).reshape(n + 2, n + 2), "u": np.ones((n + 2, n + 2), np.float32)}
+    bench.dump_outputs(str(tmp_path / "a"), big)
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    F = np.load(str(tmp_path / "a" / "F.npy"))
+    assert F.shape == (bench.DUMP_SAMPLE_CELLS,) and F.dtype == np.float64
+    assert np.all(np.diff(F) > 0) and F[-1] < (n + 2) ** 2         # distinct sorted indices into the field
+    assert np.array_equal(F, np.load(str(tmp_path / "b" / "F.npy")))
+    assert np.load(str(tmp_path / "a" / "u.npy")).dtype == np.float32
+    small = np.random.default_rng(1).random((66, 50))
+    bench.dump_outputs(str(tmp_path / "c"), {"p": small})
+    assert np.array_equal(np.load(str(tmp_path / "c" / "p.npy")), small)
 
 
 def test_bench_refuses_a_gpu_count_that_does_not_match_the_launcher():
@@ -170,7 +224,7 @@ def test_bench_strip_path_with_one_rank_native_carrier_and_cost_probe():
     """The N > 1 code path of bench.py driven with one rank (--force-dist): supervisor -> child, EnvComm
     rendezvous, StripSolver, the cost probe + re-cut block (VOF2D_BENCH_TEST_BALANCE), timed region,
     single-GPU reference leg skipped for a non-default grid."""
-    d, err = _run_bench(["--force-dist", "--nx", "1024", "--steps", "6", "--warmup", "2", "--jacobi-sweeps-timed", "20"],
+    d, err = _run_bench(["--full", "--force-dist", "--nx", "1024", "--steps", "6", "--warmup", "2", "--jacobi-sweeps-timed", "20"],
                         env={"VOF2D_BENCH_TEST_BALANCE": "1"})
     assert d["n_gpus"] == 1 and d["config"]["rows_per_rank"] == [1024] and d["value"] > 0
     assert d["config"]["exchange"] == "none" and "cost probe failed" not in err
@@ -178,7 +232,7 @@ def test_bench_strip_path_with_one_rank_native_carrier_and_cost_probe():
 
 @pytest.mark.gpu
 def test_bench_strip_path_with_one_rank_torch_carrier():
-    d, err = _run_bench(["--force-dist", "--exchange", "torch", "--nx", "1024", "--steps", "6", "--warmup", "2",
+    d, err = _run_bench(["--full", "--force-dist", "--exchange", "torch", "--nx", "1024", "--steps", "6", "--warmup", "2",
                          "--jacobi-sweeps-timed", "20"])
     assert d["n_gpus"] == 1 and d["config"]["rows_per_rank"] == [1024] and d["value"] > 0
 
@@ -195,7 +249,7 @@ def test_bench_two_ranks_rehearsed_on_one_device(dtype, nx, overlap):
     from vof2d._lib import hip_api
     from vof2d.engine import Engine, make_desc
     steps, warmup = 7, 4
-    d, err = _run_bench(["--gpus", "2", "--same-device", "--digest", "--nx", str(nx), "--dtype", dtype, "--steps", str(steps), "--warmup", str(warmup),
+    d, err = _run_bench(["--full", "--gpus", "2", "--same-device", "--digest", "--nx", str(nx), "--dtype", dtype, "--steps", str(steps), "--warmup", str(warmup),
                          "--jacobi-sweeps-timed", "20", "--overlap", str(overlap), "--attempt-timeout", "240"], timeout=1500)
     assert d["n_gpus"] == 2 and d["steps"] == steps and d["value"] > 0 and d["scaling"] == "strong"
     c = d["config"]
@@ -220,7 +274,7 @@ def test_bench_two_ranks_rehearsed_on_one_device(dtype, nx, overlap):
 def test_bench_watchdog_falls_back_to_the_second_carrier():
     """A native attempt that hangs (VOF2D_BENCH_TEST_HANG) is killed by the supervisor after
     --attempt-timeout and the torch.distributed carrier produces the line."""
-    d, err = _run_bench(["--force-dist", "--nx", "512", "--steps", "4", "--warmup", "2", "--jacobi-sweeps-timed", "20",
+    d, err = _run_bench(["--full", "--force-dist", "--nx", "512", "--steps", "4", "--warmup", "2", "--jacobi-sweeps-timed", "20",
                          "--attempt-timeout", "8"], env={"VOF2D_BENCH_TEST_HANG": "native"})
     assert "native attempt exceeded" in err and d["value"] > 0
 
@@ -256,7 +310,7 @@ def test_bench_reports_the_form_the_handle_keeps():
     config.step_schedule, config.tm_choice, config.gas_share); `roofline` then names k_tm (8 algorithmic passes), carries
     the Jacobi kernel of the step and the record of the four classic kernels one at a time, and config's per-step byte
     count is the kept form's own kernel list (launches per step x passes), not the four-kernel schedule's 19 passes."""
-    d, _ = _run_bench(["--nx", "3072", "--steps", "16", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--no-scaling-reference",
+    d, _ = _run_bench(["--full", "--nx", "3072", "--steps", "16", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--no-scaling-reference",
                     "--profile-steps", "24"])
     cfg, rf = d["config"], d["roofline"]
     assert cfg["handle_warm_steps"] == 19 and cfg["handle_warm_ms"] > 0

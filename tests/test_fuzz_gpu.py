@@ -29,6 +29,16 @@ if __name__ == "__main__":   # (campaign mode: the paths conftest.py sets up for
 
 from util import STATE, diff_report, engine
 
+
+def hip_runtime():
+    """The HIP runtime the library runs on: its HIP symbols looked up through the library's own handle.  A process that
+    imported torch after loading the library maps two runtimes (torch bundles its own libamdhip64.so), and the bare name
+    "libamdhip64.so" then opens torch's -- whose streams the library's runtime does not know."""
+    import ctypes as C
+    from vof2d._lib import LIB_PATH
+    return C.CDLL(LIB_PATH)
+
+
 SCRATCH = ("u_star", "v_star", "rhs")
 STATS = {"completed": 0, "blew_up": 0, "refused": 0, "ops": 0}   # how the cases of this process ended
 COVERAGE = ("tm_steps", "tm_chained_batches", "pair_launches", "halves_steps")   # counters of the library: cases that ran that form
@@ -610,7 +620,7 @@ def test_create_step_destroy_leaves_no_device_memory_behind(hip_api):
     communicator's worth of graphs is test_host_gpu's business): after 60 create / step / destroy cycles the device has the memory
     it had after the first few, and the last handle still equals the first one's results."""
     import ctypes as C
-    hip = C.CDLL("libamdhip64.so")
+    hip = hip_runtime()
     free, total = C.c_size_t(), C.c_size_t()
 
     def free_bytes():
@@ -644,7 +654,7 @@ def test_handles_on_a_caller_stream_and_two_handles_on_one_stream(hip_api):
     the same handles on streams of their own."""
     import ctypes as C
     from vof2d.engine import Engine, make_desc
-    hip = C.CDLL("libamdhip64.so")
+    hip = hip_runtime()
     st = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(st), 1) == 0      # hipStreamNonBlocking
     specs = [(448, 400, "f64", 1, {"fuse_tm": 1, "overlap_halves": 0}), (700, 260, "f32", 3, {"fuse_tm": 0, "overlap_halves": 2, "batch_steps": 8})]

@@ -6,14 +6,14 @@ import os
 import numpy as np
 import pytest
 
-from util import engine, same, diff_report
+from util import engine, same, diff_report, load_golden
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(HERE, "golden", "*.npz")))
 
 
 def replay(api, name, max_step=None):
-    z = np.load(os.path.join(HERE, "golden", name + ".npz"))
+    z = load_golden(name)
     nx, ny, ic, dt, cast = (int(v) for v in z["meta"])
     e = engine(api, nx, ny, "f64" if dt == 0 else "f32", "f32" if cast else "none", ic=ic)
     assert same(e.get("F"), z["F_0"]), diff_report(e.get("F"), z["F_0"], "F_0")

@@ -16,7 +16,7 @@ import os
 import numpy as np
 import pytest
 
-from util import engine, diff_report
+from util import engine, diff_report, load_golden
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(HERE, "golden", "ref_*.npz")))
@@ -32,7 +32,7 @@ def digest(a):
 
 class Ref:
     def __init__(self, name):
-        self.z = np.load(os.path.join(HERE, "golden", name + ".npz"))
+        self.z = load_golden(name)
         self.nx, self.ny, self.ic = (int(v) for v in self.z["meta"][:3])
         self.dtype = "f32" if int(self.z["meta"][3]) == 1 else "f64"     # f32: the stand-in's --f32 typing emulation
         names = [str(n) for n in self.z["digest_names"]]

@@ -1,9 +1,31 @@
 """Shared helpers of the parity tests."""
+import glob
+import os
+
 import numpy as np
 
 from vof2d.engine import Engine, make_desc
 
 STATE = ("F", "u", "v", "p")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+class GoldenArrays(dict):
+    """The arrays of one golden case, offered like np.load's NpzFile (`.files`, `[name]`)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_golden(name):
+    """golden/<name>.npz together with golden/split/<name>-<step>.npz, where the generator split a case that would
+    exceed the 1 MiB of a committed file (make_ref_golden.py save)."""
+    out = GoldenArrays()
+    for path in [os.path.join(GOLDEN, name + ".npz")] + sorted(glob.glob(os.path.join(GOLDEN, "split", name + "-*.npz"))):
+        with np.load(path) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
 
 
 def engine(api, nx, ny, dtype="f64", coord_cast="f32", ic=None, **kw):
