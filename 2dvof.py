@@ -12,6 +12,7 @@ Extensions (`python 2dvof.py -h`; the reference hard-codes them at :9,:19-20,:52
     --gpus N          row strips over N GPUs of this node (one process per GPU, RCCL halo exchange)
     --verbs           the literal main loop :513-528, one kernel per call
     --jacobi-tol T    residual-terminated pressure solve (--jacobi-max, --jacobi-crit abs|rel)
+    --pressure-solver cg   ... by conjugate gradients instead of sweeps (one GPU)
     --vis K           what the reference GUI would display (:531-559), saved with -s
     --save-every N    data/NNNNNNNN.npz checkpoints;  --resume FILE continues from one
 

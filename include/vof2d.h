@@ -144,6 +144,20 @@ int vof_set_istep(vof2d_handle h, int64_t istep);
 #define VOF_RESID_TINY 1e-300
 int vof_solve_p(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every, int32_t criterion,
                 int32_t* iters_done, double* residual);
+/* Extension: the same pressure equation solved by preconditioned conjugate gradients instead of sweeps.
+ * The right-hand side b (the field "rhs") of the pure-Neumann problem does not sum to zero, so the sweeps have no fixed
+ * point: they tend to the p for which one more sweep adds the same constant c = sum(b) / sum(ap) to every cell.  This
+ * verb solves for that p -- L p = b - c ap, with L and ap the stencil of :258-263 -- by conjugate gradients on -L
+ * preconditioned with its diagonal, warm-started from the p of the handle, whose additive constant it keeps.  With
+ * r = (b - c ap) - L p and z = r / ap ("what one more sweep would still change, beyond the drift"):
+ *   VOF_RESID_ABS:  residual = max|z|                                     over the interior
+ *   VOF_RESID_REL:  residual = max|z| / max(max|p|, VOF_RESID_TINY)
+ * through vof_residual_value; r is recomputed from p at the start and at every check (every check_every iterations, at
+ * most max_iters).  A start that satisfies tol returns 0 iterations; a non-finite value reads as +inf and ends the
+ * solve.  build_rhs as in vof_jacobi_sweeps_norms.  *drift receives c.  All sums are formed in double in a fixed
+ * order: the same state and call give the same bits.  Whole-domain handles only (a strip returns VOF_ESTATE). */
+int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every, int32_t criterion,
+                   int32_t build_rhs, int32_t* iters_done, double* residual, double* drift);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

@@ -142,6 +142,12 @@ struct vof2d_ctx {
   unsigned long long* d_courant = nullptr;  // device counters: [0] courant, [1] max|p_new - p| bits, [2] max|p_new| bits (residual solve)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int64_t istep = 0;
+  // conjugate-gradient pressure solve (vof_solve_p_cg): work arrays in the fields' layout, allocated by the first call
+  char* cg_arena = nullptr;     // r, two direction arrays (ping-pong), q
+  void* cg_fld[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* cg_part = nullptr;    // one partial per block (kCgPart doubles), then the CG_NSCAL device scalars
+  double* cg_sc = nullptr;
+  int cg_s = 1;                 // which of cg_fld[1..2] holds the current direction
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)
@@ -229,8 +235,8 @@ struct vof2d_ctx {
   hipEvent_t tev[2 * kMaxTimed] = {};
   int timed = -1;             // -1: off; otherwise launches recorded in the current batch
   int tkid[kMaxTimed];        // kernel id of each recorded launch
-  double prof_sum_ms[16] = {};
-  long prof_cnt[16] = {};
+  double prof_sum_ms[24] = {};   // (>= NKERNELS of launches.h)
+  long prof_cnt[24] = {};
   std::map<const void*, long> occ_cache;  // resident waves per kernel function (resident_waves)
   // strip halo exchange over RCCL (vof_comm_init): own communicator, stream and events
   void* comm = nullptr;          // ncclComm_t

@@ -126,10 +126,12 @@ inline bool buffer_stores_ok(const vof2d_ctx* h) {
 constexpr long kTmAlwaysCells = 16000000L;
 constexpr long kTbPlanWaves = 16384;   // waves of a k_jacobi_tb launch the work plan can describe
 enum KernelId { kMomentum = 0, kSetBC, kJacobi, kJacobiTB, kCorrect, kFctX, kFctY, kNormals, kKappa, kPredictor,
-                kRhs, kOther, kTransport, kJacobiPair, kTM, kTMUV, NKERNELS };
+                kRhs, kOther, kTransport, kJacobiPair, kTM, kTMUV, kCgApply, kCgUpdate, kCgResidual, kCgFinish, NKERNELS };
+static_assert(NKERNELS <= 24, "vof2d_ctx::prof_sum_ms / prof_cnt");
 const char* const kKernelNames[NKERNELS] = {"k_momentum", "k_set_bc", "k_jacobi", "k_jacobi_tb", "k_correct",
                                             "k_fct_x", "k_fct_y", "k_normals", "k_kappa", "k_predictor", "k_rhs",
-                                            "other", "k_transport", "k_jacobi_pair", "k_tm", "k_tm_uv"};   // (k_tm_uv: the k_tm launch that also stores u, v -- the last of a batch)
+                                            "other", "k_transport", "k_jacobi_pair", "k_tm", "k_tm_uv",
+                                            "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish"};   // (k_tm_uv: the k_tm launch that also stores u, v -- the last of a batch)
 
 // One place through which every kernel is launched.  In profiling mode the dispatch carries its
 // own start/stop events (hipExtLaunchKernelGGL: the begin/end timestamps of the dispatch itself,
@@ -459,6 +461,56 @@ struct L {
       launch_block(h, STORE_UV ? kTMUV : kTM, k_tm<T, VV, YFIRST, STORE_UV, false>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
              (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
              F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, h->tm_rhs_alt ? fKAPPA : fRHS), h->d_courant, R, tp, first, last, first2, last2);
+  }
+  // ---- conjugate gradients (kernels/cg.h): work arrays h->cg_fld = r, s (two, ping-pong), q
+  // rows per wave chunk: the pointwise kernels and the residual like every streaming kernel (pick_rows); k_cg_apply forms
+  // the direction of one extra row above and below its chunk, so its chunks are twice as long
+  static int cg_rows(const vof2d_ctx* h, bool apply) { return (apply ? 2 : 1) * pick_rows(h, h->g.ntj); }
+  static unsigned cg_blocks(const vof2d_ctx* h, bool apply) { return blocks_for(h, h->g.ntj, cg_rows(h, apply)); }
+  // sum of ap over the interior, in double, of the values the kernels form in T: ap depends on the position through
+  // "first / last row or not" and "first / last column or not" only (2dvof.py:258-262), four values with their counts
+  static double cg_sum_ap(const vof2d_ctx* h) {
+    const Consts<T> c = C(const_cast<vof2d_ctx*>(h));
+    const T zero = (T)0.0;
+    const T ax[2] = {c.dxi2 + zero, c.dxi2 + c.dxi2};          // ae + aw: wall row, inner row
+    const double nrow[2] = {2.0, (double)(h->g.nx - 2)}, ncol[2] = {2.0, (double)(h->g.ny - 2)};
+    double sum = 0.0;
+    for (int a = 0; a < 2; ++a) {
+      const T wall = (T)-1.0 * (ax[a] + c.dyi2 + zero), inner = (T)-1.0 * (ax[a] + c.dyi2 + c.dyi2);
+      sum += nrow[a] * (ncol[0] * (double)wall + ncol[1] * (double)inner);
+    }
+    return sum;
+  }
+  static void cg_finish(vof2d_ctx* h, unsigned nblocks, int mode, double sum_ap = 0.0, int restart = 0) {
+    launch(h, kCgFinish, k_cg_finish, dim3(1), 0, (const double*)h->cg_part, (int)nblocks, h->cg_sc, mode, sum_ap, restart);
+  }
+  // c = sum(b) / sum(ap) into the device scalars
+  static void cg_drift(vof2d_ctx* h, double sum_ap) {
+    const unsigned nb = cg_blocks(h, false);
+    launch(h, kCgResidual, k_cg_sum<T, V>, dim3(nb), 0, h->g, (const T*)F_<T>(h, fRHS), cg_rows(h, false), h->cg_part);
+    cg_finish(h, nb, CG_FIN_SUMB, sum_ap);
+  }
+  static void cg_residual(vof2d_ctx* h, int restart) {
+    const unsigned nb = cg_blocks(h, false);
+    launch(h, kCgResidual, k_cg_residual<T, V>, dim3(nb), 0, h->g, C(h), (const T*)F_<T>(h, fP), (const T*)F_<T>(h, fRHS),
+           reinterpret_cast<T*>(h->cg_fld[0]), cg_rows(h, false), (const double*)h->cg_sc, h->cg_part);
+    cg_finish(h, nb, CG_FIN_RESID, 0.0, restart);
+  }
+  // one iteration: two field kernels, each followed by its one-block reduction
+  static void cg_iteration(vof2d_ctx* h) {
+    const Consts<T> cc = C(h);
+    T* const r = reinterpret_cast<T*>(h->cg_fld[0]);
+    T* const s_old = reinterpret_cast<T*>(h->cg_fld[h->cg_s]);
+    h->cg_s = 3 - h->cg_s;
+    T* const s_new = reinterpret_cast<T*>(h->cg_fld[h->cg_s]);
+    T* const q = reinterpret_cast<T*>(h->cg_fld[3]);
+    const unsigned na = cg_blocks(h, true), nu = cg_blocks(h, false);
+    launch(h, kCgApply, k_cg_apply<T, V>, dim3(na), 0, h->g, cc, (const T*)r, (const T*)s_old, s_new, q, cg_rows(h, true),
+           (const double*)h->cg_sc, h->cg_part);
+    cg_finish(h, na, CG_FIN_APPLY);
+    launch(h, kCgUpdate, k_cg_update<T, V>, dim3(nu), 0, h->g, cc, F_<T>(h, fP), (const T*)s_new, r, (const T*)q, cg_rows(h, false),
+           (const double*)h->cg_sc, h->cg_part);
+    cg_finish(h, nu, CG_FIN_UPDATE);
   }
   // update_uv + both sweeps + post_process_f in one pass (k_transport); reads fld[fF], writes fld[fF2]
   static int transport_rows(const vof2d_ctx* h) {

@@ -145,6 +145,8 @@ int vof_destroy(vof2d_handle h) {
 #endif
   if (h->d_courant) (void)hipFree(h->d_courant);
   if (h->d_tbmask) (void)hipFree(h->d_tbmask);
+  if (h->cg_arena) (void)hipFree(h->cg_arena);
+  if (h->cg_part) (void)hipFree(h->cg_part);
   if (h->arena) (void)hipFree(h->arena);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -599,6 +601,65 @@ int vof_solve_p(vof2d_handle h, double tol, int32_t max_iters, int32_t check_eve
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every, int32_t* iters_done,
                          double* residual) {
   return vof_solve_p(h, tol, max_iters, check_every, VOF_RESID_ABS, iters_done, residual);
+}
+
+// ---- conjugate-gradient pressure solve (kernels/cg.h)
+static int cg_prepare(vof2d_ctx* h) {
+  if (h->cg_arena) return VOF_OK;
+  const size_t fbytes = h->field_elems * h->esz;
+  const size_t nblocks = blocks_for(h, h->g.ntj, 1);   // (the most blocks a launch can have: one-row chunks, knob "rows_per_wave")
+  const size_t pbytes = (nblocks * kCgPart + CG_NSCAL) * sizeof(double);
+  if (hipMalloc(reinterpret_cast<void**>(&h->cg_arena), 4 * fbytes) != hipSuccess) {
+    (void)hipGetLastError();
+    h->cg_arena = nullptr;
+    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the work arrays");
+  }
+  if (hipMalloc(reinterpret_cast<void**>(&h->cg_part), pbytes) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(h->cg_arena);
+    h->cg_arena = nullptr; h->cg_part = nullptr;
+    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the reduction buffer");
+  }
+  for (int k = 0; k < 4; ++k) h->cg_fld[k] = h->cg_arena + (size_t)k * fbytes;
+  h->cg_sc = h->cg_part + nblocks * kCgPart;
+  // cells outside the interior are never written again: they stay 0 (kernels/cg.h, k_cg_apply)
+  HIPCHK(h, hipMemsetAsync(h->cg_arena, 0, 4 * fbytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->cg_part, 0, pbytes, h->stream));
+  return VOF_OK;
+}
+int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every, int32_t criterion,
+                   int32_t build_rhs, int32_t* iters_done, double* residual, double* drift) {
+  if (!h || !iters_done || !residual || !drift) return VOF_EINVAL;
+  if (max_iters < 1 || check_every < 1) return fail(h, VOF_EINVAL, "max_iters and check_every must be >= 1");
+  if (criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
+  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
+    return fail(h, VOF_ESTATE, "vof_solve_p_cg needs the whole domain in one handle (the dot products of a strip would need an all-reduce)");
+  settle_ghosts(h);
+  int rc = cg_prepare(h);
+  if (rc) return rc;
+  if (build_rhs) DISPATCH_T(h, L<double>::rhs<false>(h), L<float>::rhs<false>(h));
+  // a new solve starts from the steepest-descent direction: beta = 0 and a clean direction array
+  HIPCHK(h, hipMemsetAsync(h->cg_fld[1], 0, 2 * h->field_elems * h->esz, h->stream));
+  const double sum_ap = DISPATCH_B(h, L<double>::cg_sum_ap(h), L<float>::cg_sum_ap(h));
+  DISPATCH_T(h, (L<double>::cg_drift(h, sum_ap), L<double>::cg_residual(h, 1)), (L<float>::cg_drift(h, sum_ap), L<float>::cg_residual(h, 1)));
+  int done = 0;
+  double r = 0.0, sc[CG_NSCAL];
+  for (;;) {
+    if ((rc = ensure_ok(h))) return rc;
+    HIPCHK(h, hipMemcpyAsync(sc, h->cg_sc, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    r = vof_residual_value(sc[CG_MAXZ], sc[CG_MAXP], criterion);
+    if (r <= tol || !(r < HUGE_VAL)) break;   // converged, or a non-finite field
+    if (done >= max_iters || sc[CG_STOP] != 0.0) break;   // the cap, or a direction with nothing to divide by: reported as it is
+    const int n = check_every < max_iters - done ? check_every : max_iters - done;
+    for (int k = 0; k < n; ++k) DISPATCH_T(h, L<double>::cg_iteration(h), L<float>::cg_iteration(h));
+    done += n;
+    DISPATCH_T(h, L<double>::cg_residual(h, 0), L<float>::cg_residual(h, 0));
+  }
+  *iters_done = done;
+  *residual = r;
+  *drift = sc[CG_C];
+  return VOF_OK;
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

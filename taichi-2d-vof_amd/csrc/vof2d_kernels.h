@@ -17,6 +17,7 @@
 //   jacobi_pair.h  k_jacobi_pair   (two k_jacobi_tb launches as one: pairs of waves, result and rhs rows through LDS)
 //   transport.h  k_fct_x, k_fct_y, k_transport   (update_uv + solve_VOF_rudman + post_process_f)
 //   fused_tm.h   k_tm   (k_transport of one step + k_momentum of the next, rows handed over through LDS)
+//   cg.h         k_cg_apply, k_cg_update, k_cg_residual   (extension: conjugate gradients on the pressure equation)
 #pragma once
 #include "kernels/common.h"
 #include "kernels/verbs.h"
@@ -26,3 +27,4 @@
 #include "kernels/jacobi_pair.h"
 #include "kernels/transport.h"
 #include "kernels/fused_tm.h"
+#include "kernels/cg.h"

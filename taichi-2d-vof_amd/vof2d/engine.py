@@ -158,6 +158,16 @@ class Engine:
                                   C.byref(it), C.byref(res)), "solve_p")
         return it.value, res.value
 
+    def solve_p_cg(self, tol, max_iters, check_every=10, criterion="abs", build_rhs=True):
+        """vof_solve_p_cg: conjugate gradients on the pressure equation until max|z| (\"abs\"; \"rel\": over
+        max(max|p|, tiny)) is <= tol, z = what one more Jacobi sweep would change beyond the drift constant;
+        returns (iterations done, residual, drift)."""
+        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        it, res, drift = C.c_int32(), C.c_double(), C.c_double()
+        self._ck(self.api.solve_p_cg(self._h, float(tol), int(max_iters), int(check_every), crit,
+                                     1 if build_rhs else 0, C.byref(it), C.byref(res), C.byref(drift)), "solve_p_cg")
+        return it.value, res.value, drift.value
+
     def jacobi_sweeps_norms(self, n, build_rhs=True):
         """(max|p_new - p|, max|p_new|) of the last of n sweeps over the owned rows."""
         upd, pm = C.c_double(), C.c_double()
@@ -280,7 +290,8 @@ class Engine:
         self._ck(self.api.profile_steps(self._h, int(nsteps)), "profile_steps")
         out = {}
         for k in ("k_momentum", "k_set_bc", "k_jacobi", "k_jacobi_tb", "k_correct", "k_fct_x", "k_fct_y",
-                  "k_transport", "k_normals", "k_kappa", "k_predictor", "k_rhs", "k_jacobi_pair", "k_tm", "k_tm_uv"):
+                  "k_transport", "k_normals", "k_kappa", "k_predictor", "k_rhs", "k_jacobi_pair", "k_tm", "k_tm_uv",
+                  "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish"):
             us, n = C.c_double(), C.c_int64()
             if self.api.get_profile(self._h, k.encode(), C.byref(us), C.byref(n)) != 0:
                 continue   # a kernel this build of the library does not have

@@ -85,6 +85,9 @@ class VOF2D:
     def solve_p_jacobi(self, n=1):
         self.eng.solve_p_jacobi(n)
 
+    def solve_p_cg(self, tol, max_iters, check_every=10, criterion="abs", build_rhs=True):
+        return self.eng.solve_p_cg(tol, max_iters, check_every, criterion, build_rhs)
+
     def update_uv(self):
         self.eng.update_uv()
 
