@@ -1,9 +1,9 @@
 // runtime/comm.h -- strips over RCCL: run-time binding (dlopen), the halo send/recv groups, the step with its exchanges
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, schedule.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
-#include "schedule.h"
+#include "step.h"
 
 namespace {
 
@@ -65,7 +65,7 @@ Rccl* rccl_bind(Rccl& r) {
 void comm_teardown(vof2d_ctx* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->cstream) (void)hipStreamSynchronize(h->cstream);
-  destroy_xchg_graphs(h);  // captured send/recv nodes hold the communicator: they go first
+  h->graphs.clear_exchange();  // captured send/recv nodes hold the communicator: they go first
   if (h->d_red) { (void)hipFree(h->d_red); h->d_red = nullptr; }
   if (h->comm && rccl()) (void)rccl()->CommDestroy(h->comm);
   h->comm = nullptr;
@@ -75,7 +75,6 @@ void comm_teardown(vof2d_ctx* h) {
     if (h->ev_fork[k]) (void)hipEventDestroy(h->ev_fork[k]);
     h->ev_fork[k] = nullptr;
   }
-  destroy_xchg_graphs(h);
   if (h->cstream) (void)hipStreamDestroy(h->cstream);
   h->ev_ready = h->ev_done = nullptr;
   h->cstream = nullptr;
@@ -86,17 +85,6 @@ void comm_teardown(vof2d_ctx* h) {
 // halo rows in, per side -- a row is `pitch` contiguous elements, so each message is one contiguous
 // block of field memory (no packing).  One RCCL group on the communication stream, ordered after
 // everything enqueued on the compute stream so far; the compute stream does not wait (comm_join).
-void destroy_xchg_graphs(vof2d_ctx* h) {
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 5; ++b)
-      for (int o = 0; o < 2; ++o)
-        if (h->gxchg[a][b][o]) { (void)hipGraphExecDestroy(h->gxchg[a][b][o]); h->gxchg[a][b][o] = nullptr; }
-  for (int a = 0; a < 2; ++a)
-    for (int o = 0; o < 2; ++o)
-      if (h->gxchg2[a][o]) { (void)hipGraphExecDestroy(h->gxchg2[a][o]); h->gxchg2[a][o] = nullptr; }
-  for (int k = 0; k < 16; ++k)
-    if (h->gxchg5[k]) { (void)hipGraphExecDestroy(h->gxchg5[k]); h->gxchg5[k] = nullptr; }
-}
 // (s_in_alt: between the launches of k_tm and the host's swap the new u*, v* still live in the mx / my arrays;
 // on_cstream: whatever the messages wait for was enqueued on the communication stream itself)
 constexpr int kTmBandRows = 6;    // rows per pair chunk of k_tm's edge-band launch
@@ -292,6 +280,168 @@ int enqueue_tail_step5(vof2d_ctx* h) {
   swap_F(h);
   if ((rc = comm_join(h))) return rc;
   if (!h->virtual_ghosts) L<T>::template set_bc<BC_ALL>(h);
+  return VOF_OK;
+}
+
+// ---- the steps of a strip with their exchanges (vof_step_exchange)
+// a capture that failed after the fork may leave a communication stream inside the invalidated capture: the eager launches
+// that follow need working ones
+bool comm_streams_usable_after_failed_capture(vof2d_ctx* h) {
+  for (hipStream_t* st : {&h->cstream}) {
+    if (!*st) continue;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(*st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+      (void)hipGetLastError();
+      (void)hipStreamDestroy(*st);
+      *st = nullptr;
+      if (hipStreamCreateWithFlags(st, hipStreamNonBlocking) != hipSuccess) return false;
+    }
+  }
+  return true;
+}
+// Captures the steps `enqueue` launches, exchanges included, into *slot -- or, if this RCCL / runtime cannot capture them,
+// switches the form off (*form_on = 0) and leaves the caller to carry on with `fallback`.  An error only where not even
+// that is possible.
+template <typename Enqueue>
+int capture_exchange_or_switch_off(vof2d_ctx* h, hipGraphExec_t* slot, int* form_on, const char* what, const char* fallback, Enqueue&& enqueue) {
+  const bool dbg = getenv("VOF2D_DEBUG") != nullptr;
+  if (dbg) fprintf(stderr, "[vof2d] capturing %s (parity %d)\n", what, (int)(h->istep & 1));
+  const hipError_t e = capture_graph(h, hipStreamCaptureModeRelaxed, /*upload=*/false, slot, [&] {
+    const int rc = enqueue();
+    if (dbg) fprintf(stderr, "[vof2d]   enqueued (rc %d), ending capture\n", rc);
+    return rc == VOF_OK;
+  });
+  if (e == hipSuccess) return VOF_OK;
+  (void)hipGetLastError();
+  *form_on = 0;
+  if (!comm_streams_usable_after_failed_capture(h)) return fail(h, VOF_EHIP, "cannot recreate the communication stream after a failed capture");
+  if (dbg) fprintf(stderr, "[vof2d] capture of %s failed (%s / %s): %s\n", what, hipGetErrorString(e), h->err, fallback);
+  return VOF_OK;
+}
+
+// the kernels of mode 5 need: two-column tiles whose lanes are stored or skipped together, square cells or not (k_jacobi_pair
+// falls back to two k_jacobi_tb launches), the fused transport and its virtual ghosts
+bool mode5_ok(const vof2d_ctx* h) {
+  return h->fuse_transport && h->tb >= 5 && h->d.jacobi_iters % 5 == 0 && h->d.jacobi_iters >= 5 && h->g.nx >= 16;
+}
+// n steps of mode 5: see include/vof2d.h.  The middle steps are replayed two per hipGraph launch (all three pairs of
+// arrays -- F / twin, u* v* / mx my, p / pt -- are back where they were after two steps); the head and the tail of a
+// call, and an odd middle step, are launched eagerly.
+int step_exchange_mode5(vof2d_ctx* h, int64_t nsteps) {
+  int rc;
+  if (!mode5_ok(h)) return fail(h, VOF_ESTATE, "overlap mode 5 needs the fused transport and five-sweep Jacobi launches");
+  if (nsteps == 0) return VOF_OK;
+  if (h->f_ghosts_dirty || h->uv_ghosts_dirty || h->xchg_steps == 0) {
+    // the first step after set_init_F / set_field (the reference's intermediate set_BC calls), and the first of a
+    // communicator (RCCL connects on first use): a step of mode 1
+    if ((rc = vof_step_exchange(h, 1, 1))) return rc;
+    if (--nsteps == 0) return VOF_OK;
+  }
+  const bool want_graph = !(h->d.flags & VOF_FLAG_NO_GRAPH) && h->xchg_graph;
+  // head
+  DISPATCH_T(h, tm5_head<double>(h), tm5_head<float>(h));
+  if ((rc = comm_post(h, VOF_XCHG_US | VOF_XCHG_VS | VOF_XCHG_RHS))) return rc;
+  if ((rc = comm_join(h))) return rc;
+  int64_t mid = nsteps - 1;
+  auto mid_step = [&]() -> int {
+    h->istep += 1;
+    int r2 = VOF_OK;
+    DISPATCH_T(h, r2 = enqueue_mid_step5<double>(h), r2 = enqueue_mid_step5<float>(h));
+    return r2;
+  };
+  auto eager_mid = [&] { h->xchg_steps += 1; return mid_step(); };
+  if (mid & 1) { if ((rc = eager_mid())) return rc; mid -= 1; }
+  while (mid > 0) {
+    hipGraphExec_t& exec = h->graphs.xchg5[xchg5_key(h)];
+    if (want_graph && h->xchg5_graph && !exec &&
+        (rc = capture_exchange_or_switch_off(h, &exec, &h->xchg5_graph, "two middle steps of mode 5", "eager", [&] { const int r2 = mid_step(); return r2 ? r2 : mid_step(); })))
+      return rc;
+    if (want_graph && h->xchg5_graph && exec) {
+      HIPCHK(h, hipGraphLaunch(exec, h->stream));
+      h->istep += 2;
+      h->xchg_steps += 2;
+      h->xchg_graph_steps += 2;
+    } else {
+      if ((rc = eager_mid()) || (rc = eager_mid())) return rc;
+    }
+    mid -= 2;
+  }
+  // tail
+  h->istep += 1;
+  DISPATCH_T(h, rc = enqueue_tail_step5<double>(h), rc = enqueue_tail_step5<float>(h));
+  if (rc) return rc;
+  h->xchg_steps += 1;
+  h->ghosts_virtual = h->virtual_ghosts != 0;
+  return ensure_ok(h);
+}
+
+// nsteps steps of overlap mode 0, 1, 3 or 4, each with its exchanges
+int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
+  const bool want_graph = !(h->d.flags & VOF_FLAG_NO_GRAPH);
+  GraphCache& G = h->graphs;
+  auto one_step = [&]() -> int {
+    int r2 = VOF_OK;
+    DISPATCH_T(h, r2 = enqueue_step_exchange<double>(h, overlap), r2 = enqueue_step_exchange<float>(h, overlap));
+    return r2;
+  };
+  for (int64_t s = 0; s < nsteps; ++s) {
+    // the captured step leaves the ghost cells virtual (if the handle does that at all); every other
+    // way through this loop wants them settled first
+    const bool captured_path = want_graph && h->xchg_graph && h->xchg_steps > 0 && !h->f_ghosts_dirty && !h->uv_ghosts_dirty;
+    const bool virt = captured_path && h->virtual_ghosts;
+    if (!virt) settle_ghosts(h);
+    h->istep += 1;
+    const int par = (int)(h->istep & 1), ori = ori_F(h);
+    int rc;
+    // The first step of a communicator runs eagerly: RCCL sets its peer connections up on first
+    // use, which must not happen inside a capture.  After that the whole step -- kernels on the
+    // compute stream, the send/recv groups forked onto the communication stream, the join -- is
+    // one hipGraph per (sweep order, mode): one launch per step instead of four graph launches
+    // and three RCCL group launches (~100 us of host time each).
+    // Two mode-4 steps per graph launch (a graph launch leaves ~9 us of idle queue behind it, see step.h):
+    // only once both single-step graphs of this handle exist, i.e. this RCCL has shown that it can be
+    // captured; two steps return the F / twin pair and the parity to where they were.
+    if (captured_path && overlap == 4 && h->xchg_pair && virt && nsteps - s >= 2 && G.xchg[par][4][ori] && G.xchg[par ^ 1][4][ori ^ 1]) {
+      if (!G.xchg2[par][ori] &&
+          (rc = capture_exchange_or_switch_off(h, &G.xchg2[par][ori], &h->xchg_pair, "two steps + exchanges", "one step per launch (those graphs are known to work)", [&] {
+             const int r2 = one_step();
+             h->istep += 1;
+             return r2 ? r2 : one_step();
+           })))
+        return rc;
+      if (G.xchg2[par][ori]) {
+        HIPCHK(h, hipGraphLaunch(G.xchg2[par][ori], h->stream));
+        h->istep += 1;
+        s += 1;
+        h->xchg_steps += 2;
+        h->xchg_graph_steps += 2;
+        h->ghosts_virtual = virt;
+        continue;
+      }
+    }
+    if (captured_path) {
+      hipGraphExec_t& exec = G.xchg[par][overlap][ori];
+      if (!exec && (rc = capture_exchange_or_switch_off(h, &exec, &h->xchg_graph, "step + exchanges", "eager", one_step))) return rc;
+      if (exec) {
+        HIPCHK(h, hipGraphLaunch(exec, h->stream));
+        if (overlap == 4) swap_F(h);   // the fused transport swaps the F / twin pair once per step
+        h->xchg_steps += 1;
+        h->xchg_graph_steps += 1;
+        h->ghosts_virtual = virt;
+        continue;
+      }
+    }
+    h->istep -= 1;  // vof_step_phase(0) advances it
+    const int eo = overlap == 4 ? 1 : overlap;   // eager steps (the first of a communicator, ...) of mode 4 run as mode 1
+    if ((rc = vof_step_phase(h, 0))) return rc;
+    if (eo == 1 && (rc = comm_post(h, VOF_XCHG_P))) return rc;
+    if ((rc = vof_step_phase(h, 1))) return rc;
+    if (eo && (rc = comm_post(h, eo == 3 ? (VOF_XCHG_P | VOF_XCHG_U | VOF_XCHG_V) : (VOF_XCHG_U | VOF_XCHG_V)))) return rc;
+    if ((rc = vof_step_phase(h, 2))) return rc;
+    if ((rc = comm_post(h, eo ? VOF_XCHG_F : (VOF_XCHG_F | VOF_XCHG_U | VOF_XCHG_V | VOF_XCHG_P)))) return rc;
+    if ((rc = comm_join(h))) return rc;
+    h->xchg_steps += 1;
+  }
   return VOF_OK;
 }
 

@@ -1,7 +1,8 @@
 // runtime/context.h -- field ids, constants folded like the reference does, the handle (vof2d_ctx), error helpers
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, schedule.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h (and diag.h in the diagnostic build).  Everything
+// here has internal linkage.
 #pragma once
 #include <vector>
 
@@ -126,6 +127,47 @@ bool divisors_ok(const ConstsD& s) {
 
 }  // namespace
 
+// Every captured graph of a handle (runtime/graphs.h captures them; ori: ori_F).  Nothing but exec handles, so the whole
+// cache, and the part of it whose graphs captured send / recv nodes, are flat ranges of them.
+struct GraphCache {
+  static constexpr int kStepBatches = 3;
+  hipGraphExec_t step[2][2] = {};                      // whole step, [istep parity][ori]
+  // several consecutive steady-state steps of a full domain as ONE graph (step_batch[b] steps, an even number: the
+  // F / twin pair and the step parity are back where they started): a graph launch leaves ~9 us of idle queue
+  // behind it, which one launch per step pays every step (step.h)
+  hipGraphExec_t batch[2][kStepBatches][2][2] = {};    // [form: 0 chains or the plain sequence, 1 k_tm][batch size][parity of the first step][ori]
+  hipGraphExec_t phase[5] = {};                        // phase 0, then phases 1, 2 x istep parity (slot 2 * phase - 1 + parity)
+  // ---- from here on: with the exchanges of a strip (they hold the communicator: clear_exchange)
+  hipGraphExec_t xchg[2][5][2] = {};                   // whole step + exchanges, [istep parity][overlap mode][ori]
+  hipGraphExec_t xchg2[2][2] = {};                     // TWO mode-4 steps + exchanges per launch, [parity of the first][ori] (comm.h)
+  hipGraphExec_t xchg5[16] = {};                       // TWO middle steps of mode 5 per launch, [xchg5_key]
+
+  hipGraphExec_t* begin() { return &step[0][0]; }
+  hipGraphExec_t* end() { return xchg5 + 16; }
+  static bool any(hipGraphExec_t* a, hipGraphExec_t* b) { while (a != b && !*a) ++a; return a != b; }
+  static void clear(hipGraphExec_t* a, hipGraphExec_t* b) {
+    for (; a != b; ++a)
+      if (*a) { (void)hipGraphExecDestroy(*a); *a = nullptr; }
+  }
+  bool any() { return any(begin(), end()); }
+  void clear() { clear(begin(), end()); }
+  void clear_exchange() { clear(&xchg[0][0][0], end()); }
+};
+static_assert(sizeof(GraphCache) == (4 + 4 * GraphCache::kStepBatches * 2 + 5 + 20 + 4 + 16) * sizeof(hipGraphExec_t), "GraphCache is walked as one array");
+
+// knob "fuse_tm" = -2 (exploration): both forms of the batch graphs timed on the handle's own data (tune_next_is_timed, step.h);
+// `choice` and `decided` also carry what the rule of fuse_tm = -1 found (decide_batch_form_by_rule)
+struct TuneState {
+  int n = 0;             // timed batches so far (even: chains / plain, odd: k_tm); 4: ready to decide; 5: decided
+  int choice = 0;        // the form that stays -- until the next timing: every `period` batches the two forms are timed
+  int period = 2048;     // again (a flow changes character over 16 000 steps; four alternating batches cost next to nothing)
+  int age = 0;           // batches since the last decision
+  bool decided = false;  // a decision has been made since the graphs were built
+  hipEvent_t ev[8] = {};
+  float ms[2] = {0.f, 0.f};
+  void reset() { n = 0; age = 0; decided = false; ms[0] = ms[1] = 0.f; }   // (a changed knob changes what is being compared)
+};
+
 struct vof2d_ctx {
   vof2d_desc d;
   ConstsD cd;
@@ -165,24 +207,20 @@ struct vof2d_ctx {
   void* f_home = nullptr;  // the buffer fld[fF] pointed to at creation (orientation of the F / twin pair)
   void* us_home = nullptr; // ... fld[fUS] (the u*, v* pair alternates with mx, my in the k_tm forms) and fld[fP] (k_jacobi_pair alternates p / pt)
   void* p_home = nullptr;
-  int phase_graph_ori = 0; // orientation the gphase / gxchg graphs were captured in
-  hipGraphExec_t gexec[2][2] = {};  // whole step, [istep parity][F in its home buffer ? 0 : 1]
-  // several consecutive steady-state steps of a full domain as ONE graph (step_batch[b] steps, an even number: the
-  // F / twin pair and the step parity are back where they started): a graph launch leaves ~9 us of idle queue
-  // behind it, which one launch per step pays every step (vof_step)
-  static constexpr int kStepBatches = 3;
+  int phase_graph_ori = 0; // orientation the phase graphs were captured in
+  GraphCache graphs;
+  static constexpr int kStepBatches = GraphCache::kStepBatches;
   static constexpr int kTuneBatch = 1;     // the batch size the two forms are timed with (fuse_tm = -2)
   // (the k_tm form has one plain k_momentum and one plain k_transport per batch: 4096^2 0.5256 ms/step in batches of 8, 0.5193 of 16,
   // 0.5178 of 32, 0.5346 of 4; knob "batch_steps" sets the first)
   int step_batch[kStepBatches] = {16, 8, 2};
-  hipGraphExec_t gbatch[kStepBatches][2][2] = {};   // [batch size][parity of the first step][orientation]
   // knob "overlap_halves": the batch graphs run every kernel of a step as two launches, on the rows above and below a
   // boundary that moves up by kHalvesDrift rows from kernel to kernel, the upper chain on `stream`, the lower on
   // `chain_streams`; a lower launch waits for the upper launch of the kernel before it only (enqueue_steps_halves)
   // knob "fuse_tm": the batch graphs run k_transport + the next step's k_momentum as one kernel (k_tm, kernels/fused_tm.h):
   // 0 never, 1 wherever the schedule allows, -1 (default) on large fp64 grids by a rule on the state (the share of gas
   // cells: decide_batch_form_by_rule), -2 (exploration) after timing both forms on the handle's own data: four 8-step
-  // batches alternate between the forms, the faster one stays (vof_step)
+  // batches alternate between the forms, the faster one stays (step.h)
   int fuse_tm = -1;
   double gas_share = -1.0;   // what the rule saw (get_param "gas_share")
   unsigned long long* h_gas = nullptr;   // pinned host word the count of exact-zero cells of F lands in (post_gas_count)
@@ -206,14 +244,7 @@ struct vof2d_ctx {
   bool jpair_active = false; // the launches being enqueued are k_jacobi_pair's (tb_plan describes their geometry)
   bool jpair_captured = false;   // the k_tm batch graphs the handle holds contain k_jacobi_pair launches
   int64_t pair_launches = 0; // k_jacobi_pair launches replayed (counter "pair_launches")
-  hipGraphExec_t gbatch_tm[kStepBatches][2][2] = {};   // the k_tm form of gbatch
-  int tune_n = 0;            // timed batches so far (even: chains / plain, odd: k_tm); 4: ready to decide; 5: decided
-  int tm_choice = 0;         // the form that stays -- until the next timing: every tune_period batches the two forms are timed
-  int tune_period = 2048;    // again (a flow changes character over 16 000 steps; four alternating batches cost next to nothing)
-  int tune_age = 0;          // batches since the last decision
-  bool tm_decided = false;   // a decision has been made since the graphs were built
-  hipEvent_t tune_ev[8] = {};
-  float tune_ms[2] = {0.f, 0.f};
+  TuneState tune;
   int64_t tm_steps = 0;      // steps replayed from k_tm batch graphs (counter "tm_steps")
   int tm_rows = 0;          // rows per pair chunk of k_tm (0 = 32)
   int halves = -1;   // -1: where it pays (halves_eligible), 0: never, 1: wherever the schedule allows
@@ -222,7 +253,6 @@ struct vof2d_ctx {
   int64_t halves_steps = 0;       // steps replayed from them (counter "halves_steps")
   std::vector<hipEvent_t> hev;
   bool batching = true;         // false after a failed capture of a batch: one graph launch per step from then on (build_step_batches)
-  hipGraphExec_t gphase[5] = {};  // phase 0, then phases 1, 2 x istep parity (slot 2 * phase - 1 + parity)
   int next_phase = 0;
   bool f_ghosts_dirty = true;  // F's ghost cells may not satisfy set_BC (after set_init_F / from_numpy / a single verb)
   bool uv_ghosts_dirty = false; // u / v were written without a set_BC since (update_uv verb, from_numpy): their ghost cells are not mirror images
@@ -243,10 +273,7 @@ struct vof2d_ctx {
   hipStream_t cstream = nullptr; // RCCL's kernels run here, next to the compute stream
   hipEvent_t ev_ready = nullptr, ev_done = nullptr;
   hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr};  // one per exchange of a step (graph capture forks)
-  hipGraphExec_t gxchg[2][5][2] = {};   // whole step + exchanges, [istep parity][overlap mode][F / twin orientation]
-  hipGraphExec_t gxchg2[2][2] = {};     // TWO mode-4 steps + exchanges per launch, [parity of the first][orientation] (vof_step_exchange)
-  hipGraphExec_t gxchg5[16] = {};       // TWO middle steps of mode 5 per launch, [parity | F orientation << 1 | u*, v* orientation << 2 | p orientation << 3]
-  int xchg5_graph = 1;                  // ... while this RCCL / runtime captures them
+  int xchg5_graph = 1;               // the two-step graphs of mode 5, while this RCCL / runtime captures them
   int xchg_pair = 1;                 // 0 after a failed capture of a pair: one step per launch
   int xchg_graph = 1;                // 0 after a failed capture (or VOF2D_XCHG_GRAPH=0): eager launches
   int64_t xchg_steps = 0;            // steps run by vof_step_exchange (the first one is always eager)

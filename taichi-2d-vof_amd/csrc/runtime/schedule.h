@@ -1,9 +1,9 @@
 // runtime/schedule.h -- the per-step launch schedule (2dvof.py:506-528): sweeps, phases, the fused full-domain step, ghost-cell bookkeeping, graph housekeeping
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, schedule.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
-#include "launches.h"
+#include "graphs.h"
 
 namespace {
 
@@ -444,25 +444,41 @@ int copy_rows_host(vof2d_ctx* h, int id, int g0, int g1, void* host, size_t nbyt
   return VOF_OK;
 }
 
-void destroy_xchg_graphs(vof2d_ctx* h);
+// F was replaced from outside (or a knob changed): what the rule of fuse_tm = -1 decided, and a count still in flight, were
+// of the old state.  (A decision by timing, fuse_tm = -2, stays until the next timing.)
+void forget_batch_form(vof2d_ctx* h) {
+  if (h->fuse_tm != -1) return;
+  h->tune.decided = false;
+  h->gas_pending = false;
+}
+// Constants and knobs are baked into the graphs: a change drops them all (they are re-captured on use)
 void destroy_graphs(vof2d_ctx* h) {
-  destroy_xchg_graphs(h);
-  for (int k = 0; k < 2; ++k)
-    for (int o = 0; o < 2; ++o)
-      if (h->gexec[k][o]) { (void)hipGraphExecDestroy(h->gexec[k][o]); h->gexec[k][o] = nullptr; }
-  for (int b = 0; b < vof2d_ctx::kStepBatches; ++b)
-    for (int k = 0; k < 2; ++k)
-      for (int o = 0; o < 2; ++o)
-        if (h->gbatch[b][k][o]) { (void)hipGraphExecDestroy(h->gbatch[b][k][o]); h->gbatch[b][k][o] = nullptr; }
-  for (int b = 0; b < vof2d_ctx::kStepBatches; ++b)
-    for (int k = 0; k < 2; ++k)
-      for (int o = 0; o < 2; ++o)
-        if (h->gbatch_tm[b][k][o]) { (void)hipGraphExecDestroy(h->gbatch_tm[b][k][o]); h->gbatch_tm[b][k][o] = nullptr; }
-  h->tune_n = 0; h->tune_age = 0; h->tm_decided = false; h->gas_pending = false; h->tm_broken = false; h->tune_ms[0] = h->tune_ms[1] = 0.f;   // (a changed knob changes what is being compared)
+  h->graphs.clear();
+  h->tune.reset();
+  forget_batch_form(h);
+  h->tm_broken = false;
   for (int b = 0; b < vof2d_ctx::kStepBatches; ++b) h->halves_captured[b] = false;
   h->batching = true;   // (a parameter change may be what a capture tripped over: try again)
-  for (int k = 0; k < 5; ++k)
-    if (h->gphase[k]) { (void)hipGraphExecDestroy(h->gphase[k]); h->gphase[k] = nullptr; }
+}
+// A single sweep swaps F with its twin, so field pointers baked into captured graphs go stale: drop the graphs.
+void sweep_swapped(vof2d_ctx* h) {
+  if (!h->graphs.any()) return;
+  (void)hipStreamSynchronize(h->stream);
+  destroy_graphs(h);
+}
+// The phase graphs bake the F / twin pointers in and assume the pair returns to the same orientation
+// after every step (two swaps).  The fused transport swaps once per step, so a handle that mixes
+// the entry points may arrive here with the pair the other way round: drop those graphs then
+// (they are re-captured on use).  The step and exchange graphs are keyed by the orientation.
+int match_phase_graph_orientation(vof2d_ctx* h) {
+  GraphCache& G = h->graphs;
+  if (ori_F(h) == h->phase_graph_ori) return VOF_OK;
+  if (GraphCache::any(G.phase, G.phase + 5)) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    GraphCache::clear(G.phase, G.phase + 5);
+  }
+  h->phase_graph_ori = ori_F(h);
+  return VOF_OK;
 }
 
 }  // namespace
