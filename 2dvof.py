@@ -13,6 +13,7 @@ Extensions (`python 2dvof.py -h`; the reference hard-codes them at :9,:19-20,:52
     --verbs           the literal main loop :513-528, one kernel per call
     --jacobi-tol T    residual-terminated pressure solve (--jacobi-max, --jacobi-crit abs|rel)
     --pressure-solver cg   ... by conjugate gradients instead of sweeps (one GPU)
+    --pressure-solver mg   ... by geometric multigrid: a grid-independent number of V-cycles (one GPU)
     --vis K           what the reference GUI would display (:531-559), saved with -s
     --save-every N    data/NNNNNNNN.npz checkpoints;  --resume FILE continues from one
 

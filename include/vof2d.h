@@ -158,6 +158,20 @@ int vof_solve_p(vof2d_handle h, double tol, int32_t max_iters, int32_t check_eve
  * order: the same state and call give the same bits.  Whole-domain handles only (a strip returns VOF_ESTATE). */
 int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every, int32_t criterion,
                    int32_t build_rhs, int32_t* iters_done, double* residual, double* drift);
+/* Extension: the SAME equation, drift constant, residual, stopping rule and warm start as vof_solve_p_cg, by geometric
+ * multigrid -- the coefficients of :258-262 are constants, so a fixed number of V-cycles does, whatever the grid size.
+ * Level l has nx / 2^l x ny / 2^l cells and the stencil with dxi2 / 4^l, dyi2 / 4^l and the same wall rule; levels are
+ * added while both extents are even and the coarser level keeps at least 4 cells each way.  A grid with an odd factor
+ * therefore gets a shallow hierarchy and a large coarsest level (96 x 130 -> 48 x 65): correct, but slower -- nothing
+ * is padded or re-gridded.  One cycle: mg_nu (knob, default 2) damped Jacobi sweeps (0.8), the 4-cell mean of the
+ * residual down, ..., conjugate gradients on the coarsest level to 1e-2 of its starting max|z|, ..., bilinear
+ * interpolation up, mg_nu sweeps.  Knob mg_levels caps the depth (-1: none; 1: the coarsest-level solver alone).
+ * The check runs first and then every check_every cycles, at most max_cycles: a start that satisfies tol does 0 cycles
+ * and changes nothing; a non-finite value reads as +inf at the first check.  *drift receives c.  No atomics, fixed
+ * summation order: the same state and call give the same bits and the same count.  Whole-domain handles only (a strip
+ * returns VOF_ESTATE and is left untouched). */
+int vof_solve_p_mg(vof2d_handle h, double tol, int32_t max_cycles, int32_t check_every, int32_t criterion,
+                   int32_t build_rhs, int32_t* cycles_done, double* residual, double* drift);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

@@ -137,6 +137,7 @@ struct GraphCache {
   // behind it, which one launch per step pays every step (step.h)
   hipGraphExec_t batch[2][kStepBatches][2][2] = {};    // [form: 0 chains or the plain sequence, 1 k_tm][batch size][parity of the first step][ori]
   hipGraphExec_t phase[5] = {};                        // phase 0, then phases 1, 2 x istep parity (slot 2 * phase - 1 + parity)
+  hipGraphExec_t mg = nullptr;                         // one V-cycle of vof_solve_p_mg (runtime/multigrid.h keeps what it was captured for)
   // ---- from here on: with the exchanges of a strip (they hold the communicator: clear_exchange)
   hipGraphExec_t xchg[2][5][2] = {};                   // whole step + exchanges, [istep parity][overlap mode][ori]
   hipGraphExec_t xchg2[2][2] = {};                     // TWO mode-4 steps + exchanges per launch, [parity of the first][ori] (comm.h)
@@ -153,7 +154,7 @@ struct GraphCache {
   void clear() { clear(begin(), end()); }
   void clear_exchange() { clear(&xchg[0][0][0], end()); }
 };
-static_assert(sizeof(GraphCache) == (4 + 4 * GraphCache::kStepBatches * 2 + 5 + 20 + 4 + 16) * sizeof(hipGraphExec_t), "GraphCache is walked as one array");
+static_assert(sizeof(GraphCache) == (4 + 4 * GraphCache::kStepBatches * 2 + 5 + 1 + 20 + 4 + 16) * sizeof(hipGraphExec_t), "GraphCache is walked as one array");
 
 // knob "fuse_tm" = -2 (exploration): both forms of the batch graphs timed on the handle's own data (tune_next_is_timed, step.h);
 // `choice` and `decided` also carry what the rule of fuse_tm = -1 found (decide_batch_form_by_rule)
@@ -166,6 +167,16 @@ struct TuneState {
   hipEvent_t ev[8] = {};
   float ms[2] = {0.f, 0.f};
   void reset() { n = 0; age = 0; decided = false; ms[0] = ms[1] = 0.f; }   // (a changed knob changes what is being compared)
+};
+
+// One level of the multigrid hierarchy (vof_solve_p_mg): nx / 2^l x ny / 2^l cells in the fields' pitched layout, zeros
+// outside the interior.  Level 0 is the handle's own grid: its e is p (ping-pong with pt), its f is rhs.
+struct MgLevel {
+  Geom g;
+  double scale;          // dxi2, dyi2 of the level over those of the grid: 1 / 4^l
+  size_t bytes;          // of one array
+  void* e[2];            // correction, ping-pong of the sweeps (levels >= 1)
+  void* f;               // right-hand side
 };
 
 struct vof2d_ctx {
@@ -190,6 +201,15 @@ struct vof2d_ctx {
   double* cg_part = nullptr;    // one partial per block (kCgPart doubles), then the CG_NSCAL device scalars
   double* cg_sc = nullptr;
   int cg_s = 1;                 // which of cg_fld[1..2] holds the current direction
+  // multigrid pressure solve (vof_solve_p_mg, runtime/multigrid.h): the levels below the grid, allocated by the first call
+  std::vector<MgLevel> mg_lv;   // as deep as the rule allows; knob "mg_levels" caps how many a cycle visits
+  char* mg_arena = nullptr;     // e (two), f of every level >= 1; r, two directions, q of the coarsest-level solve; its scalars
+  void* mg_cgw[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* mg_sc = nullptr;
+  int mg_nu = 2;                // knob "mg_nu": sweeps before and after the coarser levels
+  int mg_levels = -1;           // knob "mg_levels": cap on the depth of a cycle (-1: none)
+  int mg_graph = 1;             // knob "mg_graph": 0 launches every kernel of a cycle itself instead of replaying the captured cycle
+  void* mg_key[3] = {nullptr, nullptr, nullptr};   // p, pt, rhs the cached cycle was captured with
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

@@ -126,12 +126,13 @@ inline bool buffer_stores_ok(const vof2d_ctx* h) {
 constexpr long kTmAlwaysCells = 16000000L;
 constexpr long kTbPlanWaves = 16384;   // waves of a k_jacobi_tb launch the work plan can describe
 enum KernelId { kMomentum = 0, kSetBC, kJacobi, kJacobiTB, kCorrect, kFctX, kFctY, kNormals, kKappa, kPredictor,
-                kRhs, kOther, kTransport, kJacobiPair, kTM, kTMUV, kCgApply, kCgUpdate, kCgResidual, kCgFinish, NKERNELS };
+                kRhs, kOther, kTransport, kJacobiPair, kTM, kTMUV, kCgApply, kCgUpdate, kCgResidual, kCgFinish, kMgSmooth, kMgRestrict, kMgProlong, NKERNELS };
 static_assert(NKERNELS <= 24, "vof2d_ctx::prof_sum_ms / prof_cnt");
 const char* const kKernelNames[NKERNELS] = {"k_momentum", "k_set_bc", "k_jacobi", "k_jacobi_tb", "k_correct",
                                             "k_fct_x", "k_fct_y", "k_normals", "k_kappa", "k_predictor", "k_rhs",
                                             "other", "k_transport", "k_jacobi_pair", "k_tm", "k_tm_uv",
-                                            "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish"};   // (k_tm_uv: the k_tm launch that also stores u, v -- the last of a batch)
+                                            "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish",
+                                            "k_mg_smooth", "k_mg_restrict", "k_mg_prolong"};   // (k_tm_uv: the k_tm launch that also stores u, v -- the last of a batch)
 
 // One place through which every kernel is launched.  In profiling mode the dispatch carries its
 // own start/stop events (hipExtLaunchKernelGGL: the begin/end timestamps of the dispatch itself,
@@ -469,11 +470,11 @@ struct L {
   static unsigned cg_blocks(const vof2d_ctx* h, bool apply) { return blocks_for(h, h->g.ntj, cg_rows(h, apply)); }
   // sum of ap over the interior, in double, of the values the kernels form in T: ap depends on the position through
   // "first / last row or not" and "first / last column or not" only (2dvof.py:258-262), four values with their counts
-  static double cg_sum_ap(const vof2d_ctx* h) {
-    const Consts<T> c = C(const_cast<vof2d_ctx*>(h));
+  static double cg_sum_ap(const vof2d_ctx* h) { return sum_ap_of(C(const_cast<vof2d_ctx*>(h)), h->g.nx, h->g.ny); }
+  static double sum_ap_of(const Consts<T>& c, int nx, int ny) {
     const T zero = (T)0.0;
     const T ax[2] = {c.dxi2 + zero, c.dxi2 + c.dxi2};          // ae + aw: wall row, inner row
-    const double nrow[2] = {2.0, (double)(h->g.nx - 2)}, ncol[2] = {2.0, (double)(h->g.ny - 2)};
+    const double nrow[2] = {2.0, (double)(nx - 2)}, ncol[2] = {2.0, (double)(ny - 2)};
     double sum = 0.0;
     for (int a = 0; a < 2; ++a) {
       const T wall = (T)-1.0 * (ax[a] + c.dyi2 + zero), inner = (T)-1.0 * (ax[a] + c.dyi2 + c.dyi2);
@@ -481,8 +482,9 @@ struct L {
     }
     return sum;
   }
-  static void cg_finish(vof2d_ctx* h, unsigned nblocks, int mode, double sum_ap = 0.0, int restart = 0) {
-    launch(h, kCgFinish, k_cg_finish, dim3(1), 0, (const double*)h->cg_part, (int)nblocks, h->cg_sc, mode, sum_ap, restart);
+  // (sc: the scalars of the solve the partials belong to -- the handle's own, or those of a multigrid cycle's coarsest level)
+  static void cg_finish(vof2d_ctx* h, unsigned nblocks, int mode, double sum_ap = 0.0, int restart = 0, double* sc = nullptr) {
+    launch(h, kCgFinish, k_cg_finish, dim3(1), 0, (const double*)h->cg_part, (int)nblocks, sc ? sc : h->cg_sc, mode, sum_ap, restart);
   }
   // c = sum(b) / sum(ap) into the device scalars
   static void cg_drift(vof2d_ctx* h, double sum_ap) {
@@ -511,6 +513,56 @@ struct L {
     launch(h, kCgUpdate, k_cg_update<T, V>, dim3(nu), 0, h->g, cc, F_<T>(h, fP), (const T*)s_new, r, (const T*)q, cg_rows(h, false),
            (const double*)h->cg_sc, h->cg_part);
     cg_finish(h, nu, CG_FIN_UPDATE);
+  }
+  // ---- multigrid (kernels/mg.h): every wrapper takes the level(s) it works on; level 0 is the handle's own grid
+  static Consts<T> mg_consts(vof2d_ctx* h, const MgLevel& lv) {
+    Consts<T> c = C(h);
+    c.dxi2 = (T)(c.dxi2 * (T)lv.scale);   // exact: a power of four
+    c.dyi2 = (T)(c.dyi2 * (T)lv.scale);
+    return c;
+  }
+  static unsigned mg_blocks(const vof2d_ctx* h, const Geom& g, int R) { (void)h; return blocks_rows(g.nx, g.ntj, R); }
+  // one sweep e -> en; sc: the scalars holding c on level 0, nullptr below it (f is stored there)
+  static void mg_smooth(vof2d_ctx* h, const MgLevel& lv, const T* e, const T* f, T* en, const double* sc) {
+    const int R = pick_rows(h, lv.g.ntj);
+    launch(h, kMgSmooth, k_mg_smooth<T, V>, dim3(mg_blocks(h, lv.g, R)), 0, lv.g, mg_consts(h, lv), e, f, en, R, sc);
+  }
+  static void mg_restrict(vof2d_ctx* h, const MgLevel& fine, const MgLevel& coarse, const T* e, const T* f, T* fc, T* ec, const double* sc) {
+    const int R = pick_rows(h, coarse.g.ntj);
+    launch(h, kMgRestrict, k_mg_restrict<T, V>, dim3(mg_blocks(h, coarse.g, R)), 0, fine.g, coarse.g, mg_consts(h, fine), e, f, fc, ec, R, sc);
+  }
+  static void mg_prolong(vof2d_ctx* h, const MgLevel& fine, const MgLevel& coarse, const T* ec, T* e) {
+    const int R = pick_rows(h, coarse.g.ntj);
+    launch(h, kMgProlong, k_mg_prolong<T, V>, dim3(mg_blocks(h, coarse.g, R)), 0, fine.g, coarse.g, ec, e, R);
+  }
+  // L e = f - c' ap on one level by the kernels of kernels/cg.h, from the e it finds, until max|z| is down to `reduction`
+  // of its start or `cap` iterations are enqueued (k_mg_coarse_stop); w: r, two directions, q in the level's layout;
+  // own_drift: c' = sum(f) / sum(ap) of this level is formed first (on level 0 the solve's own c is in sc already)
+  static void mg_coarse_solve(vof2d_ctx* h, const MgLevel& lv, T* e, const T* f, void* const (&w)[4], double* sc, bool own_drift,
+                              int cap, double reduction) {
+    const Consts<T> cc = mg_consts(h, lv);
+    const int R1 = pick_rows(h, lv.g.ntj), R2 = 2 * R1;
+    const unsigned n1 = mg_blocks(h, lv.g, R1), n2 = mg_blocks(h, lv.g, R2);
+    T* const r = reinterpret_cast<T*>(w[0]);
+    T* const q = reinterpret_cast<T*>(w[3]);
+    if (own_drift) {
+      launch(h, kCgResidual, k_cg_sum<T, V>, dim3(n1), 0, lv.g, f, R1, h->cg_part);
+      cg_finish(h, n1, CG_FIN_SUMB, sum_ap_of(cc, lv.g.nx, lv.g.ny), 0, sc);
+    }
+    launch(h, kCgResidual, k_cg_residual<T, V>, dim3(n1), 0, lv.g, cc, (const T*)e, f, r, R1, (const double*)sc, h->cg_part);
+    cg_finish(h, n1, CG_FIN_RESID, 0.0, 1, sc);
+    launch_block(h, kOther, k_mg_coarse_stop, dim3(1), 64u, 0, sc, 1, reduction);
+    int s = 1;
+    for (int it = 0; it < cap; ++it) {
+      T* const s_old = reinterpret_cast<T*>(w[s]);
+      s = 3 - s;
+      T* const s_new = reinterpret_cast<T*>(w[s]);
+      launch(h, kCgApply, k_cg_apply<T, V>, dim3(n2), 0, lv.g, cc, (const T*)r, (const T*)s_old, s_new, q, R2, (const double*)sc, h->cg_part);
+      cg_finish(h, n2, CG_FIN_APPLY, 0.0, 0, sc);
+      launch(h, kCgUpdate, k_cg_update<T, V>, dim3(n1), 0, lv.g, cc, e, (const T*)s_new, r, (const T*)q, R1, (const double*)sc, h->cg_part);
+      cg_finish(h, n1, CG_FIN_UPDATE, 0.0, 0, sc);
+      launch_block(h, kOther, k_mg_coarse_stop, dim3(1), 64u, 0, sc, 0, reduction);
+    }
   }
   // update_uv + both sweeps + post_process_f in one pass (k_transport); reads fld[fF], writes fld[fF2]
   static int transport_rows(const vof2d_ctx* h) {

@@ -1,0 +1,182 @@
+// runtime/multigrid.h -- the hierarchy of vof_solve_p_mg, one V-cycle (enqueued, or captured once and replayed), the driver loop
+//
+// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
+// context.h, launches.h, graphs.h, schedule.h, multigrid.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+#pragma once
+#include "schedule.h"
+
+namespace {
+
+// The work arrays, reduction buffer and device scalars of vof_solve_p_cg, allocated by the first call of either solver:
+// the checks of vof_solve_p_mg run the same residual kernel into the same scalars.
+int cg_prepare(vof2d_ctx* h) {
+  if (h->cg_arena) return VOF_OK;
+  const size_t fbytes = h->field_elems * h->esz;
+  const size_t nblocks = blocks_for(h, h->g.ntj, 1);   // (the most blocks a launch can have: one-row chunks, knob "rows_per_wave")
+  const size_t pbytes = (nblocks * kCgPart + CG_NSCAL) * sizeof(double);
+  if (hipMalloc(reinterpret_cast<void**>(&h->cg_arena), 4 * fbytes) != hipSuccess) {
+    (void)hipGetLastError();
+    h->cg_arena = nullptr;
+    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the work arrays");
+  }
+  if (hipMalloc(reinterpret_cast<void**>(&h->cg_part), pbytes) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(h->cg_arena);
+    h->cg_arena = nullptr; h->cg_part = nullptr;
+    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the reduction buffer");
+  }
+  for (int k = 0; k < 4; ++k) h->cg_fld[k] = h->cg_arena + (size_t)k * fbytes;
+  h->cg_sc = h->cg_part + nblocks * kCgPart;
+  // cells outside the interior are never written again: they stay 0 (kernels/cg.h, k_cg_apply)
+  HIPCHK(h, hipMemsetAsync(h->cg_arena, 0, 4 * fbytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->cg_part, 0, pbytes, h->stream));
+  return VOF_OK;
+}
+
+constexpr double kMgCoarseReduction = 1e-2;   // the coarsest-level solve ends at this fraction of its starting max|z| ...
+inline int mg_coarse_cap(const Geom& g) { return 4 * (g.nx > g.ny ? g.nx : g.ny); }   // ... or after this many iterations
+
+// Level l >= 1: nx / 2^l x ny / 2^l cells in a pitched layout built like the fields' (vof_create): interior column 1 on a
+// 128-byte boundary, the pitch a multiple of 128 bytes with room for a whole wave tile right of ny.
+Geom mg_level_geom(const vof2d_ctx* h, int nx, int ny) {
+  Geom g{};
+  const int W = 64 * h->V, align = 128 / (int)h->esz;
+  g.nx = nx; g.ny = ny; g.row_lo = 0; g.row_hi = nx + 1; g.ilo = 1; g.ihi = nx; g.own_lo = 1; g.own_hi = nx;
+  g.wall_lo = g.wall_hi = 1;
+  g.ntj = (ny + W - 1) / W;
+  g.col0 = align - 1;
+  g.pitch = ((g.col0 + (long)ny + W + 16 + 1 + align - 1) / align) * align;
+  return g;
+}
+
+// Coarsen while both extents are even and the coarser level keeps at least 4 cells each way.  Allocated once, as deep as
+// the rule allows; the work arrays of the coarsest-level solve are sized for level 1, the largest level a cycle of two or
+// more levels can end on (a one-level cycle solves on the grid itself, with the arrays of vof_solve_p_cg).
+int mg_prepare(vof2d_ctx* h) {
+  if (!h->mg_lv.empty()) return VOF_OK;
+  std::vector<MgLevel> lv;
+  MgLevel l0{};
+  l0.g = h->g; l0.scale = 1.0; l0.bytes = h->field_elems * h->esz;
+  lv.push_back(l0);
+  const size_t align = 128 / h->esz;
+  size_t total = 0;
+  for (;;) {
+    const MgLevel& f = lv.back();
+    if (f.g.nx % 2 || f.g.ny % 2 || f.g.nx / 2 < 4 || f.g.ny / 2 < 4) break;
+    MgLevel c{};
+    c.g = mg_level_geom(h, f.g.nx / 2, f.g.ny / 2);
+    c.scale = f.scale * 0.25;
+    c.bytes = ((size_t)(c.g.nx + 2) * (size_t)c.g.pitch + align) * h->esz;
+    total += 3 * c.bytes;
+    lv.push_back(c);
+  }
+  if (lv.size() > 1) {
+    total += 4 * lv[1].bytes + CG_NSCAL * sizeof(double);
+    if (hipMalloc(reinterpret_cast<void**>(&h->mg_arena), total) != hipSuccess) {
+      (void)hipGetLastError();
+      h->mg_arena = nullptr;
+      return fail(h, VOF_ENOMEM, "vof_solve_p_mg: no memory for the coarser levels");
+    }
+    // cells outside a level's interior are never written: they stay 0
+    HIPCHK(h, hipMemsetAsync(h->mg_arena, 0, total, h->stream));
+    char* at = h->mg_arena;
+    for (size_t l = 1; l < lv.size(); ++l) {
+      lv[l].e[0] = at; lv[l].e[1] = at + lv[l].bytes; lv[l].f = at + 2 * lv[l].bytes;
+      at += 3 * lv[l].bytes;
+    }
+    for (int k = 0; k < 4; ++k) { h->mg_cgw[k] = at; at += lv[1].bytes; }
+    h->mg_sc = reinterpret_cast<double*>(at);
+  }
+  h->mg_lv.swap(lv);
+  return VOF_OK;
+}
+void mg_release(vof2d_ctx* h) {
+  if (h->mg_arena) (void)hipFree(h->mg_arena);
+  h->mg_arena = nullptr;
+  h->mg_lv.clear();
+}
+
+inline int mg_depth(const vof2d_ctx* h) {
+  const int all = (int)h->mg_lv.size();
+  return h->mg_levels >= 1 && h->mg_levels < all ? h->mg_levels : all;
+}
+
+// One V(nu, nu) cycle on h->stream, a straight line of launches.  Every level's sweeps ping-pong between two arrays (p and
+// pt on level 0): nu sweeps down, the correction added in place, nu sweeps up -- 2 nu in all, so e is back where it was.
+template <typename T>
+void mg_enqueue_cycle(vof2d_ctx* h) {
+  using K = L<T>;
+  const int last = mg_depth(h) - 1, nu = h->mg_nu < 1 ? 1 : h->mg_nu;
+  std::vector<MgLevel>& lv = h->mg_lv;
+  lv[0].e[0] = h->fld[fP]; lv[0].e[1] = h->fld[fPT]; lv[0].f = h->fld[fRHS];
+  auto E = [&](int l, int k) { return reinterpret_cast<T*>(lv[l].e[k]); };
+  auto F = [&](int l) { return reinterpret_cast<const T*>(lv[l].f); };
+  auto sc = [&](int l) { return l == 0 ? (const double*)h->cg_sc : (const double*)nullptr; };
+  auto sweeps = [&](int l, int from) {
+    for (int k = 0; k < nu; ++k) K::mg_smooth(h, lv[l], E(l, (from + k) & 1), F(l), E(l, (from + k + 1) & 1), sc(l));
+  };
+  for (int l = 0; l < last; ++l) {
+    sweeps(l, 0);
+    K::mg_restrict(h, lv[l], lv[l + 1], E(l, nu & 1), F(l), reinterpret_cast<T*>(lv[l + 1].f), E(l + 1, 0), sc(l));
+  }
+  if (last == 0)
+    K::mg_coarse_solve(h, lv[0], E(0, 0), F(0), h->cg_fld, h->cg_sc, false, mg_coarse_cap(lv[0].g), kMgCoarseReduction);
+  else
+    K::mg_coarse_solve(h, lv[last], E(last, 0), F(last), h->mg_cgw, h->mg_sc, true, mg_coarse_cap(lv[last].g), kMgCoarseReduction);
+  for (int l = last - 1; l >= 0; --l) {
+    K::mg_prolong(h, lv[l], lv[l + 1], E(l + 1, 0), E(l, nu & 1));
+    sweeps(l, nu & 1);
+  }
+}
+
+// n cycles: replays of the one captured cycle (a cycle at 1024^2 is some hundred small launches), or the launches themselves
+int mg_cycles(vof2d_ctx* h, int n) {
+  if (!h->mg_graph) {
+    for (int k = 0; k < n; ++k) DISPATCH_T(h, mg_enqueue_cycle<double>(h), mg_enqueue_cycle<float>(h));
+    return ensure_ok(h);
+  }
+  void* const key[3] = {h->fld[fP], h->fld[fPT], h->fld[fRHS]};   // a graph bakes its pointers in, and the views move
+  if (h->graphs.mg && memcmp(key, h->mg_key, sizeof(key)) != 0) GraphCache::clear(&h->graphs.mg, &h->graphs.mg + 1);
+  if (!h->graphs.mg) {
+    const int rc = capture_or_fail(h, true, &h->graphs.mg, "the multigrid cycle",
+                                   [&] { DISPATCH_T(h, mg_enqueue_cycle<double>(h), mg_enqueue_cycle<float>(h)); });
+    if (rc) return rc;
+    memcpy(h->mg_key, key, sizeof(key));
+  }
+  for (int k = 0; k < n; ++k) HIPCHK(h, hipGraphLaunch(h->graphs.mg, h->stream));
+  return VOF_OK;
+}
+
+// The driver of vof_solve_p_mg (arguments checked by the entry point): c, then check / cycles / check ... as vof_solve_p_cg
+int mg_solve(vof2d_ctx* h, double tol, int max_cycles, int check_every, int criterion, int build_rhs, int32_t* cycles_done,
+             double* residual, double* drift) {
+  int rc = cg_prepare(h);      // (the residual of the checks, the reduction buffer and the scalars are the CG verb's)
+  if (rc) return rc;
+  if ((rc = mg_prepare(h))) return rc;
+  if (build_rhs) DISPATCH_T(h, L<double>::rhs<false>(h), L<float>::rhs<false>(h));
+  // the coarsest-level solve starts every time from beta = 0 times the old direction: that array must be finite
+  if (mg_depth(h) == 1) HIPCHK(h, hipMemsetAsync(h->cg_fld[1], 0, 2 * h->field_elems * h->esz, h->stream));
+  else HIPCHK(h, hipMemsetAsync(h->mg_cgw[1], 0, 2 * h->mg_lv[1].bytes, h->stream));
+  const double sum_ap = DISPATCH_B(h, L<double>::cg_sum_ap(h), L<float>::cg_sum_ap(h));
+  DISPATCH_T(h, (L<double>::cg_drift(h, sum_ap), L<double>::cg_residual(h, 1)), (L<float>::cg_drift(h, sum_ap), L<float>::cg_residual(h, 1)));
+  int done = 0;
+  double r = 0.0, sc[CG_NSCAL];
+  for (;;) {
+    if ((rc = ensure_ok(h))) return rc;
+    HIPCHK(h, hipMemcpyAsync(sc, h->cg_sc, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    r = vof_residual_value(sc[CG_MAXZ], sc[CG_MAXP], criterion);
+    if (r <= tol || !(r < HUGE_VAL)) break;   // converged, or a non-finite field
+    if (done >= max_cycles) break;
+    const int n = check_every < max_cycles - done ? check_every : max_cycles - done;
+    if ((rc = mg_cycles(h, n))) return rc;
+    done += n;
+    DISPATCH_T(h, L<double>::cg_residual(h, 1), L<float>::cg_residual(h, 1));
+  }
+  *cycles_done = done;
+  *residual = r;
+  *drift = sc[CG_C];
+  return VOF_OK;
+}
+
+}  // namespace

@@ -11,6 +11,7 @@
 //   runtime/launches.h   one launch wrapper per kernel
 //   runtime/graphs.h     the keys of the graph cache, the one capture helper
 //   runtime/schedule.h   the per-step schedule, ghost-cell bookkeeping, dropping graphs
+//   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
@@ -19,6 +20,7 @@
 #include "runtime/launches.h"
 #include "runtime/graphs.h"
 #include "runtime/schedule.h"
+#include "runtime/multigrid.h"
 #include "runtime/step.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
@@ -44,6 +46,7 @@ const Knob kKnobs[] = {
   KNOB("tm_rows", tm_rows, false), KNOB("jacobi_pair", jpair, false), KNOB("jacobi_pair_rows", jpair_rows, false),
   KNOB("pair_vec4", pair_vec4, false), KNOB("pair_slow10", pair_slow10, false), KNOB("solve_pairs", solve_pairs, false),
   KNOB("tb_slow10", tb_slow10, false), KNOB("tune_period", tune.period, false),
+  KNOB("mg_nu", mg_nu, true), KNOB("mg_levels", mg_levels, true), KNOB("mg_graph", mg_graph, true),
 };
 #undef KNOB
 const Knob* find_knob(const char* name) {
@@ -182,6 +185,7 @@ int vof_destroy(vof2d_handle h) {
   if (h->d_tbmask) (void)hipFree(h->d_tbmask);
   if (h->cg_arena) (void)hipFree(h->cg_arena);
   if (h->cg_part) (void)hipFree(h->cg_part);
+  mg_release(h);
   if (h->arena) (void)hipFree(h->arena);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -365,30 +369,7 @@ int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t 
   return vof_solve_p(h, tol, max_iters, check_every, VOF_RESID_ABS, iters_done, residual);
 }
 
-// ---- conjugate-gradient pressure solve (kernels/cg.h)
-static int cg_prepare(vof2d_ctx* h) {
-  if (h->cg_arena) return VOF_OK;
-  const size_t fbytes = h->field_elems * h->esz;
-  const size_t nblocks = blocks_for(h, h->g.ntj, 1);   // (the most blocks a launch can have: one-row chunks, knob "rows_per_wave")
-  const size_t pbytes = (nblocks * kCgPart + CG_NSCAL) * sizeof(double);
-  if (hipMalloc(reinterpret_cast<void**>(&h->cg_arena), 4 * fbytes) != hipSuccess) {
-    (void)hipGetLastError();
-    h->cg_arena = nullptr;
-    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the work arrays");
-  }
-  if (hipMalloc(reinterpret_cast<void**>(&h->cg_part), pbytes) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipFree(h->cg_arena);
-    h->cg_arena = nullptr; h->cg_part = nullptr;
-    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the reduction buffer");
-  }
-  for (int k = 0; k < 4; ++k) h->cg_fld[k] = h->cg_arena + (size_t)k * fbytes;
-  h->cg_sc = h->cg_part + nblocks * kCgPart;
-  // cells outside the interior are never written again: they stay 0 (kernels/cg.h, k_cg_apply)
-  HIPCHK(h, hipMemsetAsync(h->cg_arena, 0, 4 * fbytes, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->cg_part, 0, pbytes, h->stream));
-  return VOF_OK;
-}
+// ---- conjugate-gradient pressure solve (kernels/cg.h; cg_prepare: runtime/multigrid.h)
 int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every, int32_t criterion,
                    int32_t build_rhs, int32_t* iters_done, double* residual, double* drift) {
   if (!h || !iters_done || !residual || !drift) return VOF_EINVAL;
@@ -422,6 +403,18 @@ int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_
   *residual = r;
   *drift = sc[CG_C];
   return VOF_OK;
+}
+
+// ---- geometric multigrid on the same equation (kernels/mg.h, runtime/multigrid.h)
+int vof_solve_p_mg(vof2d_handle h, double tol, int32_t max_cycles, int32_t check_every, int32_t criterion,
+                   int32_t build_rhs, int32_t* cycles_done, double* residual, double* drift) {
+  if (!h || !cycles_done || !residual || !drift) return VOF_EINVAL;
+  if (max_cycles < 1 || check_every < 1) return fail(h, VOF_EINVAL, "max_cycles and check_every must be >= 1");
+  if (criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
+  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
+    return fail(h, VOF_ESTATE, "vof_solve_p_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)");
+  settle_ghosts(h);
+  return mg_solve(h, tol, max_cycles, check_every, criterion, build_rhs, cycles_done, residual, drift);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

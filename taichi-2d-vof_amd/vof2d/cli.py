@@ -44,9 +44,10 @@ def build_parser():
     ext.add_argument('--jacobi-max', type=int, default=2000)
     ext.add_argument('--jacobi-crit', choices=['abs', 'rel'], default='abs',
                      help='abs: max|p_new-p| <= tol (default); rel: max|p_new-p| / max|p_new| <= tol (vof_solve_p)')
-    ext.add_argument('--pressure-solver', choices=['jacobi', 'cg'], default='jacobi',
-                     help='what --jacobi-tol runs: Jacobi sweeps (default, vof_solve_p) or conjugate gradients on the same '
-                          'equation (vof_solve_p_cg; --jacobi-max caps the iterations, --jacobi-crit as for the sweeps; one GPU)')
+    ext.add_argument('--pressure-solver', choices=['jacobi', 'cg', 'mg'], default='jacobi',
+                     help='what --jacobi-tol runs: Jacobi sweeps (default, vof_solve_p), conjugate gradients (cg, vof_solve_p_cg) '
+                          'or geometric multigrid (mg, vof_solve_p_mg) on the same equation; --jacobi-max caps the iterations '
+                          '(cg) or V-cycles (mg), --jacobi-crit as for the sweeps; one GPU')
     ext.add_argument('--device', type=int, default=0, help='HIP device ordinal (one GPU; with --gpus N rank r takes device r)')
     ext.add_argument('--vis', type=int, choices=[0, 1, 2, 3, 4], default=0,
                      help='what the reference GUI would display (SPACE cycles it there, :508-509): 0 VOF, 1 u, 2 v, '
@@ -62,11 +63,11 @@ def parse_args(argv=None):
     """build_parser().parse_args plus the combinations argparse cannot express."""
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.pressure_solver == "cg":
+    if args.pressure_solver in ("cg", "mg"):
         if not args.jacobi_tol > 0.0:
-            parser.error("--pressure-solver cg needs a tolerance: pass --jacobi-tol T (> 0)")
+            parser.error("--pressure-solver %s needs a tolerance: pass --jacobi-tol T (> 0)" % args.pressure_solver)
         if args.gpus > 1:
-            parser.error("--pressure-solver cg runs on one GPU (its dot products are not reduced over strips): drop --gpus")
+            parser.error("--pressure-solver %s runs on one GPU (its sums are not reduced over strips): drop --gpus" % args.pressure_solver)
     return args
 
 
@@ -76,8 +77,8 @@ def numerics_of(args, dt):
     num = {"dt": float(dt), "jacobi_iters": int(args.jacobi_iters), "coord_cast": str(args.coord_cast),
            "jacobi_tol": float(args.jacobi_tol), "jacobi_max": int(args.jacobi_max) if args.jacobi_tol > 0.0 else 0,
            "jacobi_crit": str(args.jacobi_crit) if args.jacobi_tol > 0.0 else ""}
-    if getattr(args, "pressure_solver", "jacobi") == "cg":   # (only then: checkpoints of sweep runs resume as before)
-        num["pressure_solver"] = "cg"
+    if getattr(args, "pressure_solver", "jacobi") in ("cg", "mg"):   # (only then: checkpoints of sweep runs resume as before)
+        num["pressure_solver"] = str(args.pressure_solver)
     return num
 
 
@@ -103,7 +104,7 @@ def load_state(path, nx, ny, dtype, numerics=None):
             raise SystemExit("--resume: %s was written with %s = %r, this run has %r (pass the same value to continue it)" %
                              (path, k.replace("_", "-"), z[key].item(), v))
     if numerics is not None and any(k.startswith("num_") for k in z.files):
-        # (recorded only by conjugate-gradient runs, so that files of sweep runs look as they always did)
+        # (recorded only by conjugate-gradient and multigrid runs, so that files of sweep runs look as they always did)
         have = str(z["num_pressure_solver"]) if "num_pressure_solver" in z.files else "jacobi"
         want = numerics.get("pressure_solver", "jacobi")
         if have != want:
@@ -140,6 +141,8 @@ class _Single:
                 sim.cal_nu_rho(); sim.get_normal_young(); sim.advect_upwind(); sim.set_BC()
                 if a.pressure_solver == "cg":
                     sim.solve_p_cg(a.jacobi_tol, a.jacobi_max, 10, a.jacobi_crit)
+                elif a.pressure_solver == "mg":
+                    sim.solve_p_mg(a.jacobi_tol, a.jacobi_max, 1, a.jacobi_crit)
                 else:
                     self.eng.solve_p(a.jacobi_tol, a.jacobi_max, 10, a.jacobi_crit)
                 sim.update_uv(); sim.set_BC()
@@ -225,8 +228,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         rank = int(os.environ.get("RANK", 0)) if world > 1 else 0
     if world > 1 and (args.verbs or args.vis):
         raise SystemExit("--verbs and --vis run on one GPU (drop --gpus)")
-    if world > 1 and args.pressure_solver == "cg":
-        raise SystemExit("--pressure-solver cg runs on one GPU (drop --gpus)")
+    if world > 1 and args.pressure_solver in ("cg", "mg"):
+        raise SystemExit("--pressure-solver %s runs on one GPU (drop --gpus)" % args.pressure_solver)
     if world > 1 and world != args.gpus:
         raise SystemExit("--gpus %d but the launcher started %d ranks" % (args.gpus, world))
     if api is None:

@@ -168,6 +168,15 @@ class Engine:
                                      1 if build_rhs else 0, C.byref(it), C.byref(res), C.byref(drift)), "solve_p_cg")
         return it.value, res.value, drift.value
 
+    def solve_p_mg(self, tol, max_cycles, check_every=1, criterion="abs", build_rhs=True):
+        """vof_solve_p_mg: V-cycles of geometric multigrid on the equation of solve_p_cg, same residual and stopping
+        rule; returns (cycles done, residual, drift).  Knobs (set_param): mg_nu, mg_levels."""
+        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        it, res, drift = C.c_int32(), C.c_double(), C.c_double()
+        self._ck(self.api.solve_p_mg(self._h, float(tol), int(max_cycles), int(check_every), crit,
+                                     1 if build_rhs else 0, C.byref(it), C.byref(res), C.byref(drift)), "solve_p_mg")
+        return it.value, res.value, drift.value
+
     def jacobi_sweeps_norms(self, n, build_rhs=True):
         """(max|p_new - p|, max|p_new|) of the last of n sweeps over the owned rows."""
         upd, pm = C.c_double(), C.c_double()
@@ -291,7 +300,8 @@ class Engine:
         out = {}
         for k in ("k_momentum", "k_set_bc", "k_jacobi", "k_jacobi_tb", "k_correct", "k_fct_x", "k_fct_y",
                   "k_transport", "k_normals", "k_kappa", "k_predictor", "k_rhs", "k_jacobi_pair", "k_tm", "k_tm_uv",
-                  "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish"):
+                  "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish",
+                  "k_mg_smooth", "k_mg_restrict", "k_mg_prolong"):
             us, n = C.c_double(), C.c_int64()
             if self.api.get_profile(self._h, k.encode(), C.byref(us), C.byref(n)) != 0:
                 continue   # a kernel this build of the library does not have

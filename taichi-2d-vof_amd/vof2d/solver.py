@@ -88,6 +88,9 @@ class VOF2D:
     def solve_p_cg(self, tol, max_iters, check_every=10, criterion="abs", build_rhs=True):
         return self.eng.solve_p_cg(tol, max_iters, check_every, criterion, build_rhs)
 
+    def solve_p_mg(self, tol, max_cycles, check_every=1, criterion="abs", build_rhs=True):
+        return self.eng.solve_p_mg(tol, max_cycles, check_every, criterion, build_rhs)
+
     def update_uv(self):
         self.eng.update_uv()
 
