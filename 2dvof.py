@@ -14,6 +14,7 @@ Extensions (`python 2dvof.py -h`; the reference hard-codes them at :9,:19-20,:52
     --jacobi-tol T    residual-terminated pressure solve (--jacobi-max, --jacobi-crit abs|rel)
     --pressure-solver cg   ... by conjugate gradients instead of sweeps (one GPU)
     --pressure-solver mg   ... by geometric multigrid: a grid-independent number of V-cycles (one GPU)
+    --mg-cycles K     with --pressure-solver mg and no tolerance: K V-cycles inside every fused step (vof_step_mg; --mg-coarse)
     --vis K           what the reference GUI would display (:531-559), saved with -s
     --save-every N    data/NNNNNNNN.npz checkpoints;  --resume FILE continues from one
 

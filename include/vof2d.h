@@ -172,6 +172,26 @@ int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_
  * returns VOF_ESTATE and is left untouched). */
 int vof_solve_p_mg(vof2d_handle h, double tol, int32_t max_cycles, int32_t check_every, int32_t criterion,
                    int32_t build_rhs, int32_t* cycles_done, double* residual, double* drift);
+/* Extension: nsteps steps of the main loop (2dvof.py:506-528) in which the ten sweeps of :521-522 are replaced by
+ * `cycles` V-cycles of vof_solve_p_mg's cycle on that verb's equation, warm-started from the handle's p.  After the call
+ * every readable field, istep and the courant_violations counter hold, bit for bit, what this sequence leaves, n times:
+ *   istep += 1; cal_nu_rho; get_normal_young; advect_upwind; set_BC;
+ *   vof_solve_p_mg(tol = -1, max_cycles = cycles, check_every = cycles, criterion, build_rhs = 1);   (exactly `cycles` cycles)
+ *   update_uv; set_BC; solve_VOF_rudman(istep); post_process_f; set_BC
+ * with the same knobs (mg_nu, mg_levels, mg_graph, mg_coarse_block).  The residual of every step is recorded on the
+ * device; nothing is read back before the end of the call.  *last_residual: the residual that verb returns in the last
+ * step (same kernels, same order of sums: equal bits); *worst_residual: the largest of the nsteps residuals;
+ * *worst_step: the istep it belongs to (the first one on a tie).  A non-finite field reads as +inf (vof_residual_value)
+ * and the steps go on.  nsteps = 0 does nothing and reports 0, 0, 0.  Any of the three pointers may be NULL; if all are,
+ * the call does not synchronise.  cycles >= 1 and a valid criterion, else VOF_EINVAL; whole-domain handles only (a
+ * strip returns VOF_ESTATE and is left untouched).  Steady-state steps replay one captured graph per step (none with
+ * VOF_FLAG_NO_GRAPH or knob mg_graph = 0: same bits); calls interleave with vof_step in any order.
+ * Knob "mg_coarse_block" (vof_set_param; default 0): the coarsest-level solve of a cycle -- of this verb and of
+ * vof_solve_p_mg -- as one launch of one workgroup with the level held in LDS, where that level has at most 1024 cells
+ * counting its ghost ring; vof_get_param reads 1 only where it is in effect.  Same solver, another order of sums:
+ * other bits than the launches'. */
+int vof_step_mg(vof2d_handle h, int64_t nsteps, int32_t cycles, int32_t criterion,
+                double* last_residual, double* worst_residual, int64_t* worst_step);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

@@ -1,4 +1,5 @@
-// kernels/mg.h -- geometric multigrid on the pressure equation (k_mg_smooth, k_mg_restrict, k_mg_prolong), and the stop rule of its coarsest-level solve
+// kernels/mg.h -- geometric multigrid on the pressure equation (k_mg_smooth, k_mg_restrict, k_mg_prolong), the stop rule of its
+// coarsest-level solve, that solve as one workgroup (k_mg_coarse_block), and the per-step residual record of vof_step_mg (k_mg_step_record)
 //
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
@@ -21,6 +22,7 @@
 // anyway (load_row, as k_jacobi and k_cg_residual).  Lanes whose first column lies right of the level's ny leave.
 #pragma once
 #include "cg.h"
+#include "residual_rule.h"
 
 namespace vof {
 
@@ -192,6 +194,144 @@ __global__ void k_mg_coarse_stop(double* __restrict__ sc, int start, double redu
   } else if (z <= reduction * sc[MG_Z0]) {
     sc[CG_STOP] = 1.0;
   }
+}
+
+// ------------------------------------------------------------------ the coarsest-level solve as ONE workgroup (knob "mg_coarse_block")
+// What L<T>::mg_coarse_solve enqueues as 3 + 5 x cap launches -- L e = f - c' ap from the e it finds, diagonally preconditioned
+// conjugate gradients until max|z| is down to `reduction` of its start or `cap` iterations -- for a level of at most
+// kMgBlockCells cells counting its ghost ring.  e, r, s, q live in LDS for the whole solve (4 x 1024 x 8 bytes in fp64);
+// cell (i, j) is element i (ny + 2) + j, its ghost ring stays 0 as in the level's arrays in memory.  A thread owns the
+// interior cells t, t + 256, ... in every phase, so only s -- whose neighbours the stencil reads -- needs a barrier
+// between its writer and its readers; the reductions carry the others.  Sums in double for both field types: a thread's
+// cells in order, lanes -> wave by __shfl_down, waves -> block through LDS in wave order, every thread adding the four
+// wave values itself -- so alpha, beta and the stop decision are formed by every thread from the same bits and the
+// control flow stays uniform.  A zero or non-finite denominator ends the solve instead of dividing (kernels/cg.h).
+// Another order of sums than the launches': other bits, same solver -- hence a knob.
+constexpr int kMgBlockCells = 1024;
+
+__device__ __forceinline__ void mg_block_reduce(double& sum, double& mx, double (*red)[2]) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    sum += __shfl_down(sum, d, 64);
+    mx = __builtin_fmax(mx, __shfl_down(mx, d, 64));
+  }
+  __syncthreads();   // (everybody is through reading the previous reduction)
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sum; red[threadIdx.x >> 6][1] = mx; }
+  __syncthreads();
+  sum = red[0][0]; mx = red[0][1];
+  for (int k = 1; k < 4; ++k) { sum += red[k][0]; mx = __builtin_fmax(mx, red[k][1]); }
+}
+
+// sc_c: the scalars holding the solve's own c (a one-level cycle: the level is the grid), nullptr below the grid, where
+// c' = sum(f) / sum_ap of this level is formed first
+template <typename T>
+__global__ __launch_bounds__(256) void k_mg_coarse_block(Geom g, Consts<T> c, T* __restrict__ e, const T* __restrict__ f,
+                                                          const double* __restrict__ sc_c, double sum_ap, int cap, double reduction) {
+  __shared__ T le[kMgBlockCells], lr[kMgBlockCells], ls[kMgBlockCells], lq[kMgBlockCells];
+  __shared__ double red[4][2];
+  const int t = threadIdx.x, nx = g.nx, ny = g.ny, w = ny + 2, ncell = nx * ny;
+  for (int k = t; k < (nx + 2) * w; k += 256) { ls[k] = (T)0.0; le[k] = (T)0.0; }
+  __syncthreads();
+  double sum = 0.0, mx = 0.0;
+  for (int n = t; n < ncell; n += 256) {
+    const int i = 1 + n / ny, j = 1 + n % ny;
+    const T ff = f[at(g, i, j)];
+    lq[i * w + j] = ff;   // (parked: q is not formed before the first iteration)
+    le[i * w + j] = e[at(g, i, j)];
+    sum += (double)ff;
+  }
+  double cc_d;
+  if (sc_c) cc_d = sc_c[CG_C];
+  else { mg_block_reduce(sum, mx, red); cc_d = sum / sum_ap; }
+  const T cc = (T)cc_d;
+  __syncthreads();   // e of the neighbours
+  auto coef = [&](int i, int j, T& ae, T& aw, T& an, T& as_) {
+    ae = i != nx ? c.dxi2 : (T)0.0; aw = i != 1 ? c.dxi2 : (T)0.0;
+    an = j != ny ? c.dyi2 : (T)0.0; as_ = j != 1 ? c.dyi2 : (T)0.0;
+  };
+  // r = (f - c ap) - L e,  dot(r, z),  max|z|
+  sum = 0.0; mx = 0.0;
+  for (int n = t; n < ncell; n += 256) {
+    const int i = 1 + n / ny, j = 1 + n % ny, k = i * w + j;
+    T ae, aw, an, as_;
+    coef(i, j, ae, aw, an, as_);
+    const T ap = (T)-1.0 * (ae + aw + an + as_), pc = le[k];
+    const T Le = ae * (le[k + w] - pc) + aw * (le[k - w] - pc) + an * (le[k + 1] - pc) + as_ * (le[k - 1] - pc);
+    const T rr = (lq[k] - cc * ap) - Le, z = rr / ap;
+    lr[k] = rr;
+    sum += (double)rr * (double)z;
+    mx = cg_amax(mx, (double)z);
+  }
+  mg_block_reduce(sum, mx, red);
+  double rz = sum, beta = 0.0;
+  const double z0 = mx;
+  bool stop = !(z0 > 0.0);
+  for (int it = 0; it < cap && !stop; ++it) {
+    // s <- z + beta s
+    const T bt = (T)beta;
+    for (int n = t; n < ncell; n += 256) {
+      const int i = 1 + n / ny, j = 1 + n % ny, k = i * w + j;
+      T ae, aw, an, as_;
+      coef(i, j, ae, aw, an, as_);
+      ls[k] = lr[k] / ((T)-1.0 * (ae + aw + an + as_)) + bt * ls[k];
+    }
+    __syncthreads();
+    // q = L s,  dot(s, q)
+    sum = 0.0; mx = 0.0;
+    for (int n = t; n < ncell; n += 256) {
+      const int i = 1 + n / ny, j = 1 + n % ny, k = i * w + j;
+      T ae, aw, an, as_;
+      coef(i, j, ae, aw, an, as_);
+      const T sc_ = ls[k];
+      const T q = ae * (ls[k + w] - sc_) + aw * (ls[k - w] - sc_) + an * (ls[k + 1] - sc_) + as_ * (ls[k - 1] - sc_);
+      lq[k] = q;
+      sum += (double)sc_ * (double)q;
+    }
+    mg_block_reduce(sum, mx, red);
+    double alpha = 0.0;
+    if (sum != 0.0 && __builtin_isfinite(sum) && __builtin_isfinite(rz)) alpha = rz / sum;
+    if (!__builtin_isfinite(alpha)) alpha = 0.0;
+    if (alpha == 0.0) break;   // nothing to divide by (or nothing left to do)
+    // e += alpha s,  r -= alpha q,  dot(r, z),  max|z|
+    const T al = (T)alpha;
+    sum = 0.0; mx = 0.0;
+    for (int n = t; n < ncell; n += 256) {
+      const int i = 1 + n / ny, j = 1 + n % ny, k = i * w + j;
+      T ae, aw, an, as_;
+      coef(i, j, ae, aw, an, as_);
+      le[k] = le[k] + al * ls[k];
+      const T rr = lr[k] - al * lq[k];
+      lr[k] = rr;
+      const T z = rr / ((T)-1.0 * (ae + aw + an + as_));
+      sum += (double)rr * (double)z;
+      mx = cg_amax(mx, (double)z);
+    }
+    mg_block_reduce(sum, mx, red);
+    beta = 0.0;
+    if (rz != 0.0 && __builtin_isfinite(sum)) beta = sum / rz;
+    if (!__builtin_isfinite(sum) || !__builtin_isfinite(beta)) { beta = 0.0; stop = true; }
+    rz = sum;
+    if (mx <= reduction * z0) stop = true;
+  }
+  for (int n = t; n < ncell; n += 256) {
+    const int i = 1 + n / ny, j = 1 + n % ny;
+    e[at(g, i, j)] = le[i * w + j];
+  }
+}
+
+// ------------------------------------------------------------------ the residual record of a vof_step_mg call
+// One thread, behind k_cg_residual + k_cg_finish at the end of a step's cycles: the step's residual by the rule of
+// vof_residual_value (kernels/residual_rule.h) into the handle's record -- last, worst, which recorded step the worst
+// belongs to (1-based; the first one on a tie), steps recorded.  The stream is a straight line: no atomics.  The host
+// zeroes the record at the start of a call and reads it once, at the end.
+enum : int { MGR_LAST = 0, MGR_WORST, MGR_WORST_AT, MGR_COUNT, MGR_N };
+__global__ void k_mg_step_record(const double* __restrict__ sc, double* __restrict__ rec, int criterion) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double r = residual_rule(sc[CG_MAXZ], sc[CG_MAXP], criterion);
+  const double n = rec[MGR_COUNT] + 1.0;
+  rec[MGR_LAST] = r;
+  if (n == 1.0 || r > rec[MGR_WORST]) { rec[MGR_WORST] = r; rec[MGR_WORST_AT] = n; }
+  rec[MGR_COUNT] = n;
 }
 
 }  // namespace vof

@@ -138,6 +138,7 @@ struct GraphCache {
   hipGraphExec_t batch[2][kStepBatches][2][2] = {};    // [form: 0 chains or the plain sequence, 1 k_tm][batch size][parity of the first step][ori]
   hipGraphExec_t phase[5] = {};                        // phase 0, then phases 1, 2 x istep parity (slot 2 * phase - 1 + parity)
   hipGraphExec_t mg = nullptr;                         // one V-cycle of vof_solve_p_mg (runtime/multigrid.h keeps what it was captured for)
+  hipGraphExec_t step_mg[2][2] = {};                   // whole step of vof_step_mg, [istep parity][ori] (runtime/step.h keeps what they were captured for)
   // ---- from here on: with the exchanges of a strip (they hold the communicator: clear_exchange)
   hipGraphExec_t xchg[2][5][2] = {};                   // whole step + exchanges, [istep parity][overlap mode][ori]
   hipGraphExec_t xchg2[2][2] = {};                     // TWO mode-4 steps + exchanges per launch, [parity of the first][ori] (comm.h)
@@ -154,7 +155,7 @@ struct GraphCache {
   void clear() { clear(begin(), end()); }
   void clear_exchange() { clear(&xchg[0][0][0], end()); }
 };
-static_assert(sizeof(GraphCache) == (4 + 4 * GraphCache::kStepBatches * 2 + 5 + 1 + 20 + 4 + 16) * sizeof(hipGraphExec_t), "GraphCache is walked as one array");
+static_assert(sizeof(GraphCache) == (4 + 4 * GraphCache::kStepBatches * 2 + 5 + 1 + 4 + 20 + 4 + 16) * sizeof(hipGraphExec_t), "GraphCache is walked as one array");
 
 // knob "fuse_tm" = -2 (exploration): both forms of the batch graphs timed on the handle's own data (tune_next_is_timed, step.h);
 // `choice` and `decided` also carry what the rule of fuse_tm = -1 found (decide_batch_form_by_rule)
@@ -178,6 +179,9 @@ struct MgLevel {
   void* e[2];            // correction, ping-pong of the sweeps (levels >= 1)
   void* f;               // right-hand side
 };
+
+// The pressure solve of a vof_step_mg step, where a step of vof_step has its Jacobi sweeps (runtime/schedule.h)
+struct StepMg { int cycles, criterion; };
 
 struct vof2d_ctx {
   vof2d_desc d;
@@ -210,6 +214,11 @@ struct vof2d_ctx {
   int mg_levels = -1;           // knob "mg_levels": cap on the depth of a cycle (-1: none)
   int mg_graph = 1;             // knob "mg_graph": 0 launches every kernel of a cycle itself instead of replaying the captured cycle
   void* mg_key[3] = {nullptr, nullptr, nullptr};   // p, pt, rhs the cached cycle was captured with
+  int mg_coarse_block = 0;      // knob "mg_coarse_block": the coarsest-level solve as one launch of one workgroup (k_mg_coarse_block) where the level is small enough
+  // vof_step_mg (runtime/step.h): the residual record on the device (kernels/mg.h, MGR_*), and what the step graphs were captured for
+  double* mg_rec = nullptr;
+  void* step_mg_key[NFIELDS] = {};   // the field views (F and its twin apart: the graphs are keyed by the orientation)
+  int step_mg_cycles = 0, step_mg_crit = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

@@ -126,13 +126,13 @@ inline bool buffer_stores_ok(const vof2d_ctx* h) {
 constexpr long kTmAlwaysCells = 16000000L;
 constexpr long kTbPlanWaves = 16384;   // waves of a k_jacobi_tb launch the work plan can describe
 enum KernelId { kMomentum = 0, kSetBC, kJacobi, kJacobiTB, kCorrect, kFctX, kFctY, kNormals, kKappa, kPredictor,
-                kRhs, kOther, kTransport, kJacobiPair, kTM, kTMUV, kCgApply, kCgUpdate, kCgResidual, kCgFinish, kMgSmooth, kMgRestrict, kMgProlong, NKERNELS };
+                kRhs, kOther, kTransport, kJacobiPair, kTM, kTMUV, kCgApply, kCgUpdate, kCgResidual, kCgFinish, kMgSmooth, kMgRestrict, kMgProlong, kMgCoarseBlock, NKERNELS };
 static_assert(NKERNELS <= 24, "vof2d_ctx::prof_sum_ms / prof_cnt");
 const char* const kKernelNames[NKERNELS] = {"k_momentum", "k_set_bc", "k_jacobi", "k_jacobi_tb", "k_correct",
                                             "k_fct_x", "k_fct_y", "k_normals", "k_kappa", "k_predictor", "k_rhs",
                                             "other", "k_transport", "k_jacobi_pair", "k_tm", "k_tm_uv",
                                             "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish",
-                                            "k_mg_smooth", "k_mg_restrict", "k_mg_prolong"};   // (k_tm_uv: the k_tm launch that also stores u, v -- the last of a batch)
+                                            "k_mg_smooth", "k_mg_restrict", "k_mg_prolong", "k_mg_coarse_block"};   // (k_tm_uv: the k_tm launch that also stores u, v -- the last of a batch)
 
 // One place through which every kernel is launched.  In profiling mode the dispatch carries its
 // own start/stop events (hipExtLaunchKernelGGL: the begin/end timestamps of the dispatch itself,
@@ -563,6 +563,12 @@ struct L {
       cg_finish(h, n1, CG_FIN_UPDATE, 0.0, 0, sc);
       launch_block(h, kOther, k_mg_coarse_stop, dim3(1), 64u, 0, sc, 0, reduction);
     }
+  }
+  // ... the same solve as ONE launch of one workgroup (knob "mg_coarse_block"; the caller has checked that the level fits:
+  // mg_block_in_effect, runtime/multigrid.h).  sc_c: the scalars holding c where the level is the grid itself, else nullptr.
+  static void mg_coarse_block(vof2d_ctx* h, const MgLevel& lv, T* e, const T* f, const double* sc_c, int cap, double reduction) {
+    const Consts<T> cc = mg_consts(h, lv);
+    launch(h, kMgCoarseBlock, k_mg_coarse_block<T>, dim3(1), 0, lv.g, cc, e, f, sc_c, sum_ap_of(cc, lv.g.nx, lv.g.ny), cap, reduction);
   }
   // update_uv + both sweeps + post_process_f in one pass (k_transport); reads fld[fF], writes fld[fF2]
   static int transport_rows(const vof2d_ctx* h) {

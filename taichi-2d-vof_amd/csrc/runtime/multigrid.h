@@ -92,13 +92,29 @@ int mg_prepare(vof2d_ctx* h) {
 }
 void mg_release(vof2d_ctx* h) {
   if (h->mg_arena) (void)hipFree(h->mg_arena);
+  if (h->mg_rec) (void)hipFree(h->mg_rec);
   h->mg_arena = nullptr;
+  h->mg_rec = nullptr;
   h->mg_lv.clear();
 }
 
 inline int mg_depth(const vof2d_ctx* h) {
   const int all = (int)h->mg_lv.size();
   return h->mg_levels >= 1 && h->mg_levels < all ? h->mg_levels : all;
+}
+
+// Knob "mg_coarse_block": the coarsest level a cycle of this handle ends on -- by the rule of mg_prepare and the cap of
+// knob "mg_levels", from the extents alone: vof_get_param may ask before the hierarchy exists -- and whether its solve
+// runs as one workgroup (k_mg_coarse_block: the level with its ghost ring fits kMgBlockCells)
+inline void mg_coarsest_extents(const vof2d_ctx* h, int& nx, int& ny) {
+  nx = h->g.nx; ny = h->g.ny;
+  for (int l = 1; (h->mg_levels < 1 || l < h->mg_levels) && !(nx % 2 || ny % 2 || nx / 2 < 4 || ny / 2 < 4); ++l) { nx /= 2; ny /= 2; }
+}
+inline bool mg_block_in_effect(const vof2d_ctx* h) {
+  if (!h->mg_coarse_block || !(h->g.wall_lo && h->g.wall_hi)) return false;
+  int nx, ny;
+  mg_coarsest_extents(h, nx, ny);
+  return (nx + 2) * (ny + 2) <= kMgBlockCells;
 }
 
 // One V(nu, nu) cycle on h->stream, a straight line of launches.  Every level's sweeps ping-pong between two arrays (p and
@@ -119,7 +135,9 @@ void mg_enqueue_cycle(vof2d_ctx* h) {
     sweeps(l, 0);
     K::mg_restrict(h, lv[l], lv[l + 1], E(l, nu & 1), F(l), reinterpret_cast<T*>(lv[l + 1].f), E(l + 1, 0), sc(l));
   }
-  if (last == 0)
+  if (mg_block_in_effect(h))
+    K::mg_coarse_block(h, lv[last], E(last, 0), F(last), sc(last), mg_coarse_cap(lv[last].g), kMgCoarseReduction);
+  else if (last == 0)
     K::mg_coarse_solve(h, lv[0], E(0, 0), F(0), h->cg_fld, h->cg_sc, false, mg_coarse_cap(lv[0].g), kMgCoarseReduction);
   else
     K::mg_coarse_solve(h, lv[last], E(last, 0), F(last), h->mg_cgw, h->mg_sc, true, mg_coarse_cap(lv[last].g), kMgCoarseReduction);
@@ -127,6 +145,24 @@ void mg_enqueue_cycle(vof2d_ctx* h) {
     K::mg_prolong(h, lv[l], lv[l + 1], E(l + 1, 0), E(l, nu & 1));
     sweeps(l, nu & 1);
   }
+}
+
+// The pressure solve of a vof_step_mg step, enqueued on h->stream (eagerly, or inside the capture of the step): what
+// vof_solve_p_mg(tol = -1, max_cycles = check_every = cycles, build_rhs = 1) runs behind the rhs the step's k_momentum
+// has formed -- the clean direction arrays (the part of them the coarsest level reads; the block kernel reads none), the
+// drift constant, the cycles, the residual -- minus the residual in front (nobody would read it) and every host wait,
+// plus the record.  The caller has run cg_prepare and mg_prepare and owns h->mg_rec.
+template <typename T>
+void mg_enqueue_step_solve(vof2d_ctx* h, int cycles, int criterion) {
+  if (!mg_block_in_effect(h)) {
+    if (mg_depth(h) == 1) (void)hipMemsetAsync(h->cg_fld[1], 0, 2 * h->field_elems * h->esz, h->stream);
+    else
+      for (int k = 1; k <= 2; ++k) (void)hipMemsetAsync(h->mg_cgw[k], 0, h->mg_lv[mg_depth(h) - 1].bytes, h->stream);
+  }
+  L<T>::cg_drift(h, L<T>::cg_sum_ap(h));
+  for (int k = 0; k < cycles; ++k) mg_enqueue_cycle<T>(h);
+  L<T>::cg_residual(h, 1);
+  launch_block(h, kOther, k_mg_step_record, dim3(1), 64u, 0, (const double*)h->cg_sc, h->mg_rec, criterion);
 }
 
 // n cycles: replays of the one captured cycle (a cycle at 1024^2 is some hundred small launches), or the launches themselves

@@ -134,15 +134,20 @@ void jacobi_n(vof2d_ctx* h, int n, bool resid_last, int adapt_par = -1) {
 // single verb): p's ghosts only ever feed values the wall conditions override (u[1] = 0, v[:,1] =
 // 0) or zero stencil coefficients, and the first sweep itself stores the wall-face zeros of u, v
 // the second sweep reads.
+// mg (vof_step_mg): the sweeps of :521-522 are replaced by mg->cycles V-cycles, their residual recorded on the device
+// (mg_enqueue_step_solve, runtime/multigrid.h); everything around them is the same schedule.
+template <typename T> void mg_enqueue_step_solve(vof2d_ctx* h, int cycles, int criterion);
 template <typename T>
 void enqueue_phase(vof2d_ctx* h, int phase, int64_t istep, bool merge_bc = false, bool lean = false, bool virt = false,
-                   int adapt_par = -1 /* istep & 1 when the caller's launch sequence is keyed by the step parity */) {
+                   int adapt_par = -1 /* istep & 1 when the caller's launch sequence is keyed by the step parity */,
+                   const StepMg* mg = nullptr) {
   const bool y_first = (istep % 2 == 0);    // :526, :312-318
   if (phase == 0) {
     // cal_nu_rho (:513) is folded into its consumers: rho/nu = f(F[i,j]) recomputed per cell;
     // :514, :517 and the (sweep-invariant, BC-independent) rhs of :239-241 in one pass
-    L<T>::momentum(h, virt, adapt_par);     // virt: the previous step's set_BC launch was left out (see enqueue_step)
-    jacobi_n<T>(h, h->d.jacobi_iters, false, adapt_par);  // :521-522
+    L<T>::momentum(h, virt, mg ? -1 : adapt_par);     // virt: the previous step's set_BC launch was left out (see enqueue_step)
+    if (mg) mg_enqueue_step_solve<T>(h, mg->cycles, mg->criterion);
+    else jacobi_n<T>(h, h->d.jacobi_iters, false, adapt_par);  // :521-522
     if (!lean) L<T>::template set_bc<BC_P | BC_F>(h);  // p part of :525 / :528; F part of :518 (first step)
   } else if (phase == 1) {
     // :524 inside the first sweep of :526
@@ -159,7 +164,7 @@ void enqueue_phase(vof2d_ctx* h, int phase, int64_t istep, bool merge_bc = false
   }
 }
 template <typename T>
-void enqueue_step(vof2d_ctx* h, int64_t istep, bool lean = false, bool virt = false) {
+void enqueue_step(vof2d_ctx* h, int64_t istep, bool lean = false, bool virt = false, const StepMg* mg = nullptr) {
   const bool full = h->g.wall_lo && h->g.wall_hi;
   if (lean && full && h->fuse_transport) {
     // :524 + :526-527 as ONE kernel: the first sweep's F never goes to memory.  One swap of the
@@ -169,14 +174,15 @@ void enqueue_step(vof2d_ctx* h, int64_t istep, bool lean = false, bool virt = fa
     // wall velocity is zero, update_uv overwrites what p's ghosts would enter, the Jacobi stencil
     // multiplies them by zero coefficients), and that kernel forms them from the interior cells
     // itself.  Whoever else looks at the fields goes through settle_ghosts first.
-    L<T>::momentum(h, virt, (int)(istep & 1));
-    jacobi_n<T>(h, h->d.jacobi_iters, false, (int)(istep & 1));
+    L<T>::momentum(h, virt, mg ? -1 : (int)(istep & 1));   // (no Jacobi launches behind it: no work plan to make)
+    if (mg) mg_enqueue_step_solve<T>(h, mg->cycles, mg->criterion);
+    else jacobi_n<T>(h, h->d.jacobi_iters, false, (int)(istep & 1));
     if (istep % 2 == 0) L<T>::template transport<true>(h); else L<T>::template transport<false>(h);
     swap_F(h);
     if (!virt) L<T>::template set_bc<BC_ALL>(h);
     return;
   }
-  for (int ph = 0; ph < 3; ++ph) enqueue_phase<T>(h, ph, istep, full, lean, false, (int)(istep & 1));
+  for (int ph = 0; ph < 3; ++ph) enqueue_phase<T>(h, ph, istep, full, lean, false, (int)(istep & 1), mg);
   if (lean) L<T>::template set_bc<BC_ALL>(h);   // :518, :525, :528 in one launch
 }
 

@@ -5,6 +5,7 @@
 // context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
 #include "schedule.h"
+#include "multigrid.h"
 
 namespace {
 
@@ -229,6 +230,82 @@ int step_n(vof2d_ctx* h, int64_t nsteps) {
     h->uv_ghosts_dirty = false;
     h->ghosts_virtual = virt;
   }
+  return VOF_OK;
+}
+
+// ---- vof_step_mg: the same three ways minus the batches, the step's sweeps replaced by `cycles` V-cycles (enqueue_step
+// with a StepMg).  The step graphs bake in every field view, the cycle count and the criterion of the record: they are
+// dropped when one of those changes (F and its twin apart: the slots are keyed by the orientation), and with every
+// other graph when a knob does (destroy_graphs).
+int run_step_mg_graph(vof2d_ctx* h, bool virt, const StepMg& mg) {
+  GraphCache& G = h->graphs;
+  void* key[NFIELDS];
+  memcpy(key, h->fld, sizeof(key));
+  key[fF] = key[fF2] = nullptr;
+  if (GraphCache::any(&G.step_mg[0][0], &G.step_mg[0][0] + 4) &&
+      (memcmp(key, h->step_mg_key, sizeof(key)) != 0 || h->step_mg_cycles != mg.cycles || h->step_mg_crit != mg.criterion)) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    GraphCache::clear(&G.step_mg[0][0], &G.step_mg[0][0] + 4);
+  }
+  hipGraphExec_t& exec = G.step_mg[(int)(h->istep & 1)][ori_F(h)];
+  int rc;
+  if (!exec) {
+    if ((rc = capture_or_fail(h, /*upload=*/true, &exec, "the multigrid step graph", [&] {
+          DISPATCH_T(h, enqueue_step<double>(h, h->istep, true, virt, &mg), enqueue_step<float>(h, h->istep, true, virt, &mg));
+        })))
+      return rc;
+    memcpy(h->step_mg_key, key, sizeof(key));
+    h->step_mg_cycles = mg.cycles; h->step_mg_crit = mg.criterion;
+  }
+  HIPCHK(h, hipGraphLaunch(exec, h->stream));
+  if (h->fuse_transport) swap_F(h);     // (a full domain: see run_step_graph)
+  return VOF_OK;
+}
+// nsteps steps; the record of the call into whichever of the three pointers are given (one 32-byte read-back at the end;
+// none, and no wait, if all are null).  The entry point has checked the arguments and that the handle is a full domain.
+int step_mg_n(vof2d_ctx* h, int64_t nsteps, int cycles, int criterion, double* last_residual, double* worst_residual, int64_t* worst_step) {
+  double rec[MGR_N] = {};
+  const int64_t istep0 = h->istep;
+  if (nsteps > 0) {
+    int rc = cg_prepare(h);
+    if (rc) return rc;
+    if ((rc = mg_prepare(h))) return rc;
+    if (!h->mg_rec && hipMalloc(reinterpret_cast<void**>(&h->mg_rec), sizeof(rec)) != hipSuccess) {
+      (void)hipGetLastError();
+      h->mg_rec = nullptr;
+      return fail(h, VOF_ENOMEM, "vof_step_mg: no memory for the residual record");
+    }
+    HIPCHK(h, hipMemsetAsync(h->mg_rec, 0, sizeof(rec), h->stream));
+    // A k_tm batch of vof_step may have left the next step's predictor formed ahead: it is formed again (k_momentum is the
+    // first launch of every step here, and writes the same bits from the same u, v, F), so all that is to do is to hand
+    // the handle back in the state every other entry point expects.
+    (void)settle_ahead(h);
+    const StepMg mg{cycles, criterion};
+    const bool use_graph = !(h->d.flags & VOF_FLAG_NO_GRAPH) && h->mg_graph;
+    for (int64_t s = 0; s < nsteps; ++s) {
+      h->istep += 1;
+      const bool lean = !h->f_ghosts_dirty;
+      const bool virt = step_leaves_ghosts_virtual(h);
+      if (!virt) settle_ghosts(h);
+      const bool captured = use_graph && lean && !h->uv_ghosts_dirty;
+      if (captured) rc = run_step_mg_graph(h, virt, mg);
+      else {
+        DISPATCH_T(h, enqueue_step<double>(h, h->istep, lean, virt, &mg), enqueue_step<float>(h, h->istep, lean, virt, &mg));
+        rc = ensure_ok(h);
+      }
+      if (rc) return rc;
+      h->f_ghosts_dirty = false;
+      h->uv_ghosts_dirty = false;
+      h->ghosts_virtual = virt;
+    }
+    if (last_residual || worst_residual || worst_step) {
+      HIPCHK(h, hipMemcpyAsync(rec, h->mg_rec, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+  }
+  if (last_residual) *last_residual = rec[MGR_LAST];
+  if (worst_residual) *worst_residual = rec[MGR_WORST];
+  if (worst_step) *worst_step = rec[MGR_COUNT] > 0.0 ? istep0 + (int64_t)rec[MGR_WORST_AT] : 0;
   return VOF_OK;
 }
 

@@ -12,7 +12,7 @@
 //   runtime/graphs.h     the keys of the graph cache, the one capture helper
 //   runtime/schedule.h   the per-step schedule, ghost-cell bookkeeping, dropping graphs
 //   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop
-//   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly
+//   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -47,6 +47,7 @@ const Knob kKnobs[] = {
   KNOB("pair_vec4", pair_vec4, false), KNOB("pair_slow10", pair_slow10, false), KNOB("solve_pairs", solve_pairs, false),
   KNOB("tb_slow10", tb_slow10, false), KNOB("tune_period", tune.period, false),
   KNOB("mg_nu", mg_nu, true), KNOB("mg_levels", mg_levels, true), KNOB("mg_graph", mg_graph, true),
+  KNOB("mg_coarse_block", mg_coarse_block, false),
 };
 #undef KNOB
 const Knob* find_knob(const char* name) {
@@ -313,12 +314,7 @@ int vof_set_istep(vof2d_handle h, int64_t istep) {
 }
 
 double vof_residual_value(double max_update, double max_p, int32_t criterion) {
-  if (!(max_update < HUGE_VAL)) return HUGE_VAL;   /* inf or NaN: diverged */
-  if (criterion == VOF_RESID_ABS) return max_update;
-  /* a finite update over a tiny (or zero) max|p_new| must not read as "diverged": the quotient is
-   * clamped to the largest finite double, so only a non-finite UPDATE ever returns +inf */
-  const double q = max_update / (max_p > VOF_RESID_TINY ? max_p : VOF_RESID_TINY);
-  return q < HUGE_VAL ? q : DBL_MAX;
+  return residual_rule(max_update, max_p, criterion);   // (kernels/residual_rule.h: the device forms it by the same lines)
 }
 int vof_jacobi_sweeps_norms(vof2d_handle h, int32_t n, int32_t build_rhs, double* max_update, double* max_p) {
   if (!h || !max_update || !max_p) return VOF_EINVAL;
@@ -415,6 +411,19 @@ int vof_solve_p_mg(vof2d_handle h, double tol, int32_t max_cycles, int32_t check
     return fail(h, VOF_ESTATE, "vof_solve_p_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)");
   settle_ghosts(h);
   return mg_solve(h, tol, max_cycles, check_every, criterion, build_rhs, cycles_done, residual, drift);
+}
+
+// ---- time steps whose pressure solve is a fixed number of those cycles (runtime/step.h)
+int vof_step_mg(vof2d_handle h, int64_t nsteps, int32_t cycles, int32_t criterion, double* last_residual, double* worst_residual,
+                int64_t* worst_step) {
+  if (!h) return VOF_EINVAL;
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (cycles < 1) return fail(h, VOF_EINVAL, "cycles must be >= 1");
+  if (criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
+  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
+    return fail(h, VOF_ESTATE, "vof_step_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)");
+  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  return step_mg_n(h, nsteps, cycles, criterion, last_residual, worst_residual, worst_step);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {
@@ -590,6 +599,7 @@ int vof_get_param(vof2d_handle h, const char* name, double* value) {
     *value = (h->g.wall_lo && h->g.wall_hi && h->fuse_transport) ? 1.0 : 0.0;
     return VOF_OK;
   }
+  if (!strcmp(name, "mg_coarse_block")) { *value = mg_block_in_effect(h) ? 1.0 : 0.0; return VOF_OK; }   // 1 if a cycle of this handle ends in k_mg_coarse_block
   if (const Knob* k = find_knob(name))
     if (k->readable) { *value = (double)*k->at(h); return VOF_OK; }
   return fail(h, VOF_EINVAL, "unknown parameter");

@@ -18,7 +18,8 @@
 //   transport.h  k_fct_x, k_fct_y, k_transport   (update_uv + solve_VOF_rudman + post_process_f)
 //   fused_tm.h   k_tm   (k_transport of one step + k_momentum of the next, rows handed over through LDS)
 //   cg.h         k_cg_apply, k_cg_update, k_cg_residual   (extension: conjugate gradients on the pressure equation)
-//   mg.h         k_mg_smooth, k_mg_restrict, k_mg_prolong  (extension: geometric multigrid on the same equation)
+//   mg.h         k_mg_smooth, k_mg_restrict, k_mg_prolong, k_mg_coarse_block, k_mg_step_record  (extension: geometric multigrid on the same equation)
+//   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
 #include "kernels/verbs.h"

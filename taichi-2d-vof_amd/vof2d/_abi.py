@@ -76,6 +76,7 @@ SIGNATURES = {
     "solve_p": (C.c_int, [H, _dbl, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_dbl)]),
     "solve_p_cg": (C.c_int, [H, _dbl, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "solve_p_mg": (C.c_int, [H, _dbl, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "step_mg": (C.c_int, [H, _i64, _i32, _i32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_i64)]),
     "get_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "set_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "get_rows": (C.c_int, [H, _str, _i32, _i32, C.c_void_p, C.c_size_t]),
@@ -112,7 +113,7 @@ SIGNATURES = {
 # entry points that only the GPU library implements (timing / profiling on a HIP stream)
 GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_profile", "reset_profile",
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
-            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg")
+            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg")
 
 
 class Api:

@@ -48,6 +48,13 @@ def build_parser():
                      help='what --jacobi-tol runs: Jacobi sweeps (default, vof_solve_p), conjugate gradients (cg, vof_solve_p_cg) '
                           'or geometric multigrid (mg, vof_solve_p_mg) on the same equation; --jacobi-max caps the iterations '
                           '(cg) or V-cycles (mg), --jacobi-crit as for the sweeps; one GPU')
+    ext.add_argument('--mg-cycles', type=int, default=0, metavar='K',
+                     help='with --pressure-solver mg and without --jacobi-tol: every step runs K V-cycles (K >= 1), warm-started '
+                          'from the previous p, inside the fused step (vof_step_mg); --jacobi-crit is the criterion of the '
+                          'residual the status line reports; one GPU')
+    ext.add_argument('--mg-coarse', choices=['block', 'launches'], default='block',
+                     help='with --mg-cycles: the coarsest-level solve of a cycle as one workgroup (block, default; where that '
+                          'level is small enough) or as the launches of vof_solve_p_mg')
     ext.add_argument('--device', type=int, default=0, help='HIP device ordinal (one GPU; with --gpus N rank r takes device r)')
     ext.add_argument('--vis', type=int, choices=[0, 1, 2, 3, 4], default=0,
                      help='what the reference GUI would display (SPACE cycles it there, :508-509): 0 VOF, 1 u, 2 v, '
@@ -63,6 +70,16 @@ def parse_args(argv=None):
     """build_parser().parse_args plus the combinations argparse cannot express."""
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.mg_cycles != 0:
+        if args.mg_cycles < 1:
+            parser.error("--mg-cycles needs K >= 1")
+        if args.pressure_solver != "mg":
+            parser.error("--mg-cycles counts the V-cycles of --pressure-solver mg: pass that solver, not %s" % args.pressure_solver)
+        if args.jacobi_tol > 0.0:
+            parser.error("--mg-cycles fixes the work of a step, --jacobi-tol ends it on a residual: pass one of them")
+        if args.gpus > 1:
+            parser.error("--mg-cycles runs on one GPU (the levels and sums of a strip would span its neighbours): drop --gpus")
+        return args
     if args.pressure_solver in ("cg", "mg"):
         if not args.jacobi_tol > 0.0:
             parser.error("--pressure-solver %s needs a tolerance: pass --jacobi-tol T (> 0)" % args.pressure_solver)
@@ -79,6 +96,9 @@ def numerics_of(args, dt):
            "jacobi_crit": str(args.jacobi_crit) if args.jacobi_tol > 0.0 else ""}
     if getattr(args, "pressure_solver", "jacobi") in ("cg", "mg"):   # (only then: checkpoints of sweep runs resume as before)
         num["pressure_solver"] = str(args.pressure_solver)
+    if getattr(args, "mg_cycles", 0) > 0:   # (only then, as above)
+        num["mg_cycles"] = int(args.mg_cycles)
+        num["mg_coarse"] = str(args.mg_coarse)
     return num
 
 
@@ -110,6 +130,13 @@ def load_state(path, nx, ny, dtype, numerics=None):
         if have != want:
             raise SystemExit("--resume: %s was written with pressure-solver = %r, this run has %r (pass the same value to continue it)" %
                              (path, have, want))
+        # (... and only by runs with a fixed cycle count)
+        for k, none in (("mg_cycles", 0), ("mg_coarse", "")):
+            have = z["num_" + k].item() if "num_" + k in z.files else none
+            want = numerics.get(k, none)
+            if have != want:
+                raise SystemExit("--resume: %s was written with %s = %r, this run has %r (pass the same value to continue it)" %
+                                 (path, k.replace("_", "-"), have, want))
     return {f: z[f] for f in STATE}, int(z["istep"]), int(z["courant_violations"]) if "courant_violations" in z.files else 0
 
 
@@ -123,6 +150,9 @@ class _Single:
                          jacobi_iters=args.jacobi_iters, api=api, **consts)
         self.eng, self.rank, self.args = self.sim.eng, 0, args
         self.base_courant = 0
+        self.mg_worst = (0.0, 0)                     # worst residual of --mg-cycles steps since the last report, its step
+        if getattr(args, "mg_cycles", 0) > 0 and args.mg_coarse == "block":
+            self.eng.set_param("mg_coarse_block", 1)
 
     def init(self, ic):
         self.sim.set_init_F(ic)
@@ -147,10 +177,22 @@ class _Single:
                     self.eng.solve_p(a.jacobi_tol, a.jacobi_max, 10, a.jacobi_crit)
                 sim.update_uv(); sim.set_BC()
                 sim.solve_VOF_rudman(sim.istep); sim.post_process_f(); sim.set_BC()
+        elif getattr(a, "mg_cycles", 0) > 0:
+            _, worst, at = sim.step_mg(n, a.mg_cycles, a.jacobi_crit)
+            if not worst <= self.mg_worst[0]:
+                self.mg_worst = (worst, at)
         elif a.verbs:
             sim.step_verbs(n)
         else:
             sim.step(n)
+
+    def report(self):
+        """What the status line adds for this run ('' for most), and a fresh start of whatever it accumulates."""
+        if getattr(self.args, "mg_cycles", 0) <= 0:
+            return ''
+        worst, at = self.mg_worst
+        self.mg_worst = (0.0, 0)
+        return f' Worst {self.args.jacobi_crit} residual after {self.args.mg_cycles} V-cycles: {worst:8.2e} (step {at}).'
 
     def full(self, name):
         return self.eng.get(name)
@@ -201,6 +243,9 @@ class _Strips:
             e.solve_VOF_rudman(e.istep); e.post_process_f(); e.set_BC()
             self.s.exchange()                         # F, u, v, p: the 8 rows the step consumed are well inside the halo
 
+    def report(self):
+        return ''
+
     def full(self, name):
         return self.s.gather(name)                   # rank 0: (nx+2, ny+2); others: None
 
@@ -230,6 +275,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         raise SystemExit("--verbs and --vis run on one GPU (drop --gpus)")
     if world > 1 and args.pressure_solver in ("cg", "mg"):
         raise SystemExit("--pressure-solver %s runs on one GPU (drop --gpus)" % args.pressure_solver)
+    if world > 1 and getattr(args, "mg_cycles", 0) > 0:
+        raise SystemExit("--mg-cycles runs on one GPU (drop --gpus)")
     if world > 1 and world != args.gpus:
         raise SystemExit("--gpus %d but the launcher started %d ranks" % (args.gpus, world))
     if api is None:
@@ -289,12 +336,13 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                     save_state('data/%08d.npz' % istep, fields, istep, nx, ny, args.dtype, args.ic, warn, numerics)
             if (istep % nstep) == 0:  # Output data every <nstep> steps            (:530)
                 warn = drv.courant()
+                extra = drv.report()
                 Fnp = drv.full("F") if args.s else None
                 if not lead:
                     continue
                 from .vis import OPTIONS, save_display
                 say(f'>>> Number of steps:{istep:<5d}, Time:{istep*dt:5.2e} sec. Displaying {OPTIONS[args.vis][0]}.'
-                    + (f' [{warn} Courant warnings]' if warn else ''))
+                    + extra + (f' [{warn} Courant warnings]' if warn else ''))
                 if args.s:
                     import matplotlib
                     matplotlib.use('Agg')

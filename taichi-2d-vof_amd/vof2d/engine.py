@@ -177,6 +177,15 @@ class Engine:
                                      1 if build_rhs else 0, C.byref(it), C.byref(res), C.byref(drift)), "solve_p_mg")
         return it.value, res.value, drift.value
 
+    def step_mg(self, nsteps, cycles, criterion="rel"):
+        """vof_step_mg: nsteps time steps whose pressure solve is `cycles` V-cycles of solve_p_mg's cycle, warm-started
+        from p; returns (residual of the last step, worst residual of the call, the istep it belongs to).  One read-back,
+        at the end.  Knobs (set_param): mg_nu, mg_levels, mg_graph, mg_coarse_block."""
+        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        last, worst, at = C.c_double(), C.c_double(), C.c_int64()
+        self._ck(self.api.step_mg(self._h, int(nsteps), int(cycles), crit, C.byref(last), C.byref(worst), C.byref(at)), "step_mg")
+        return last.value, worst.value, at.value
+
     def jacobi_sweeps_norms(self, n, build_rhs=True):
         """(max|p_new - p|, max|p_new|) of the last of n sweeps over the owned rows."""
         upd, pm = C.c_double(), C.c_double()
@@ -301,7 +310,7 @@ class Engine:
         for k in ("k_momentum", "k_set_bc", "k_jacobi", "k_jacobi_tb", "k_correct", "k_fct_x", "k_fct_y",
                   "k_transport", "k_normals", "k_kappa", "k_predictor", "k_rhs", "k_jacobi_pair", "k_tm", "k_tm_uv",
                   "k_cg_apply", "k_cg_update", "k_cg_residual", "k_cg_finish",
-                  "k_mg_smooth", "k_mg_restrict", "k_mg_prolong"):
+                  "k_mg_smooth", "k_mg_restrict", "k_mg_prolong", "k_mg_coarse_block"):
             us, n = C.c_double(), C.c_int64()
             if self.api.get_profile(self._h, k.encode(), C.byref(us), C.byref(n)) != 0:
                 continue   # a kernel this build of the library does not have

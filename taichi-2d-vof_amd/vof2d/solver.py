@@ -126,6 +126,11 @@ class VOF2D:
     def step(self, nsteps=1):
         self.eng.step(nsteps)
 
+    def step_mg(self, nsteps, cycles, criterion="rel"):
+        """nsteps steps with `cycles` multigrid V-cycles each instead of the sweeps (vof_step_mg):
+        (last residual, worst residual, its step)."""
+        return self.eng.step_mg(nsteps, cycles, criterion)
+
     @property
     def istep(self):
         return self.eng.istep
