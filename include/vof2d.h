@@ -192,6 +192,50 @@ int vof_solve_p_mg(vof2d_handle h, double tol, int32_t max_cycles, int32_t check
  * other bits than the launches'. */
 int vof_step_mg(vof2d_handle h, int64_t nsteps, int32_t cycles, int32_t criterion,
                 double* last_residual, double* worst_residual, int64_t* worst_step);
+/* Extension: what a user of a volume-of-fluid code watches, reduced on the device in one pass over F, u, v instead of
+ * copying the fields to the host.  A row is VOF_DIAG_N doubles (unused slots read 0), over the handle's owned interior
+ * cells, i in [max(own_lo, 1), min(own_hi, nx)] and j in [1, ny]; every operand is converted to double first:
+ *   ISTEP     the handle's istep                      CELLS   the number of cells summed
+ *   SUM_F     sum F                                   SUM_FI, SUM_FJ   sum F * i, sum F * j  (global integer indices: the host
+ *             forms the coordinates, xc = (SUM_FI / SUM_F - 0.5) dx)
+ *   SUM_KE    sum rho * 0.5 * (uc * uc + vc * vc), uc = (u[i,j] + u[i+1,j]) * 0.5, vc = (v[i,j] + v[i,j+1]) * 0.5 (interp_velocity,
+ *             :492), rho = rho_g * (1 - Fc) + rho_l * Fc (:202) with the plain clamp Fc = fmin(fmax(F, 0), 1)
+ *   SUM_DIV2, MAX_DIV   sum div * div and max |div|, div = (u[i+1,j] - u[i,j]) * dxi + (v[i,j+1] - v[i,j]) * dyi, with the dxi, dyi of
+ *             vof_get_param: what the projection leaves in u, v
+ *   MAX_U, MAX_V   max(|u[i,j]|, |u[i+1,j]|) and max(|v[i,j]|, |v[i,j+1]|) over the cells (both faces of every owned cell)
+ *   MIN_F, MAX_F
+ * The expression order is stated in csrc/kernels/diag.h; the sums are formed in double in a fixed order (no atomics): the
+ * same state gives the same bits.  A NaN operand of a maximum counts as +inf (a NaN F: MAX_F = +inf, MIN_F = -inf), the
+ * sums propagate it; nothing is skipped.  The values are those of the arrays vof_get_field would return at that moment
+ * (ghost cells a fused step left virtual are settled first); no field, istep, counter or cached graph changes, and a
+ * vof_step that follows gives the bits it would have given without the call.  Works on strip handles: the value is the
+ * handle's partial (row own_hi + 1 of u is a stored halo row), the driver combines the partials (vof2d/diag.py).
+ * Synchronises and copies the row to out. */
+#define VOF_DIAG_ISTEP 0
+#define VOF_DIAG_SUM_F 1
+#define VOF_DIAG_SUM_FI 2
+#define VOF_DIAG_SUM_FJ 3
+#define VOF_DIAG_SUM_KE 4
+#define VOF_DIAG_SUM_DIV2 5
+#define VOF_DIAG_MAX_DIV 6
+#define VOF_DIAG_MAX_U 7
+#define VOF_DIAG_MAX_V 8
+#define VOF_DIAG_MIN_F 9
+#define VOF_DIAG_MAX_F 10
+#define VOF_DIAG_CELLS 11
+#define VOF_DIAG_N 16
+int vof_diagnostics(vof2d_handle h, double* out /* VOF_DIAG_N */);
+/* Extension: nsteps steps that record a time series of those rows on the device.  For r = 0 .. nsteps / every - 1: `every`
+ * steps -- exactly vof_step(h, every) if mg_cycles == 0, exactly vof_step_mg(h, every, mg_cycles, criterion, NULL, NULL,
+ * NULL) if mg_cycles >= 1 -- then row r; a remainder of nsteps % every steps is stepped and gets no row.  Nothing waits
+ * for the device before the end of the call; then one copy writes rows x VOF_DIAG_N doubles to out and *rows_written
+ * (may be NULL) is set.  Row r equals, bit for bit, what the loop "step `every` steps; vof_diagnostics" yields on a twin
+ * handle, and every readable field, istep and courant_violations end where that loop (and a single vof_step(nsteps))
+ * leaves them.  every < 1, nsteps < 0, cap_rows < nsteps / every, out == NULL with a row due, mg_cycles < 0, a bad
+ * criterion with mg_cycles >= 1: VOF_EINVAL; a strip handle: VOF_ESTATE; the handle is left untouched by either.
+ * nsteps == 0 does nothing and reports 0 rows. */
+int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
+                  double* out, int64_t cap_rows, int64_t* rows_written);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

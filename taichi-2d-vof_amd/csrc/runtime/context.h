@@ -219,6 +219,10 @@ struct vof2d_ctx {
   double* mg_rec = nullptr;
   void* step_mg_key[NFIELDS] = {};   // the field views (F and its twin apart: the graphs are keyed by the orientation)
   int step_mg_cycles = 0, step_mg_crit = 0;
+  // vof_diagnostics / vof_step_diag (runtime/diag_reduce.h): one partial per block of k_diag, and the rows recorded on the device
+  double* diag_part = nullptr;
+  double* diag_rows = nullptr;       // diag_cap rows of VOF_DIAG_N doubles, grown on demand
+  int64_t diag_cap = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

@@ -13,6 +13,7 @@
 //   runtime/schedule.h   the per-step schedule, ghost-cell bookkeeping, dropping graphs
 //   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
+//   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -22,6 +23,7 @@
 #include "runtime/schedule.h"
 #include "runtime/multigrid.h"
 #include "runtime/step.h"
+#include "runtime/diag_reduce.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -187,6 +189,7 @@ int vof_destroy(vof2d_handle h) {
   if (h->cg_arena) (void)hipFree(h->cg_arena);
   if (h->cg_part) (void)hipFree(h->cg_part);
   mg_release(h);
+  diag_release(h);
   if (h->arena) (void)hipFree(h->arena);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -424,6 +427,35 @@ int vof_step_mg(vof2d_handle h, int64_t nsteps, int32_t cycles, int32_t criterio
     return fail(h, VOF_ESTATE, "vof_step_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)");
   if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
   return step_mg_n(h, nsteps, cycles, criterion, last_residual, worst_residual, worst_step);
+}
+
+// ---- diagnostics on the device (kernels/diag.h, runtime/diag_reduce.h)
+int vof_diagnostics(vof2d_handle h, double* out) {
+  if (!h || !out) return VOF_EINVAL;
+  int rc = diag_prepare(h, 1);
+  if (rc) return rc;
+  if ((rc = diag_enqueue(h, 0))) return rc;
+  HIPCHK(h, hipMemcpyAsync(out, h->diag_rows, VOF_DIAG_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return VOF_OK;
+}
+int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
+                  int64_t* rows_written) {
+  if (!h) return VOF_EINVAL;
+  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
+  if (mg_cycles >= 1 && criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
+  if (cap_rows < nsteps / every) return fail(h, VOF_EINVAL, "cap_rows is smaller than nsteps / every");
+  if (!out && nsteps / every > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one row is due");
+  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
+    return fail(h, VOF_ESTATE, "vof_step_diag needs the whole domain in one handle (a strip's steps need their exchanges: call vof_diagnostics between them)");
+  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (nsteps == 0) {
+    if (rows_written) *rows_written = 0;
+    return VOF_OK;
+  }
+  return step_diag_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

@@ -62,6 +62,11 @@ def build_parser():
     ext.add_argument('--save-every', type=int, default=0, metavar='N',
                      help='write data/NNNNNNNN.npz (F, u, v, p with ghost cells, istep) every N steps: the use the '
                           "reference's data/ directory (:501) was made for")
+    ext.add_argument('--diag-every', type=int, default=None, metavar='N',
+                     help='every N steps append a row to data/diagnostics.csv: liquid volume, centroid, kinetic energy, max and '
+                          'rms divergence of u, v, max |u|, max |v|, CFL number, min and max F, reduced on the device '
+                          '(vof_step_diag; with --jacobi-tol, --verbs or --gpus N vof_diagnostics at the multiples of N); the '
+                          'status line then reports volume, div_max and cfl')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
 
@@ -70,6 +75,8 @@ def parse_args(argv=None):
     """build_parser().parse_args plus the combinations argparse cannot express."""
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.diag_every is not None and args.diag_every < 1:
+        parser.error("--diag-every needs N >= 1")
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -151,6 +158,10 @@ class _Single:
         self.eng, self.rank, self.args = self.sim.eng, 0, args
         self.base_courant = 0
         self.mg_worst = (0.0, 0)                     # worst residual of --mg-cycles steps since the last report, its step
+        self.diag_every = getattr(args, "diag_every", None) or 0
+        # the fused steps record their rows on the device (vof_step_diag); the Python loops ask at the multiples of N
+        self.diag_in_advance = bool(self.diag_every) and not (args.jacobi_tol > 0.0 or args.verbs)
+        self.diag_rows = []
         if getattr(args, "mg_cycles", 0) > 0 and args.mg_coarse == "block":
             self.eng.set_param("mg_coarse_block", 1)
 
@@ -177,18 +188,45 @@ class _Single:
                     self.eng.solve_p(a.jacobi_tol, a.jacobi_max, 10, a.jacobi_crit)
                 sim.update_uv(); sim.set_BC()
                 sim.solve_VOF_rudman(sim.istep); sim.post_process_f(); sim.set_BC()
+        elif self.diag_in_advance:
+            self._advance_diag(n)
         elif getattr(a, "mg_cycles", 0) > 0:
-            _, worst, at = sim.step_mg(n, a.mg_cycles, a.jacobi_crit)
-            if not worst <= self.mg_worst[0]:
-                self.mg_worst = (worst, at)
+            self._step_mg(n)
         elif a.verbs:
             sim.step_verbs(n)
         else:
             sim.step(n)
 
+    def _step_mg(self, n):
+        _, worst, at = self.sim.step_mg(n, self.args.mg_cycles, self.args.jacobi_crit)
+        if not worst <= self.mg_worst[0]:
+            self.mg_worst = (worst, at)
+
+    def _advance_diag(self, n):
+        """n fused steps with a row at every multiple of N: plain steps up to the first multiple (a resumed run may start
+        anywhere), then one vof_step_diag for the rest."""
+        from . import diag
+        N, K = self.diag_every, getattr(self.args, "mg_cycles", 0)
+        head = min(n, -self.sim.istep % N)
+        if head:
+            self._step_mg(head) if K > 0 else self.sim.step(head)
+            if self.sim.istep % N == 0:
+                self.diag_rows.append(self.eng.diagnostics())
+        if n - head:
+            # (with --mg-cycles the rows replace the residual record of vof_step_mg: the status line reports div_max)
+            rows = self.sim.step_diag(n - head, N, K, self.args.jacobi_crit)
+            self.diag_rows += [diag.raw_of(r) for r in rows]
+
+    def record_diag(self):
+        self.diag_rows.append(self.eng.diagnostics())
+
+    def take_diag(self):
+        rows, self.diag_rows = self.diag_rows, []
+        return rows
+
     def report(self):
         """What the status line adds for this run ('' for most), and a fresh start of whatever it accumulates."""
-        if getattr(self.args, "mg_cycles", 0) <= 0:
+        if getattr(self.args, "mg_cycles", 0) <= 0 or self.diag_in_advance:
             return ''
         worst, at = self.mg_worst
         self.mg_worst = (0.0, 0)
@@ -216,6 +254,9 @@ class _Strips:
                              comm=comm, dist=getattr(comm, "dist", None), **consts)
         self.eng, self.rank, self.world, self.args = self.s.eng, rank, world, args
         self.base_courant = 0
+        self.diag_every = getattr(args, "diag_every", None) or 0
+        self.diag_in_advance = False
+        self.diag_rows = []
 
     def init(self, ic):
         pass                                         # StripSolver ran set_init_F on its strip
@@ -242,6 +283,13 @@ class _Strips:
             e.update_uv(); e.set_BC()
             e.solve_VOF_rudman(e.istep); e.post_process_f(); e.set_BC()
             self.s.exchange()                         # F, u, v, p: the 8 rows the step consumed are well inside the halo
+
+    def record_diag(self):
+        self.diag_rows.append(self.s.diagnostics())   # (collective: every rank holds the combined row, rank 0 writes it)
+
+    def take_diag(self):
+        rows, self.diag_rows = self.diag_rows, []
+        return rows
 
     def report(self):
         return ''
@@ -316,8 +364,31 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         if lead:
             say(f'>>> Resumed from {args.resume} at step {istep}.')
 
+    diag_every = drv.diag_every
+    stop_at_diag = bool(diag_every) and not drv.diag_in_advance
+    diag_last = None
+    if diag_every and lead:
+        from . import diag
+        dx, dy = eng.get_param("dx"), eng.get_param("dy")
+        diag_path = 'data/diagnostics.csv'
+        if not (args.resume and os.path.exists(diag_path) and os.path.getsize(diag_path) > 0):
+            with open(diag_path, 'w') as f:      # the header once; a resumed run appends to what is there
+                f.write(','.join(('istep', 'time') + diag.DERIVED) + '\n')
+
+    def write_diag(rows):
+        """Append the rows (raw dicts) to data/diagnostics.csv; returns the derived values of the last one."""
+        last = None
+        with open(diag_path, 'a') as f:
+            for raw in rows:
+                last = diag.derive(raw, dx, dy, dt, nx, ny)
+                k = int(raw["ISTEP"])
+                f.write(','.join([str(k), repr(k * dt)] + [repr(float(last[c])) for c in diag.DERIVED]) + '\n')
+        return last
+
     def next_stop(i):
         n = nstep - i % nstep
+        if stop_at_diag:
+            n = min(n, diag_every - i % diag_every)
         if args.save_every:
             n = min(n, args.save_every - i % args.save_every)
         if args.steps:
@@ -329,6 +400,12 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             n = next_stop(istep)
             drv.advance(n)
             istep += n
+            if diag_every:
+                if stop_at_diag and istep % diag_every == 0:
+                    drv.record_diag()
+                rows = drv.take_diag()
+                if lead and rows:
+                    diag_last = write_diag(rows)
             if args.save_every and istep % args.save_every == 0:
                 fields = {f: drv.full(f) for f in STATE}
                 warn = drv.courant()
@@ -342,7 +419,9 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                     continue
                 from .vis import OPTIONS, save_display
                 say(f'>>> Number of steps:{istep:<5d}, Time:{istep*dt:5.2e} sec. Displaying {OPTIONS[args.vis][0]}.'
-                    + extra + (f' [{warn} Courant warnings]' if warn else ''))
+                    + extra
+                    + (f' Volume: {diag_last["volume"]:.6e}, max|div u|: {diag_last["div_max"]:8.2e}, CFL: {diag_last["cfl"]:8.2e}.' if diag_last else '')
+                    + (f' [{warn} Courant warnings]' if warn else ''))
                 if args.s:
                     import matplotlib
                     matplotlib.use('Agg')

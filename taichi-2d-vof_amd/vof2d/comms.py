@@ -1,7 +1,7 @@
 """Process-group plumbing of the strip solver: who am I, how do bytes get from rank 0 to
 everybody, how is a scalar maximised over the ranks.
 
-Two carriers with the same four methods (`broadcast_bytes`, `allreduce_max`, `barrier`,
+Two carriers with the same methods (`broadcast_bytes`, `allreduce_max`, `allreduce_sum`, `barrier`,
 `gather_object`):
 
 * `TorchComm`  wraps torch.distributed (backend "nccl" = RCCL on ROCm, "gloo" on CPU).  The CPU
@@ -71,6 +71,19 @@ class TorchComm:
         t = torch.tensor([float(value)], dtype=torch.float64, device=self.device if self.device is not None else "cpu")
         self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
         return float(t.item())
+
+    def allreduce_sum(self, values, engine=None):
+        """Element-wise sum of a few doubles over the ranks, added in rank order on every rank (the same bits everywhere,
+        whatever the backend's reduction tree)."""
+        import torch
+        dev = self.device if self.device is not None else "cpu"
+        mine = torch.tensor([float(v) for v in values], dtype=torch.float64, device=dev)
+        parts = [torch.empty_like(mine) for _ in range(self.world)]
+        self.dist.all_gather(parts, mine)
+        out = [0.0] * len(values)
+        for t in parts:
+            out = [a + b for a, b in zip(out, t.tolist())]
+        return out
 
     def barrier(self, engine=None):
         self.dist.barrier()
@@ -165,6 +178,19 @@ class EnvComm:
         if engine is None:
             raise RuntimeError("EnvComm reduces through the strip's RCCL communicator: pass the engine")
         return engine.comm_allreduce_max(value)
+
+    def allreduce_sum(self, values, engine=None):
+        """Element-wise sum of a few doubles over the ranks, added in rank order (through the rendezvous directory: a few
+        numbers per call, off the data path)."""
+        if self.world == 1:
+            return [float(v) for v in values]
+        parts = self.gather_object([float(v) for v in values])
+        out = None
+        if self.rank == 0:
+            out = [0.0] * len(values)
+            for p in parts:
+                out = [a + b for a, b in zip(out, p)]
+        return [float(v) for v in self.broadcast_object(out)]
 
     def barrier(self, engine=None):
         self.allreduce_max(0.0, engine)

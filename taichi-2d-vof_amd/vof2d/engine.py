@@ -186,6 +186,25 @@ class Engine:
         self._ck(self.api.step_mg(self._h, int(nsteps), int(cycles), crit, C.byref(last), C.byref(worst), C.byref(at)), "step_mg")
         return last.value, worst.value, at.value
 
+    def diagnostics(self):
+        """vof_diagnostics: one fixed-order pass over F, u, v on the owned interior cells; the raw row as a dict keyed by
+        diag.NAMES (a strip's value is its partial: diag.combine; the physical quantities: diag.derive)."""
+        from . import diag
+        row = (C.c_double * _abi.VOF_DIAG_N)()
+        self._ck(self.api.diagnostics(self._h, row), "diagnostics")
+        return diag.raw_of(list(row))
+
+    def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
+        """vof_step_diag: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), a row of diagnostics recorded on
+        the device behind every `every` of them, one read-back at the end; returns the (rows, VOF_DIAG_N) float64 array."""
+        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        rows = max(int(nsteps), 0) // int(every) if int(every) >= 1 else 0
+        out = np.zeros((rows, _abi.VOF_DIAG_N), dtype=np.float64)
+        done = C.c_int64()
+        self._ck(self.api.step_diag(self._h, int(nsteps), int(every), int(mg_cycles), crit,
+                                    out.ctypes.data_as(C.POINTER(C.c_double)) if rows else None, rows, C.byref(done)), "step_diag")
+        return out[:done.value]
+
     def jacobi_sweeps_norms(self, n, build_rhs=True):
         """(max|p_new - p|, max|p_new|) of the last of n sweeps over the owned rows."""
         upd, pm = C.c_double(), C.c_double()

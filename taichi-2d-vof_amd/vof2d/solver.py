@@ -131,6 +131,14 @@ class VOF2D:
         (last residual, worst residual, its step)."""
         return self.eng.step_mg(nsteps, cycles, criterion)
 
+    def diagnostics(self):
+        """The raw row of vof_diagnostics as a dict (vof2d/diag.py: NAMES, derive)."""
+        return self.eng.diagnostics()
+
+    def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
+        """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
+        return self.eng.step_diag(nsteps, every, mg_cycles, criterion)
+
     @property
     def istep(self):
         return self.eng.istep

@@ -458,6 +458,22 @@ class StripSolver:
     def solve_p_residual(self, tol, max_iters, check_every=10):
         return self.solve_p(tol, max_iters, check_every, "abs")
 
+    def diagnostics(self):
+        """vof_diagnostics of the whole domain on every rank: this strip's partial, the five sums and CELLS added over the
+        ranks (in rank order), the extrema by MAX (MIN_F as the MAX of its negative).  world == 1: the single-domain value."""
+        from . import diag
+        raw = self.eng.diagnostics()
+        if self.world == 1:
+            return raw
+        with self._ctx():
+            sums = self.comm.allreduce_sum([raw[k] for k in diag.SUMS], self.eng)
+            out = dict(raw)
+            out.update(zip(diag.SUMS, sums))
+            for k in diag.MAXIMA:
+                out[k] = self.comm.allreduce_max(raw[k], self.eng)
+            out["MIN_F"] = -self.comm.allreduce_max(-raw["MIN_F"], self.eng)
+        return out
+
     def sync(self):
         self.eng.sync()
 
