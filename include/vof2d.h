@@ -236,6 +236,45 @@ int vof_diagnostics(vof2d_handle h, double* out /* VOF_DIAG_N */);
  * nsteps == 0 does nothing and reports 0 rows. */
 int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
                   double* out, int64_t cap_rows, int64_t* rows_written);
+/* Extension: the interface itself, as one PLIC (piecewise-linear) segment per mixed cell, reconstructed and compacted on the device
+ * instead of copying F to the host and contouring it.  Cells: the handle's owned interior cells, i in [max(own_lo, 1), min(own_hi, nx)],
+ * j in [1, ny]; every operand is converted to double first (one code path for both dtypes).
+ *   mixed       eps < F && F < 1 - eps (a NaN F is not mixed); eps NaN, negative or >= 0.5: VOF_EINVAL
+ *   mxsum, mysum  Youngs' gradient of 2dvof.py:287-297 in that order of operations, with the double dx, dy of vof_get_param, on the array
+ *               vof_get_field would return at that moment (ghost cells a fused step left virtual are settled first)
+ *   degenerate  |mxsum| < 1e-10 && |mysum| < 1e-10 (the reference's test, :300): counted in SUM_DEGENERATE, no row
+ *   the line    in the unit cell, with a = |mxsum| dx and b = |mysum| dy scaled to a + b = 1, n1 = min, n2 = max, Fm = min(F, 1 - F):
+ *               alpha = sqrt(2 n1 n2 Fm) if 2 n2 Fm < n1, else n2 Fm + n1 / 2; alpha -> 1 - alpha if F > 0.5; liquid is a xi + b eta < alpha.
+ *               One end lies on xi = 0 if b > 0 and alpha <= b, else on eta = 1; the other on eta = 0 if a > 0 and alpha <= a, else on
+ *               xi = 1; xi -> 1 - xi if mxsum < 0, eta -> 1 - eta if mysum < 0; x = (i - 1 + xi) dx, y = (j - 1 + eta) dy
+ *   a row       VOF_IFACE_N doubles: I, J (global cell indices), (X0, Y0) -> (X1, Y1) ordered so that the liquid lies to the LEFT,
+ *               (NX, NY) = (mxsum, mysum) / its Euclidean norm: the unit normal in physical space, liquid -> gas
+ * The expression order is stated in csrc/kernels/interface.h.  Rows come in ascending (i, j) order, i first.  At most cap_rows rows are
+ * written and nothing behind min(SEGMENTS, cap_rows) rows is touched; `summary` always describes ALL segments, so rows = NULL with
+ * cap_rows = 0 sizes a buffer or reads the length alone:
+ *   SUM_SEGMENTS    rows that exist (may exceed cap_rows)          SUM_DEGENERATE  mixed cells without an orientation
+ *   SUM_LENGTH      sum of sqrt(ddx * ddx + ddy * ddy) over all segments, in double, in the fixed order that file states
+ *   SUM_ISTEP       the handle's istep
+ * No atomics anywhere: the same state and call give the same bytes.  No field, istep, counter or cached graph changes, and a vof_step /
+ * vof_step_mg / vof_step_diag that follows gives the bits it would have given without the call.  Works on strip handles: the value is
+ * the strip's own rows (the neighbours i -+ 1 of an owned row are stored halo rows); the strips' rows in rank order are the domain's
+ * list.  rows == NULL with cap_rows > 0, cap_rows < 0, summary == NULL, a bad eps, more than 2^31 - 1 cells: VOF_EINVAL, the handle
+ * untouched.  Synchronises and copies out. */
+#define VOF_IFACE_I 0   /* global cell indices, as doubles */
+#define VOF_IFACE_J 1
+#define VOF_IFACE_X0 2  /* end points in physical coordinates; liquid lies to the LEFT of (X0,Y0) -> (X1,Y1) */
+#define VOF_IFACE_Y0 3
+#define VOF_IFACE_X1 4
+#define VOF_IFACE_Y1 5
+#define VOF_IFACE_NX 6  /* unit normal in physical space, liquid -> gas (the direction of mxsum, mysum) */
+#define VOF_IFACE_NY 7
+#define VOF_IFACE_N 8
+#define VOF_IFACE_SUM_SEGMENTS 0   /* slots of `summary`: rows that exist (may exceed cap_rows) */
+#define VOF_IFACE_SUM_DEGENERATE 1 /* mixed cells with no orientation: counted, no row */
+#define VOF_IFACE_SUM_LENGTH 2     /* sum of the segments' physical lengths, ALL segments, fixed order */
+#define VOF_IFACE_SUM_ISTEP 3
+#define VOF_IFACE_SUM_N 4
+int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary /* VOF_IFACE_SUM_N */);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

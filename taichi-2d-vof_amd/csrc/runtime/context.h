@@ -223,6 +223,12 @@ struct vof2d_ctx {
   double* diag_part = nullptr;
   double* diag_rows = nullptr;       // diag_cap rows of VOF_DIAG_N doubles, grown on demand
   int64_t diag_cap = 0;
+  // vof_interface (runtime/interface.h): the segment count of every (row, column tile), turned into offsets in place; behind it, in
+  // the same allocation, one partial per block of k_iface and the summary; the segments, grown on demand
+  int* iface_cnt = nullptr;
+  double* iface_part = nullptr;
+  double* iface_rows = nullptr;      // iface_cap rows of VOF_IFACE_N doubles
+  int64_t iface_cap = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

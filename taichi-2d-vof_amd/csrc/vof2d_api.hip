@@ -14,6 +14,7 @@
 //   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
 //   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
+//   runtime/interface.h  the buffers, launches and copies of vof_interface
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -24,6 +25,7 @@
 #include "runtime/multigrid.h"
 #include "runtime/step.h"
 #include "runtime/diag_reduce.h"
+#include "runtime/interface.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -190,6 +192,7 @@ int vof_destroy(vof2d_handle h) {
   if (h->cg_part) (void)hipFree(h->cg_part);
   mg_release(h);
   diag_release(h);
+  iface_release(h);
   if (h->arena) (void)hipFree(h->arena);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -456,6 +459,15 @@ int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycl
     return VOF_OK;
   }
   return step_diag_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
+}
+
+// ---- the interface as PLIC segments (kernels/interface.h, runtime/interface.h)
+int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary) {
+  if (!h || !summary) return VOF_EINVAL;
+  if (!(eps >= 0.0 && eps < 0.5)) return fail(h, VOF_EINVAL, "eps must lie in [0, 0.5)");
+  if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
+  if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_interface keeps 32-bit offsets: at most 2^31 - 1 cells");
+  return iface_run(h, eps, rows, cap_rows, summary);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

@@ -20,6 +20,7 @@
 //   cg.h         k_cg_apply, k_cg_update, k_cg_residual   (extension: conjugate gradients on the pressure equation)
 //   mg.h         k_mg_smooth, k_mg_restrict, k_mg_prolong, k_mg_coarse_block, k_mg_step_record  (extension: geometric multigrid on the same equation)
 //   diag.h       k_diag, k_diag_finish   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
+//   interface.h  k_iface, k_iface_scan   (extension: the interface as PLIC segments, counted, scanned and emitted in (i, j) order)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
@@ -33,3 +34,4 @@
 #include "kernels/cg.h"
 #include "kernels/mg.h"
 #include "kernels/diag.h"
+#include "kernels/interface.h"

@@ -16,6 +16,9 @@ VOF_XCHG_F, VOF_XCHG_U, VOF_XCHG_V, VOF_XCHG_P = 1, 2, 4, 8
 VOF_XCHG_US, VOF_XCHG_VS, VOF_XCHG_RHS = 16, 32, 64
 VOF_RESID_ABS, VOF_RESID_REL, VOF_RESID_TINY = 0, 1, 1e-300
 VOF_DIAG_N = 16   # doubles in a row of vof_diagnostics (the slots: vof2d/diag.py)
+# vof_interface: the slots of a segment row and of the summary (vof2d/interface.py)
+VOF_IFACE_I, VOF_IFACE_J, VOF_IFACE_X0, VOF_IFACE_Y0, VOF_IFACE_X1, VOF_IFACE_Y1, VOF_IFACE_NX, VOF_IFACE_NY, VOF_IFACE_N = range(9)
+VOF_IFACE_SUM_SEGMENTS, VOF_IFACE_SUM_DEGENERATE, VOF_IFACE_SUM_LENGTH, VOF_IFACE_SUM_ISTEP, VOF_IFACE_SUM_N = range(5)
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -80,6 +83,7 @@ SIGNATURES = {
     "step_mg": (C.c_int, [H, _i64, _i32, _i32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_i64)]),
     "diagnostics": (C.c_int, [H, C.POINTER(_dbl)]),
     "step_diag": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
+    "interface": (C.c_int, [H, _dbl, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
     "get_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "set_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "get_rows": (C.c_int, [H, _str, _i32, _i32, C.c_void_p, C.c_size_t]),
@@ -116,7 +120,7 @@ SIGNATURES = {
 # entry points that only the GPU library implements (timing / profiling on a HIP stream)
 GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_profile", "reset_profile",
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
-            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag")
+            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface")
 
 
 class Api:

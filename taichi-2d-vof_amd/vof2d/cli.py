@@ -67,6 +67,10 @@ def build_parser():
                           'rms divergence of u, v, max |u|, max |v|, CFL number, min and max F, reduced on the device '
                           '(vof_step_diag; with --jacobi-tol, --verbs or --gpus N vof_diagnostics at the multiples of N); the '
                           'status line then reports volume, div_max and cfl')
+    ext.add_argument('--interface-every', type=int, default=None, metavar='N',
+                     help='every N steps write data/interface_NNNNNN.npy -- the interface as one PLIC segment per mixed cell, '
+                          'rows of i, j, x0, y0, x1, y1, nx, ny extracted on the device (vof_interface) -- and append istep, '
+                          'segments, degenerate, length to data/interface.csv; with -s the VOF frame draws the segments')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
 
@@ -77,6 +81,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.diag_every is not None and args.diag_every < 1:
         parser.error("--diag-every needs N >= 1")
+    if args.interface_every is not None and args.interface_every < 1:
+        parser.error("--interface-every needs N >= 1")
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -220,6 +226,9 @@ class _Single:
     def record_diag(self):
         self.diag_rows.append(self.eng.diagnostics())
 
+    def interface(self):
+        return self.eng.interface()
+
     def take_diag(self):
         rows, self.diag_rows = self.diag_rows, []
         return rows
@@ -286,6 +295,9 @@ class _Strips:
 
     def record_diag(self):
         self.diag_rows.append(self.s.diagnostics())   # (collective: every rank holds the combined row, rank 0 writes it)
+
+    def interface(self):
+        return self.s.interface()                    # (collective: rank 0 holds the domain's list, the others None)
 
     def take_diag(self):
         rows, self.diag_rows = self.diag_rows, []
@@ -375,6 +387,14 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             with open(diag_path, 'w') as f:      # the header once; a resumed run appends to what is there
                 f.write(','.join(('istep', 'time') + diag.DERIVED) + '\n')
 
+    # the interface is read between calls (vof_interface records nothing in advance): every step loop is cut at the multiples of N
+    iface_every = getattr(args, "interface_every", None) or 0
+    iface_last = None
+    iface_path = 'data/interface.csv'
+    if iface_every and lead and not (args.resume and os.path.exists(iface_path) and os.path.getsize(iface_path) > 0):
+        with open(iface_path, 'w') as f:
+            f.write('istep,segments,degenerate,length\n')
+
     def write_diag(rows):
         """Append the rows (raw dicts) to data/diagnostics.csv; returns the derived values of the last one."""
         last = None
@@ -389,6 +409,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         n = nstep - i % nstep
         if stop_at_diag:
             n = min(n, diag_every - i % diag_every)
+        if iface_every:
+            n = min(n, iface_every - i % iface_every)
         if args.save_every:
             n = min(n, args.save_every - i % args.save_every)
         if args.steps:
@@ -406,6 +428,13 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                 rows = drv.take_diag()
                 if lead and rows:
                     diag_last = write_diag(rows)
+            if iface_every and istep % iface_every == 0:
+                iface_last = drv.interface()
+                if lead:
+                    seg, summ = iface_last
+                    np.save('data/interface_%06d.npy' % istep, seg)
+                    with open(iface_path, 'a') as f:
+                        f.write('%d,%d,%d,%r\n' % (istep, summ["SEGMENTS"], summ["DEGENERATE"], float(summ["LENGTH"])))
             if args.save_every and istep % args.save_every == 0:
                 fields = {f: drv.full(f) for f in STATE}
                 warn = drv.courant()
@@ -415,6 +444,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                 warn = drv.courant()
                 extra = drv.report()
                 Fnp = drv.full("F") if args.s else None
+                if args.s and iface_every and istep % iface_every != 0:
+                    iface_last = drv.interface()      # (the frame shows the interface of its own step)
                 if not lead:
                     continue
                 from .vis import OPTIONS, save_display
@@ -433,6 +464,9 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                     plt.figure(figsize=(fx, fy))
                     plt.axis('off')
                     plt.contourf(Fnp.T, cmap=plt.cm.Blues)
+                    if iface_every:
+                        from .vis import draw_segments
+                        draw_segments(plt.gca(), iface_last[0], eng.get_param("dx"), eng.get_param("dy"))
                     plt.savefig(f'output/{count:06d}-f.png')
                     plt.close()
     except KeyboardInterrupt:

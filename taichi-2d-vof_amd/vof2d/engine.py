@@ -205,6 +205,25 @@ class Engine:
                                     out.ctypes.data_as(C.POINTER(C.c_double)) if rows else None, rows, C.byref(done)), "step_diag")
         return out[:done.value]
 
+    def interface(self, eps=1e-6):
+        """vof_interface: one PLIC segment per mixed cell (eps < F < 1 - eps) of the owned interior rows, reconstructed and
+        compacted on the device in ascending (i, j) order; returns (rows, summary): an (n, VOF_IFACE_N) float64 array (the
+        slots: vof2d/interface.py) and the summary as a dict keyed by interface.SUMMARY.  One call with the capacity the
+        last call needed (plus a margin); a second one if the list has outgrown it."""
+        from . import interface
+        ptr = C.POINTER(C.c_double)
+        summ = (C.c_double * _abi.VOF_IFACE_SUM_N)()
+        cap = getattr(self, "_iface_cap", 0)
+        while True:
+            rows = np.empty((cap, _abi.VOF_IFACE_N), dtype=np.float64)
+            self._ck(self.api.interface(self._h, float(eps), rows.ctypes.data_as(ptr) if cap else None, cap, summ), "interface")
+            n = int(summ[_abi.VOF_IFACE_SUM_SEGMENTS])
+            if n <= cap:
+                break
+            cap = n + n // 8 + 16
+        self._iface_cap = cap
+        return rows[:n].copy(), interface.summary_of(list(summ))
+
     def jacobi_sweeps_norms(self, n, build_rhs=True):
         """(max|p_new - p|, max|p_new|) of the last of n sweeps over the owned rows."""
         upd, pm = C.c_double(), C.c_double()

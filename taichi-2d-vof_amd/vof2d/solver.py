@@ -135,6 +135,10 @@ class VOF2D:
         """The raw row of vof_diagnostics as a dict (vof2d/diag.py: NAMES, derive)."""
         return self.eng.diagnostics()
 
+    def interface(self, eps=1e-6):
+        """The interface as PLIC segments, extracted on the device (vof_interface): (rows, summary), vof2d/interface.py."""
+        return self.eng.interface(eps)
+
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)

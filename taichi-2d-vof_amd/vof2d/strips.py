@@ -474,6 +474,17 @@ class StripSolver:
             out["MIN_F"] = -self.comm.allreduce_max(-raw["MIN_F"], self.eng)
         return out
 
+    def interface(self, eps=1e-6):
+        """vof_interface of the whole domain on rank 0 (None elsewhere): every strip extracts its own rows, rank 0 gathers
+        them in rank order (which is the domain's (i, j) order) and adds the counts and lengths in that order.
+        world == 1: the single-domain value."""
+        from . import interface
+        mine = self.eng.interface(eps)
+        if self.world == 1:
+            return mine
+        parts = self.comm.gather_object(mine)
+        return interface.combine(parts) if self.rank == 0 else None
+
     def sync(self):
         self.eng.sync()
 

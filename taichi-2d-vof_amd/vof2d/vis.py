@@ -40,6 +40,19 @@ def colour_image(rgb_buf, option):
     return cmap(np.asarray(rgb_buf).transpose(1, 0)[::-1])
 
 
+def draw_segments(ax, rows, dx, dy, **kw):
+    """The PLIC segments of vof_interface (vof2d/interface.py) over a picture of the array F.T drawn in index coordinates
+    (plt.contourf(F.T): cell (i, j), centred at ((i - 0.5) dx, (j - 0.5) dy), sits at (i, j))."""
+    from matplotlib.collections import LineCollection
+    from . import interface as I
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, I.VOF_IFACE_N)
+    ends = np.stack((rows[:, [I.X0, I.Y0]], rows[:, [I.X1, I.Y1]]), axis=1) / np.array([dx, dy]) + 0.5
+    style = {"colors": "k", "linewidths": 0.6}
+    style.update(kw)
+    ax.add_collection(LineCollection(ends, **style))
+    return len(ends)
+
+
 def save_display(path, sim, option, arrow_spacing=4):
     """What the reference's GUI would show for vis_option % 5 == option, written to `path`."""
     import matplotlib
