@@ -14,13 +14,13 @@
 //   s <- z + beta s,  q = L s,  alpha = dot(r, z) / dot(s, q),  p += alpha s,  r -= alpha q,  beta = dot(r, z)_new / dot(r, z)
 // (both dot products are <= 0; only their quotients are used).
 //
-// Reductions are reproducible: every lane accumulates in double (both field types), lanes -> wave by __shfl_down,
-// waves -> block through LDS in wave order, one partial per block into a buffer indexed by block, and k_cg_finish
-// (one block) adds that buffer in a fixed order and forms alpha / beta ON THE DEVICE -- the host reads nothing between
-// iterations.  No floating-point atomics.  A zero or non-finite denominator sets the stop word instead of dividing;
-// every later launch of the batch then returns at once and the host's check decides.
+// Reductions are reproducible: every lane accumulates in double (both field types) and publishes through the fixed-order
+// reduction of kernels/reduce.h (one sum, two maxima per block); k_cg_finish (one block) folds the partials and forms
+// alpha / beta ON THE DEVICE -- the host reads nothing between iterations.  No floating-point atomics.  A zero or
+// non-finite denominator sets the stop word instead of dividing; every later launch of the batch then returns at once
+// and the host's check decides.
 #pragma once
-#include "common.h"
+#include "reduce.h"
 
 namespace vof {
 
@@ -43,56 +43,15 @@ __device__ __forceinline__ bool cg_tile(const Geom& g, int R, int& j0, int& ra, 
   return ra <= g.ihi;
 }
 
-// max with "a NaN counts as +inf" (norm_acc of kernels/jacobi.h)
-__device__ __forceinline__ double cg_amax(double m, double x) {
-  const double a = __builtin_fabs(x);
-  return a != a ? __builtin_huge_val() : __builtin_fmax(m, a);
-}
-
-// lane values -> one partial per block: a[0] is added, a[1] and a[2] are maxima (>= 0).  Every thread of the block calls it.
-__device__ __forceinline__ void cg_publish(const double (&a)[kCgPart], double* __restrict__ part) {
-  __shared__ double red[4][kCgPart];
-  double w0 = a[0], w1 = a[1], w2 = a[2];
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    w0 += __shfl_down(w0, s, 64);
-    w1 = __builtin_fmax(w1, __shfl_down(w1, s, 64));
-    w2 = __builtin_fmax(w2, __shfl_down(w2, s, 64));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[wave][0] = w0; red[wave][1] = w1; red[wave][2] = w2; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = red[0][0], t1 = red[0][1], t2 = red[0][2];
-    for (int k = 1; k < 4; ++k) { t0 += red[k][0]; t1 = __builtin_fmax(t1, red[k][1]); t2 = __builtin_fmax(t2, red[k][2]); }
-    double* o = part + (size_t)blockIdx.x * kCgPart;
-    o[0] = t0; o[1] = t1; o[2] = t2;
-  }
-}
-
 // ------------------------------------------------------------------ the block partials -> scalars, alpha, beta
-// ONE block of 256 threads: thread t adds partials t, t + 256, ... in that order, then a tree over the threads with a
-// fixed shape.  The launch boundary in front of it is what makes the partials of every other block visible.
+// ONE block of 256 threads folds the partials (fold_partials of kernels/reduce.h); thread 0 acts on the result.  The launch
+// boundary in front of it is what makes the partials of every other block visible.
 __global__ __launch_bounds__(256) void k_cg_finish(const double* __restrict__ part, int nblocks, double* __restrict__ sc,
                                                     int mode, double sum_ap, int restart) {
   __shared__ double red[256][kCgPart];
-  const int t = threadIdx.x;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-  for (int b = t; b < nblocks; b += 256) {
-    const double* o = part + (size_t)b * kCgPart;
-    a0 += o[0]; a1 = __builtin_fmax(a1, o[1]); a2 = __builtin_fmax(a2, o[2]);
-  }
-  red[t][0] = a0; red[t][1] = a1; red[t][2] = a2;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      red[t][0] += red[t + s][0];
-      red[t][1] = __builtin_fmax(red[t][1], red[t + s][1]);
-      red[t][2] = __builtin_fmax(red[t][2], red[t + s][2]);
-    }
-    __syncthreads();
-  }
-  if (t != 0) return;
+  const double zero[kCgPart] = {0.0, 0.0, 0.0};
+  fold_partials<256, 1, 2>(part, nblocks, zero, red);
+  if (threadIdx.x != 0) return;
   const double sum = red[0][0], m1 = red[0][1], m2 = red[0][2];
   if (mode == CG_FIN_SUMB) {          // c = sum(b) / sum(ap)
     sc[CG_SUMB] = sum;
@@ -140,7 +99,7 @@ __global__ __launch_bounds__(256) void k_cg_sum(Geom g, const T* __restrict__ b,
       o += g.pitch;
     }
   }
-  cg_publish(acc, part);
+  block_publish<1, 2>(acc, part);
 }
 
 // ------------------------------------------------------------------ r = (b - c ap) - L p, recomputed from p
@@ -195,7 +154,7 @@ __global__ __launch_bounds__(256) void k_cg_residual(Geom g, Consts<T> c, const 
       o += pitch;
     }
   }
-  cg_publish(acc, part);
+  block_publish<1, 2>(acc, part);
 }
 
 // ------------------------------------------------------------------ s <- z + beta s,  q = L s,  dot(s, q)
@@ -267,7 +226,7 @@ __global__ __launch_bounds__(256) void k_cg_apply(Geom g, Consts<T> c, const T* 
       o += pitch;
     }
   }
-  cg_publish(acc, part);
+  block_publish<1, 2>(acc, part);
 }
 
 // ------------------------------------------------------------------ p += alpha s,  r -= alpha q,  dot(r, z), max|z|, max|p|
@@ -313,7 +272,7 @@ __global__ __launch_bounds__(256) void k_cg_update(Geom g, Consts<T> c, T* __res
       o += g.pitch;
     }
   }
-  cg_publish(acc, part);
+  block_publish<1, 2>(acc, part);
 }
 
 }  // namespace vof

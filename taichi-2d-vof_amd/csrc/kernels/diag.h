@@ -18,13 +18,12 @@
 //   SUM_DIV2 += div * div            MAX_DIV = max(MAX_DIV, |div|)
 //   MAX_U = max(MAX_U, |uw|, |ue|)   MAX_V = max(MAX_V, |vs|, |vn|)
 //   MAX_F = max(MAX_F, f)            MIN_F = -max(-f)
-// A NaN operand of a maximum counts as +inf (cg_amax of kernels/cg.h; a NaN F therefore reads MAX_F = +inf, MIN_F = -inf);
+// A NaN operand of a maximum counts as +inf (cg_amax, diag_max of kernels/reduce.h; a NaN F therefore reads MAX_F = +inf, MIN_F = -inf);
 // the sums propagate it.  No contraction (-ffp-contract=off): each term is the bits of the line above.
 //
-// Order of the sums, fixed: a lane adds its cells row by row, column by column; lanes -> wave by __shfl_down; waves ->
-// block through LDS in wave order; one partial of kDiagPart doubles per block into a buffer indexed by block; k_diag_finish
-// (one block) adds the partials -- thread t takes t, t + 256, ... -- and a tree over its threads.  The reduction of
-// kernels/cg.h widened to five sums and five maxima; no atomics, no LDS beyond the block reduction.
+// Order of the sums, fixed: a lane adds its cells row by row, column by column; from there the reduction of
+// kernels/reduce.h, five sums and five maxima wide: one partial of kDiagPart doubles per block, folded by k_diag_finish
+// (one block of 256 threads).  No atomics, no LDS beyond the reduction.
 // Traffic: F and v rows are loaded once, the u row i + 1 of one iteration is the row i of the next: 3 array passes.
 #pragma once
 #include "cg.h"
@@ -34,36 +33,6 @@ namespace vof {
 // slots of a row of diagnostics (= VOF_DIAG_* of include/vof2d.h)
 enum : int { DG_ISTEP = 0, DG_SUM_F, DG_SUM_FI, DG_SUM_FJ, DG_SUM_KE, DG_SUM_DIV2, DG_MAX_DIV, DG_MAX_U, DG_MAX_V, DG_MIN_F, DG_MAX_F, DG_CELLS, DG_N = 16 };
 constexpr int kDiagSums = 5, kDiagPart = 10;   // doubles per block in the partials buffer: five sums, then five maxima (|div|, |u|, |v|, -F, F)
-
-// max with "a NaN counts as +inf", of signed values
-__device__ __forceinline__ double diag_max(double m, double x) { return x != x ? __builtin_huge_val() : __builtin_fmax(m, x); }
-
-// lane values -> one partial per block: a[0 .. 4] are added, a[5 .. 9] are maxima.  Every thread of the block calls it.
-__device__ __forceinline__ void diag_publish(const double (&a)[kDiagPart], double* __restrict__ part) {
-  __shared__ double red[4][kDiagPart];
-  double w[kDiagPart];
-#pragma unroll
-  for (int k = 0; k < kDiagPart; ++k) w[k] = a[k];
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-#pragma unroll
-    for (int k = 0; k < kDiagSums; ++k) w[k] += __shfl_down(w[k], s, 64);
-#pragma unroll
-    for (int k = kDiagSums; k < kDiagPart; ++k) w[k] = __builtin_fmax(w[k], __shfl_down(w[k], s, 64));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kDiagPart; ++k) red[wave][k] = w[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kDiagPart) {   // thread k folds value k of the four waves, in wave order
-    const int k = threadIdx.x;
-    double t = red[0][k];
-    for (int n = 1; n < 4; ++n) t = k < kDiagSums ? t + red[n][k] : __builtin_fmax(t, red[n][k]);
-    part[(size_t)blockIdx.x * kDiagPart + k] = t;
-  }
-}
 
 // ------------------------------------------------------------------ the pass over F, u, v
 template <typename T, int V>
@@ -111,37 +80,19 @@ __global__ __launch_bounds__(256) void k_diag(Geom g, const T* __restrict__ F, c
       o += pitch;
     }
   }
-  diag_publish(acc, part);
+  block_publish<kDiagSums, kDiagPart - kDiagSums>(acc, part);
 }
 
 // ------------------------------------------------------------------ the block partials -> one row of diagnostics
-// ONE block of 256 threads, the shape of k_cg_finish: thread t folds partials t, t + 256, ... in that order, then a tree
-// over the threads.  Threads 0 .. DG_N - 1 store one slot each of the row (unused slots read 0).  The launch boundary in
-// front of it is what makes the partials of every other block visible.
+// ONE block of 256 threads, the shape of k_cg_finish: fold_partials of kernels/reduce.h, then threads 0 .. DG_N - 1 store
+// one slot each of the row (unused slots read 0).  The launch boundary in front of it is what makes the partials of
+// every other block visible.
 __global__ __launch_bounds__(256) void k_diag_finish(const double* __restrict__ part, int nblocks, double* __restrict__ row, double istep, double cells) {
   __shared__ double red[256][kDiagPart];
   const int t = threadIdx.x;
   const double ninf = -__builtin_huge_val();
-  double a[kDiagPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, ninf, ninf};
-  for (int b = t; b < nblocks; b += 256) {
-    const double* o = part + (size_t)b * kDiagPart;
-#pragma unroll
-    for (int k = 0; k < kDiagSums; ++k) a[k] += o[k];
-#pragma unroll
-    for (int k = kDiagSums; k < kDiagPart; ++k) a[k] = __builtin_fmax(a[k], o[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < kDiagPart; ++k) red[t][k] = a[k];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int k = 0; k < kDiagSums; ++k) red[t][k] += red[t + s][k];
-#pragma unroll
-      for (int k = kDiagSums; k < kDiagPart; ++k) red[t][k] = __builtin_fmax(red[t][k], red[t + s][k]);
-    }
-    __syncthreads();
-  }
+  const double init[kDiagPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, ninf, ninf};
+  fold_partials<256, kDiagSums, kDiagPart - kDiagSums>(part, nblocks, init, red);
   if (t >= DG_N) return;
   double x = 0.0;
   if (t == DG_ISTEP) x = istep;

@@ -32,17 +32,17 @@
 //   k_iface<EMIT = false>  a wave marches its 64 * V columns over its chunk of rows with the rows i - 1, i, i + 1 of F in
 //                          registers (each row of F is loaded once per chunk, plus two lead-in rows) and writes the number of
 //                          segments of every (row, column tile) into cnt[(i - g.ilo) * ntj + tile]; the lengths and the
-//                          degenerate count go through the reduction of kernels/diag.h into one partial per block
+//                          degenerate count go through the reduction of kernels/reduce.h into one partial per block
 //   k_iface_scan           one block: cnt -> exclusive offsets in place (thread t owns a run of consecutive entries; the
 //                          runs' totals are scanned through LDS), and the summary
 //   k_iface<EMIT = true>   recomputes the cells and stores segment k of a (row, tile) at row offset[(row, tile)] + k of
 //                          the output, k being the segment's rank within the wave in column order (ballot + mbcnt over
 //                          the lanes' V cells); rows from `cap` on are not stored
-// Order of the LENGTH sum, fixed: a lane adds the lengths of its cells row by row, column by column; lanes -> wave by
-// __shfl_down; waves -> block through LDS in wave order (diag_publish); k_iface_scan adds the block partials -- thread t
-// takes t, t + 1024, ... -- and a tree over its threads.  The degenerate count travels the same way as a double (exact).
+// Order of the LENGTH sum, fixed: a lane adds the lengths of its cells row by row, column by column; from there the
+// reduction of kernels/reduce.h, two sums wide: one partial of kIfacePart doubles per block, folded by k_iface_scan (one
+// block of 1024 threads).  The degenerate count travels the same way as a double (exact).
 #pragma once
-#include "diag.h"
+#include "cg.h"
 
 namespace vof {
 
@@ -50,6 +50,7 @@ namespace vof {
 enum : int { IF_I = 0, IF_J, IF_X0, IF_Y0, IF_X1, IF_Y1, IF_NX, IF_NY, IF_N = 8 };
 enum : int { IFS_SEGMENTS = 0, IFS_DEGENERATE, IFS_LENGTH, IFS_ISTEP, IFS_N = 4 };
 constexpr int kIfaceScanThreads = 1024;
+constexpr int kIfacePart = 2;   // doubles per block in the partials buffer: the length, the degenerate cells
 
 struct IfaceConsts { double eps, one_m_eps, cx, cy, dx, dy; };
 
@@ -91,15 +92,15 @@ __device__ __forceinline__ int iface_cell(const IfaceConsts& c, const double (&f
 
 // ------------------------------------------------------------------ the pass over F: count (+ length), or emit
 // cnt: EMIT = false, written: segments per (row, tile); EMIT = true, read: the exclusive offsets k_iface_scan left there.
-// part: kDiagPart doubles per block (slot 0: length, slot 1: degenerate cells; the rest unused) -- EMIT = false only.
+// part: kIfacePart doubles per block (slot 0: length, slot 1: degenerate cells) -- EMIT = false only.
 // rows: the output, `cap` rows of IF_N doubles -- EMIT = true only.
 template <typename T, int V, bool EMIT>
 __global__ __launch_bounds__(256) void k_iface(Geom g, const T* __restrict__ F, int R, IfaceConsts c, int* __restrict__ cnt, double* __restrict__ part,
                                                 double* __restrict__ rows, long long cap) {
   int j0, ra, rb;
   const bool active = cg_tile<V>(g, R, j0, ra, rb);
-  const double ninf = -__builtin_huge_val();
-  double acc[kDiagPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, ninf, ninf};
+  double acc[kIfacePart] = {0.0, 0.0};
+  int ndeg = 0;   // the lane's degenerate cells (an integer until the lanes are folded: one register, the same value)
   if (active) {
     const int ny = g.ny;
     const int64_t pitch = g.pitch;
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(256) void k_iface(Geom g, const T* __restrict__ F, 
             }
             ++rank;
           } else if (!EMIT && kind[q] == 1) {
-            acc[1] += 1.0;
+            ++ndeg;
           }
         }
       }
@@ -166,20 +167,23 @@ __global__ __launch_bounds__(256) void k_iface(Geom g, const T* __restrict__ F, 
       o += pitch;
     }
   }
-  if constexpr (!EMIT) diag_publish(acc, part);
+  if constexpr (!EMIT) {
+    acc[1] = (double)ndeg;
+    block_publish<kIfacePart, 0>(acc, part);
+  }
 }
 
 // ------------------------------------------------------------------ counts -> exclusive offsets, block partials -> summary
 // ONE block of kIfaceScanThreads threads.  Thread t owns the entries [t * run, (t + 1) * run) of cnt (run = ceil(n / threads)):
 // it adds them up, the block scans the threads' totals (waves by __shfl_up, the 16 wave totals by thread 0 through LDS), and
-// the thread writes its entries' exclusive offsets back.  Then the partials: thread t folds t, t + 1024, ... in that order, a
-// tree over the threads, and threads 0 .. IFS_N - 1 store one slot of the summary each.  The launch boundary in front of it
-// is what makes the counts and partials of every block visible.
+// the thread writes its entries' exclusive offsets back.  Then the partials (fold_partials of kernels/reduce.h), and
+// threads 0 .. IFS_N - 1 store one slot of the summary each.  The launch boundary in front of it is what makes the counts
+// and partials of every block visible.
 __global__ __launch_bounds__(kIfaceScanThreads) void k_iface_scan(int* __restrict__ cnt, long long n, const double* __restrict__ part, int nblocks,
                                                                    double* __restrict__ summary, double istep) {
   constexpr int NT = kIfaceScanThreads, NW = NT / 64;
   __shared__ long long wsum[NW + 1];
-  __shared__ double red[NT][2];
+  __shared__ double red[NT][kIfacePart];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const long long run = (n + NT - 1) / NT;
   const long long e0 = (long long)t * run, e1 = e0 + run < n ? e0 + run : n;
@@ -205,17 +209,8 @@ __global__ __launch_bounds__(kIfaceScanThreads) void k_iface_scan(int* __restric
     off += k;
   }
   const double segments = (double)wsum[NW];
-  double a0 = 0.0, a1 = 0.0;
-  for (int b = t; b < nblocks; b += NT) {
-    a0 += part[(size_t)b * kDiagPart];
-    a1 += part[(size_t)b * kDiagPart + 1];
-  }
-  red[t][0] = a0; red[t][1] = a1;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) { red[t][0] += red[t + s][0]; red[t][1] += red[t + s][1]; }
-    __syncthreads();
-  }
+  const double zero[kIfacePart] = {0.0, 0.0};
+  fold_partials<NT, kIfacePart, 0>(part, nblocks, zero, red);
   if (t >= IFS_N) return;
   summary[t] = t == IFS_SEGMENTS ? segments : t == IFS_DEGENERATE ? red[0][1] : t == IFS_LENGTH ? red[0][0] : istep;
 }

@@ -203,20 +203,17 @@ __global__ void k_mg_coarse_stop(double* __restrict__ sc, int start, double redu
 // cell (i, j) is element i (ny + 2) + j, its ghost ring stays 0 as in the level's arrays in memory.  A thread owns the
 // interior cells t, t + 256, ... in every phase, so only s -- whose neighbours the stencil reads -- needs a barrier
 // between its writer and its readers; the reductions carry the others.  Sums in double for both field types: a thread's
-// cells in order, lanes -> wave by __shfl_down, waves -> block through LDS in wave order, every thread adding the four
+// cells in order, lanes -> wave by wave_fold of kernels/reduce.h, waves -> block through LDS in wave order, every thread adding the four
 // wave values itself -- so alpha, beta and the stop decision are formed by every thread from the same bits and the
 // control flow stays uniform.  A zero or non-finite denominator ends the solve instead of dividing (kernels/cg.h).
 // Another order of sums than the launches': other bits, same solver -- hence a knob.
 constexpr int kMgBlockCells = 1024;
 
 __device__ __forceinline__ void mg_block_reduce(double& sum, double& mx, double (*red)[2]) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    sum += __shfl_down(sum, d, 64);
-    mx = __builtin_fmax(mx, __shfl_down(mx, d, 64));
-  }
+  double w[2] = {sum, mx};
+  wave_fold<1, 1>(w);   // (kernels/reduce.h)
   __syncthreads();   // (everybody is through reading the previous reduction)
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sum; red[threadIdx.x >> 6][1] = mx; }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = w[0]; red[threadIdx.x >> 6][1] = w[1]; }
   __syncthreads();
   sum = red[0][0]; mx = red[0][1];
   for (int k = 1; k < 4; ++k) { sum += red[k][0]; mx = __builtin_fmax(mx, red[k][1]); }

@@ -30,7 +30,7 @@ inline int64_t iface_entries(const vof2d_ctx* h) {
 int iface_prepare(vof2d_ctx* h, int64_t rows) {
   if (!h->iface_cnt) {
     const size_t ints = ((size_t)iface_entries(h) + 2) & ~(size_t)1;   // (the doubles behind them stay 8-byte aligned)
-    const size_t dbl = (size_t)iface_blocks(h) * kDiagPart + IFS_N;
+    const size_t dbl = (size_t)iface_blocks(h) * kIfacePart + IFS_N;
     char* p = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&p), ints * sizeof(int) + dbl * sizeof(double)) != hipSuccess) {
       (void)hipGetLastError();
@@ -75,7 +75,7 @@ void iface_launch(vof2d_ctx* h, double eps, int64_t cap) {
            (long long)cap);
   if (!EMIT)
     launch_block(h, kOther, k_iface_scan, dim3(1), (unsigned)kIfaceScanThreads, 0, h->iface_cnt, (long long)iface_entries(h), (const double*)h->iface_part, (int)nb,
-           h->iface_part + (size_t)nb * kDiagPart, (double)h->istep);
+           h->iface_part + (size_t)nb * kIfacePart, (double)h->istep);
 }
 
 // The segments of the field F as vof_get_field would return it now: settle_ghosts first (the 3 x 3 neighbourhood of a cell
@@ -87,7 +87,7 @@ int iface_run(vof2d_ctx* h, double eps, double* rows, int64_t cap_rows, double* 
   settle_ghosts(h);
   DISPATCH_T(h, (iface_launch<double, false>(h, eps, 0)), (iface_launch<float, false>(h, eps, 0)));
   if ((rc = ensure_ok(h))) return rc;
-  HIPCHK(h, hipMemcpyAsync(summary, h->iface_part + (size_t)iface_blocks(h) * kDiagPart, IFS_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(summary, h->iface_part + (size_t)iface_blocks(h) * kIfacePart, IFS_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   int64_t n = (int64_t)summary[IFS_SEGMENTS];
   if (n > cap_rows) n = cap_rows;

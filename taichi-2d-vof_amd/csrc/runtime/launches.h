@@ -463,11 +463,7 @@ struct L {
              (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
              F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, h->tm_rhs_alt ? fKAPPA : fRHS), h->d_courant, R, tp, first, last, first2, last2);
   }
-  // ---- conjugate gradients (kernels/cg.h): work arrays h->cg_fld = r, s (two, ping-pong), q
-  // rows per wave chunk: the pointwise kernels and the residual like every streaming kernel (pick_rows); k_cg_apply forms
-  // the direction of one extra row above and below its chunk, so its chunks are twice as long
-  static int cg_rows(const vof2d_ctx* h, bool apply) { return (apply ? 2 : 1) * pick_rows(h, h->g.ntj); }
-  static unsigned cg_blocks(const vof2d_ctx* h, bool apply) { return blocks_for(h, h->g.ntj, cg_rows(h, apply)); }
+  // ---- conjugate gradients (kernels/cg.h)
   // sum of ap over the interior, in double, of the values the kernels form in T: ap depends on the position through
   // "first / last row or not" and "first / last column or not" only (2dvof.py:258-262), four values with their counts
   static double cg_sum_ap(const vof2d_ctx* h) { return sum_ap_of(C(const_cast<vof2d_ctx*>(h)), h->g.nx, h->g.ny); }
@@ -482,38 +478,49 @@ struct L {
     }
     return sum;
   }
-  // (sc: the scalars of the solve the partials belong to -- the handle's own, or those of a multigrid cycle's coarsest level)
-  static void cg_finish(vof2d_ctx* h, unsigned nblocks, int mode, double sum_ap = 0.0, int restart = 0, double* sc = nullptr) {
-    launch(h, kCgFinish, k_cg_finish, dim3(1), 0, (const double*)h->cg_part, (int)nblocks, sc ? sc : h->cg_sc, mode, sum_ap, restart);
+  // Where a solve runs: the handle's own grid (p, rhs, h->cg_fld, h->cg_sc) or the coarsest level of a multigrid cycle.
+  // w: r, two directions (ping-pong), q in the grid's layout; sc: the scalars of the solve.  Rows per wave chunk: the
+  // pointwise kernels and the residual like every streaming kernel (pick_rows; R1, n1 blocks); k_cg_apply forms the
+  // direction of one extra row above and below its chunk, so its chunks are twice as long (R2, n2 blocks).  Every
+  // launch leaves one partial per block in h->cg_part, which the k_cg_finish behind it folds.
+  struct CgGrid {
+    Geom g; Consts<T> c; T* e; const T* f; void* const* w; double* sc;
+    int R1, R2; unsigned n1, n2;
+  };
+  static CgGrid cg_grid(vof2d_ctx* h, const Geom& g, const Consts<T>& c, T* e, const T* f, void* const (&w)[4], double* sc) {
+    const int R1 = pick_rows(h, g.ntj), rows = g.ihi - g.ilo + 1;   // (the rows cg_tile cuts into chunks)
+    return {g, c, e, f, w, sc, R1, 2 * R1, blocks_rows(rows, g.ntj, R1), blocks_rows(rows, g.ntj, 2 * R1)};
   }
-  // c = sum(b) / sum(ap) into the device scalars
-  static void cg_drift(vof2d_ctx* h, double sum_ap) {
-    const unsigned nb = cg_blocks(h, false);
-    launch(h, kCgResidual, k_cg_sum<T, V>, dim3(nb), 0, h->g, (const T*)F_<T>(h, fRHS), cg_rows(h, false), h->cg_part);
-    cg_finish(h, nb, CG_FIN_SUMB, sum_ap);
+  static CgGrid cg_own(vof2d_ctx* h) { return cg_grid(h, h->g, C(h), F_<T>(h, fP), (const T*)F_<T>(h, fRHS), h->cg_fld, h->cg_sc); }
+  static void cg_finish(vof2d_ctx* h, const CgGrid& a, unsigned nblocks, int mode, double sum_ap = 0.0, int restart = 0) {
+    launch(h, kCgFinish, k_cg_finish, dim3(1), 0, (const double*)h->cg_part, (int)nblocks, a.sc, mode, sum_ap, restart);
   }
-  static void cg_residual(vof2d_ctx* h, int restart) {
-    const unsigned nb = cg_blocks(h, false);
-    launch(h, kCgResidual, k_cg_residual<T, V>, dim3(nb), 0, h->g, C(h), (const T*)F_<T>(h, fP), (const T*)F_<T>(h, fRHS),
-           reinterpret_cast<T*>(h->cg_fld[0]), cg_rows(h, false), (const double*)h->cg_sc, h->cg_part);
-    cg_finish(h, nb, CG_FIN_RESID, 0.0, restart);
+  // c = sum(f) / sum(ap) into the scalars
+  static void cg_drift(vof2d_ctx* h, const CgGrid& a, double sum_ap) {
+    launch(h, kCgResidual, k_cg_sum<T, V>, dim3(a.n1), 0, a.g, a.f, a.R1, h->cg_part);
+    cg_finish(h, a, a.n1, CG_FIN_SUMB, sum_ap);
   }
-  // one iteration: two field kernels, each followed by its one-block reduction
-  static void cg_iteration(vof2d_ctx* h) {
-    const Consts<T> cc = C(h);
-    T* const r = reinterpret_cast<T*>(h->cg_fld[0]);
-    T* const s_old = reinterpret_cast<T*>(h->cg_fld[h->cg_s]);
-    h->cg_s = 3 - h->cg_s;
-    T* const s_new = reinterpret_cast<T*>(h->cg_fld[h->cg_s]);
-    T* const q = reinterpret_cast<T*>(h->cg_fld[3]);
-    const unsigned na = cg_blocks(h, true), nu = cg_blocks(h, false);
-    launch(h, kCgApply, k_cg_apply<T, V>, dim3(na), 0, h->g, cc, (const T*)r, (const T*)s_old, s_new, q, cg_rows(h, true),
-           (const double*)h->cg_sc, h->cg_part);
-    cg_finish(h, na, CG_FIN_APPLY);
-    launch(h, kCgUpdate, k_cg_update<T, V>, dim3(nu), 0, h->g, cc, F_<T>(h, fP), (const T*)s_new, r, (const T*)q, cg_rows(h, false),
-           (const double*)h->cg_sc, h->cg_part);
-    cg_finish(h, nu, CG_FIN_UPDATE);
+  static void cg_residual(vof2d_ctx* h, const CgGrid& a, int restart) {
+    launch(h, kCgResidual, k_cg_residual<T, V>, dim3(a.n1), 0, a.g, a.c, (const T*)a.e, a.f, reinterpret_cast<T*>(a.w[0]), a.R1,
+           (const double*)a.sc, h->cg_part);
+    cg_finish(h, a, a.n1, CG_FIN_RESID, 0.0, restart);
   }
+  // one iteration: two field kernels, each followed by its one-block reduction; s: which of w[1..2] holds the current direction
+  static void cg_iteration(vof2d_ctx* h, const CgGrid& a, int& s) {
+    T* const r = reinterpret_cast<T*>(a.w[0]);
+    T* const s_old = reinterpret_cast<T*>(a.w[s]);
+    s = 3 - s;
+    T* const s_new = reinterpret_cast<T*>(a.w[s]);
+    T* const q = reinterpret_cast<T*>(a.w[3]);
+    launch(h, kCgApply, k_cg_apply<T, V>, dim3(a.n2), 0, a.g, a.c, (const T*)r, (const T*)s_old, s_new, q, a.R2, (const double*)a.sc, h->cg_part);
+    cg_finish(h, a, a.n2, CG_FIN_APPLY);
+    launch(h, kCgUpdate, k_cg_update<T, V>, dim3(a.n1), 0, a.g, a.c, a.e, (const T*)s_new, r, (const T*)q, a.R1, (const double*)a.sc, h->cg_part);
+    cg_finish(h, a, a.n1, CG_FIN_UPDATE);
+  }
+  // ... on the handle's grid (h->cg_s survives between the cg_iteration calls of one solve)
+  static void cg_drift(vof2d_ctx* h, double sum_ap) { cg_drift(h, cg_own(h), sum_ap); }
+  static void cg_residual(vof2d_ctx* h, int restart) { cg_residual(h, cg_own(h), restart); }
+  static void cg_iteration(vof2d_ctx* h) { cg_iteration(h, cg_own(h), h->cg_s); }
   // ---- multigrid (kernels/mg.h): every wrapper takes the level(s) it works on; level 0 is the handle's own grid
   static Consts<T> mg_consts(vof2d_ctx* h, const MgLevel& lv) {
     Consts<T> c = C(h);
@@ -541,26 +548,13 @@ struct L {
   static void mg_coarse_solve(vof2d_ctx* h, const MgLevel& lv, T* e, const T* f, void* const (&w)[4], double* sc, bool own_drift,
                               int cap, double reduction) {
     const Consts<T> cc = mg_consts(h, lv);
-    const int R1 = pick_rows(h, lv.g.ntj), R2 = 2 * R1;
-    const unsigned n1 = mg_blocks(h, lv.g, R1), n2 = mg_blocks(h, lv.g, R2);
-    T* const r = reinterpret_cast<T*>(w[0]);
-    T* const q = reinterpret_cast<T*>(w[3]);
-    if (own_drift) {
-      launch(h, kCgResidual, k_cg_sum<T, V>, dim3(n1), 0, lv.g, f, R1, h->cg_part);
-      cg_finish(h, n1, CG_FIN_SUMB, sum_ap_of(cc, lv.g.nx, lv.g.ny), 0, sc);
-    }
-    launch(h, kCgResidual, k_cg_residual<T, V>, dim3(n1), 0, lv.g, cc, (const T*)e, f, r, R1, (const double*)sc, h->cg_part);
-    cg_finish(h, n1, CG_FIN_RESID, 0.0, 1, sc);
+    const CgGrid a = cg_grid(h, lv.g, cc, e, f, w, sc);
+    if (own_drift) cg_drift(h, a, sum_ap_of(cc, lv.g.nx, lv.g.ny));
+    cg_residual(h, a, 1);
     launch_block(h, kOther, k_mg_coarse_stop, dim3(1), 64u, 0, sc, 1, reduction);
     int s = 1;
     for (int it = 0; it < cap; ++it) {
-      T* const s_old = reinterpret_cast<T*>(w[s]);
-      s = 3 - s;
-      T* const s_new = reinterpret_cast<T*>(w[s]);
-      launch(h, kCgApply, k_cg_apply<T, V>, dim3(n2), 0, lv.g, cc, (const T*)r, (const T*)s_old, s_new, q, R2, (const double*)sc, h->cg_part);
-      cg_finish(h, n2, CG_FIN_APPLY, 0.0, 0, sc);
-      launch(h, kCgUpdate, k_cg_update<T, V>, dim3(n1), 0, lv.g, cc, e, (const T*)s_new, r, (const T*)q, R1, (const double*)sc, h->cg_part);
-      cg_finish(h, n1, CG_FIN_UPDATE, 0.0, 0, sc);
+      cg_iteration(h, a, s);
       launch_block(h, kOther, k_mg_coarse_stop, dim3(1), 64u, 0, sc, 0, reduction);
     }
   }

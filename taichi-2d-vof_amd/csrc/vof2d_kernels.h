@@ -17,6 +17,7 @@
 //   jacobi_pair.h  k_jacobi_pair   (two k_jacobi_tb launches as one: pairs of waves, result and rhs rows through LDS)
 //   transport.h  k_fct_x, k_fct_y, k_transport   (update_uv + solve_VOF_rudman + post_process_f)
 //   fused_tm.h   k_tm   (k_transport of one step + k_momentum of the next, rows handed over through LDS)
+//   reduce.h     block_publish, fold_partials   (the fixed-order reduction of the four families below; no kernel of its own)
 //   cg.h         k_cg_apply, k_cg_update, k_cg_residual   (extension: conjugate gradients on the pressure equation)
 //   mg.h         k_mg_smooth, k_mg_restrict, k_mg_prolong, k_mg_coarse_block, k_mg_step_record  (extension: geometric multigrid on the same equation)
 //   diag.h       k_diag, k_diag_finish   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
@@ -31,6 +32,7 @@
 #include "kernels/jacobi_pair.h"
 #include "kernels/transport.h"
 #include "kernels/fused_tm.h"
+#include "kernels/reduce.h"
 #include "kernels/cg.h"
 #include "kernels/mg.h"
 #include "kernels/diag.h"

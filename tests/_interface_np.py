@@ -1,5 +1,5 @@
 """NumPy restatement of vof_interface for the tests, term for term in the expression order stated at the head of
-taichi-2d-vof_amd/csrc/kernels/interface.h, the order of the LENGTH sum included.  It is the yardstick for bits.
+taichi-2d-vof_amd/csrc/kernels/interface.h; the order of the LENGTH sum is that of tests/_reduce_np.py.  It is the yardstick for bits.
 
 `restate(F, eps, dx, dy, ...)` takes the array F as vof_get_field returns it (rows indexed [i - row0], ghost columns
 included: ny + 2 columns) and returns (rows, summary, unit): the (n, 8) float64 rows in ascending (i, j) order, the summary
@@ -9,7 +9,8 @@ the same branch.
 """
 import numpy as np
 
-TILE = 128            # columns of a wave tile: 64 lanes x V = 2 (VecWidth of csrc/vof2d_device.h)
+from _reduce_np import TILE, fixed_order
+
 SCAN_THREADS = 1024   # kIfaceScanThreads
 
 
@@ -25,42 +26,15 @@ def chunk_rows(nx, ny, row_lo=0, row_hi=None, rmin=4, rmax=32):
     return max(P, rmin)
 
 
+def diag_chunk_rows(nx, ny, row_lo=0, row_hi=None):
+    """diag_chunk of runtime/diag_reduce.h: the same rule with 2 and 16."""
+    return chunk_rows(nx, ny, row_lo, row_hi, rmin=2, rmax=16)
+
+
 def length_sum(L, R):
     """The LENGTH of the kernels from the per-cell lengths L (rows lo .. hi, columns 1 .. ny; 0 where there is no segment):
-    lane, wave, block, k_iface_scan -- the order stated in kernels/interface.h."""
-    nrows, ny = L.shape
-    ntj = (ny + TILE - 1) // TILE
-    Lp = np.zeros((nrows, ntj * TILE))
-    Lp[:, :ny] = L
-    Lp = Lp.reshape(nrows, ntj, 64, 2)
-    nch = (nrows + R - 1) // R
-    acc = np.zeros((nch, ntj, 64))
-    for ch in range(nch):                      # a lane adds its cells row by row, column by column
-        for r in range(ch * R, min(ch * R + R, nrows)):
-            acc[ch] = acc[ch] + Lp[r, :, :, 0]
-            acc[ch] = acc[ch] + Lp[r, :, :, 1]
-    w = acc.reshape(nch * ntj, 64)             # wave = chunk * ntj + tile
-    s = 32
-    while s > 0:                               # lanes -> wave by __shfl_down
-        new = w.copy()
-        new[:, :64 - s] = w[:, :64 - s] + w[:, s:]
-        w = new
-        s >>= 1
-    waves = w[:, 0]
-    nb = (len(waves) + 3) // 4
-    wv = np.zeros(nb * 4)
-    wv[:len(waves)] = waves
-    wv = wv.reshape(nb, 4)
-    part = ((wv[:, 0] + wv[:, 1]) + wv[:, 2]) + wv[:, 3]   # waves -> block in wave order
-    red = np.zeros(SCAN_THREADS)
-    for start in range(0, nb, SCAN_THREADS):   # thread t takes t, t + 1024, ...
-        blk = part[start:start + SCAN_THREADS]
-        red[:len(blk)] = red[:len(blk)] + blk
-    s = SCAN_THREADS // 2
-    while s > 0:                               # ... and a tree over the threads
-        red[:s] = red[:s] + red[s:2 * s]
-        s >>= 1
-    return float(red[0])
+    the order of kernels/reduce.h with the 1024 threads of k_iface_scan."""
+    return fixed_order(L, R, SCAN_THREADS, "add")
 
 
 def restate(F, eps, dx, dy, lo=1, hi=None, row0=0, R=None):

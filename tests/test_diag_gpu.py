@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 import _diag_np as dnp
+import _interface_np as inp
+import _reduce_np as rnp
 from test_step_mg_gpu import FIELDS, assert_same_state
 from util import engine
 from vof2d import _abi, diag, halo_rows
@@ -30,10 +32,12 @@ def restated(e):
                        e.get_param("rho_l"), lo=lo, hi=hi, row0=e.row_lo)
 
 
-def hold_to_restatement(e, ctx):
+def hold_to_restatement(e, ctx, bits=False):
+    """bits: the sums also equal, bit for bit, the restated order of the reduction with the handle's chunk length"""
     raw = e.diagnostics()
     terms, ext, cells = restated(e)
-    dnp.check(raw, terms, ext, cells, istep=e.istep, ctx=ctx, say=print)
+    R = inp.diag_chunk_rows(e.nx, e.ny, e.row_lo, e.row_hi) if bits else None
+    dnp.check(raw, terms, ext, cells, istep=e.istep, ctx=ctx, say=print, R=R)
     return raw
 
 
@@ -47,7 +51,7 @@ def test_200_f32_after_0_1_and_50_steps(hip_api, ic):
     e = engine(hip_api, 200, 200, "f32", "f32", ic=ic)
     for upto in (0, 1, 50):
         e.step(upto - e.istep)
-        raw = hold_to_restatement(e, "200x200 f32 ic %d step %d" % (ic, upto))
+        raw = hold_to_restatement(e, "200x200 f32 ic %d step %d" % (ic, upto), bits=True)
         assert raw["CELLS"] == 200 * 200 and raw["SUM_F"] > 0
     assert raw["MAX_U"] > 0 and raw["MAX_DIV"] > 0 and raw["SUM_KE"] > 0
 
@@ -59,7 +63,19 @@ def test_small_and_rectangular_f64(hip_api, nx, ny, ic, kw):
         assert e.get_param("dxi") != e.get_param("dyi")
     for upto in (0, 1, 20):
         e.step(upto - e.istep)
-        hold_to_restatement(e, "%dx%d f64 ic %d step %d" % (nx, ny, ic, upto))
+        hold_to_restatement(e, "%dx%d f64 ic %d step %d" % (nx, ny, ic, upto), bits=True)
+
+
+def test_more_partials_than_folding_threads_f64(hip_api):
+    """1100 x 130: the rule gives 2-row chunks, 550 chunks x 2 tiles = 1100 waves = 275 blocks, so threads 0 .. 18 of
+    k_diag_finish fold two partials each; the second tile is ragged (2 of 128 columns).  Sums and extrema with ==."""
+    nx, ny = 1100, 130
+    R = inp.diag_chunk_rows(nx, ny)
+    assert R == 2 and rnp.blocks(nx, ny, R) == 275 > 256
+    e = engine(hip_api, nx, ny, "f64", "f32", ic=3)
+    for upto in (0, 1):
+        e.step(upto - e.istep)
+        hold_to_restatement(e, "%dx%d f64 ic 3 step %d" % (nx, ny, upto), bits=True)
 
 
 def test_1024_f64_after_20_steps(hip_api):

@@ -138,6 +138,64 @@ def test_length_sum_is_a_sum():
     assert inp.chunk_rows(4096, 4096) == 32 and inp.chunk_rows(200, 200) == 4 and inp.chunk_rows(2048, 2048) == 8
 
 
+def length_sum_as_first_stated(L, R):
+    """The body of _interface_np.length_sum before tests/_reduce_np.py took it over: kept as the yardstick of fixed_order."""
+    TILE, SCAN_THREADS = 128, 1024
+    nrows, ny = L.shape
+    ntj = (ny + TILE - 1) // TILE
+    Lp = np.zeros((nrows, ntj * TILE))
+    Lp[:, :ny] = L
+    Lp = Lp.reshape(nrows, ntj, 64, 2)
+    nch = (nrows + R - 1) // R
+    acc = np.zeros((nch, ntj, 64))
+    for ch in range(nch):                      # a lane adds its cells row by row, column by column
+        for r in range(ch * R, min(ch * R + R, nrows)):
+            acc[ch] = acc[ch] + Lp[r, :, :, 0]
+            acc[ch] = acc[ch] + Lp[r, :, :, 1]
+    w = acc.reshape(nch * ntj, 64)             # wave = chunk * ntj + tile
+    s = 32
+    while s > 0:                               # lanes -> wave by __shfl_down
+        new = w.copy()
+        new[:, :64 - s] = w[:, :64 - s] + w[:, s:]
+        w = new
+        s >>= 1
+    waves = w[:, 0]
+    nb = (len(waves) + 3) // 4
+    wv = np.zeros(nb * 4)
+    wv[:len(waves)] = waves
+    wv = wv.reshape(nb, 4)
+    part = ((wv[:, 0] + wv[:, 1]) + wv[:, 2]) + wv[:, 3]   # waves -> block in wave order
+    red = np.zeros(SCAN_THREADS)
+    for start in range(0, nb, SCAN_THREADS):   # thread t takes t, t + 1024, ...
+        blk = part[start:start + SCAN_THREADS]
+        red[:len(blk)] = red[:len(blk)] + blk
+    s = SCAN_THREADS // 2
+    while s > 0:                               # ... and a tree over the threads
+        red[:s] = red[:s] + red[s:2 * s]
+        s >>= 1
+    return float(red[0])
+
+
+def test_fixed_order_has_the_bits_of_the_first_length_sum():
+    """tests/_reduce_np.fixed_order on random per-cell terms: narrower than a tile, one full tile, two and three tiles with a
+    ragged last one; one-row chunks, the rule's 4 and a length that divides nothing.  nrows: fewer rows than a chunk, a ragged
+    last chunk, and with 1500 rows of three tiles in one-row chunks 1125 blocks -- more than the 1024 folding threads."""
+    import struct
+    from _reduce_np import blocks, fixed_order
+    rng = np.random.default_rng(11)
+    assert blocks(1500, 300, 1) == 1125
+    for ny in (17, 128, 130, 300):
+        for R in (1, 4, 7):
+            for nrows in (3, 33, 1500 if ny == 300 else 210):
+                L = rng.random((nrows, ny)) * (rng.random((nrows, ny)) < 0.3)
+                got, want = fixed_order(L, R, 1024, "add"), length_sum_as_first_stated(L, R)
+                assert struct.pack("d", got) == struct.pack("d", want) and got == inp.length_sum(L, R), (nrows, ny, R, got, want)
+    # the other fold: a maximum does not depend on the order, so fixed_order must return np.max for any geometry and width
+    M = rng.standard_normal((70, 300))
+    assert fixed_order(M, 4, 256, "fmax") == M.max() and fixed_order(-np.abs(M), 2, 256, "fmax", init=0.0) == 0.0
+    assert fixed_order(np.zeros((0, 40)), 4, 256, "add") == 0.0 and fixed_order(np.zeros((0, 40)), 4, 256, "fmax") == -math.inf
+
+
 def test_polylines_chain_the_flat_interface_and_the_circle():
     from vof2d import interface
     nx, ny = 40, 24

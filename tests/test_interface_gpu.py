@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _interface_np as inp
+import _reduce_np as rnp
 from test_diag_gpu import TM_GRID
 from test_step_mg_gpu import FIELDS, assert_same_state
 from util import engine
@@ -82,6 +83,18 @@ def test_small_rectangular_and_three_tiles_f64(hip_api, nx, ny, ic, kw):
         assert len(tiles) >= 2
         if ic == 1:
             assert any(len(set(((rows[rows[:, 0] == i, 1] - 1) // inp.TILE).astype(int))) >= 2 for i in set(rows[:, 0]))
+
+
+def test_more_partials_than_scan_threads_f64(hip_api):
+    """3277 x 513, the drop over the pool at step 0: five column tiles (the last one a single column) and 4-row chunks, the
+    fewest rows for which the count pass has more blocks than k_iface_scan has threads -- 820 chunks x 5 tiles = 4100 waves =
+    1025 blocks, one row less gives 1024 -- so thread 0 folds two partials.  Everything with ==."""
+    nx, ny = 3277, 513
+    R = inp.chunk_rows(nx, ny)
+    assert R == 4 and rnp.blocks(nx, ny, R) == 1025 > inp.SCAN_THREADS == 1024 == rnp.blocks(nx - 1, ny, inp.chunk_rows(nx - 1, ny))
+    e = engine(hip_api, nx, ny, "f64", "f32", ic=3)
+    rows, summ = hold_to_restatement(e, "%dx%d f64 ic 3 step 0" % (nx, ny))
+    assert summ["SEGMENTS"] > 0 and summ["LENGTH"] > 0
 
 
 def test_behind_a_k_tm_batch(hip_api):
