@@ -19,6 +19,10 @@
 // alpha / beta ON THE DEVICE -- the host reads nothing between iterations.  No floating-point atomics.  A zero or
 // non-finite denominator sets the stop word instead of dividing; every later launch of the batch then returns at once
 // and the host's check decides.
+//
+// tests/_solver_bits_np.py restates every kernel here operation for operation (and the scalar logic of k_cg_finish mode by
+// mode); tests/test_solver_bits_gpu.py holds the kernels to it bit for bit.  tests/_cg_np.py restates the METHOD, from the
+// textbook: the independent judge of what a solve converges to, not of these bits.
 #pragma once
 #include "reduce.h"
 

@@ -12,7 +12,8 @@
 // right-hand side f in the fields' pitched layout (its own Geom) with zeros outside the interior; on the finest level e
 // is p itself and f is b - c ap, formed on the fly from rhs and the device scalar CG_C (sc != nullptr).
 //
-// Expression order (tests/_mg_np.py restates it):
+// Expression order (tests/_solver_bits_np.py restates it operation for operation and tests/test_solver_bits_gpu.py holds the
+// kernels to it bit for bit; tests/_mg_np.py restates the METHOD from the textbook, not this order):
 //   smoothing      e_new = e + w * (((f - c ap) - L e) / ap),  w = 0.8, L e as the four differences above in that order
 //   restriction    f_coarse = 0.25 * ((r[2I-1][2J-1] + r[2I-1][2J]) + (r[2I][2J-1] + r[2I][2J])),  r = (f - c ap) - L e
 //   prolongation   along j first:  lo = 0.75 * x[J] + 0.25 * x[J-1],  hi = 0.75 * x[J] + 0.25 * x[J+1]   (fine columns 2J-1, 2J)
