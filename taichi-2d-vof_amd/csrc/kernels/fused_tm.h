@@ -31,8 +31,6 @@
 
 namespace vof {
 
-struct TmGeom { static constexpr int HF = 8; };   // invalid columns per tile side of the fused march: 4 (transport) + 3 (momentum), rounded up to even
-
 template <typename T, int V>
 struct TmRing {
   static constexpr int W = 64 * V, NR = 8;
@@ -68,7 +66,7 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
                                                    const T* __restrict__ p, T* __restrict__ Uo, T* __restrict__ Vo,
                                                    unsigned long long* __restrict__ courant, int c0, int lane, int ma, int mb,
                                                    WaveTimer& wt_) {
-  constexpr int W = 64 * V, HF = TmGeom::HF;
+  constexpr int W = TmGeom<V>::W, HF = TmGeom<V>::H;
   // the transport wave is the one the momentum wave waits for: priority 1 (4096^2 fp64: 314 -> 299 us y first, 327 -> 305 x first;
   // the momentum wave instead: 314 / 333).  ABL_PRIO0 of the diagnostic build = without it.
   if constexpr ((ABL & ABL_PRIO0) == 0) __builtin_amdgcn_s_setprio(1);
@@ -192,7 +190,7 @@ template <typename T, int V, bool BS, bool IN, int ABL>
 __device__ __forceinline__ void tm_momentum_march(const Geom& g, const Consts<T>& c, TmRing<T, V>& ring, T* __restrict__ us_out,
                                                   T* __restrict__ vs_out, T* __restrict__ rhs, int c0, int lane, int ma, int mb,
                                                   WaveTimer& wt_) {
-  constexpr int W = 64 * V, HF = TmGeom::HF;
+  constexpr int W = TmGeom<V>::W, HF = TmGeom<V>::H;
   if constexpr ((ABL & ABL_PRIO1) != 0) __builtin_amdgcn_s_setprio(1);
   const int t_lo = ma - 5, t_hi = mb + 8;   // lockstep steps of the pair
   if constexpr ((ABL & ABL_IDLE1) != 0) {
@@ -282,7 +280,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void k
                                             unsigned long long* __restrict__ courant, int R, TbPlan tp, int first, int last,
                                             int first2 = 1, int last2 = 0) {
   // rows [first, last] and -- the two edge bands of a strip in one launch -- [first2, last2] (last2 < first2: none), each cut in chunks of R
-  constexpr int W = 64 * V, HF = TmGeom::HF, STRIDE = W - 2 * HF;
+  constexpr int W = TmGeom<V>::W, HF = TmGeom<V>::H, STRIDE = TmGeom<V>::STRIDE;
   static_assert(HF >= 4 + 3 && HF % V == 0, "momentum's inputs must lie inside the transport march's valid columns");
   static_assert(sizeof(TbPlanShared) <= sizeof(TmRing<double, 2>) / 2, "the planner block borrows the ring's LDS");
   __shared__ __attribute__((aligned(16))) char smem[sizeof(TmRing<T, V>) > sizeof(TbPlanShared) ? sizeof(TmRing<T, V>) : sizeof(TbPlanShared)];

@@ -145,11 +145,8 @@ __global__ __launch_bounds__(256) void k_jacobi_tb(Geom g, Consts<T> c, const T*
   // (their reciprocal yI is 0, so div_by_const returns 0), whose product is the same exact zero.
   static_assert(TS >= 2 && TS <= 5, "rhs ring holds 6 rows");
   WaveTimer wt_(WT_JACOBI_TB);
-  constexpr int W = 64 * V;
-  // invalid columns per tile side after TS sweeps: TS-1 from the cross-lane exchange of sweeps
-  // 2..TS, plus 1 when the first sweep also takes its j-neighbours from adjacent lanes (SQ)
-  constexpr int H = ((TS - 1 + (SQ ? 1 : 0) + V - 1) / V) * V;
-  constexpr int STRIDE = W - 2 * H;
+  typedef JacobiTbGeom<V, TS, SQ> TG;   // (H: the invalid columns per tile side after TS sweeps)
+  constexpr int W = TG::W, H = TG::H, STRIDE = TG::STRIDE;
   int lblock = xcd_contiguous_block(blockIdx.x, gridDim.x);
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int wave = lblock * (blockDim.x >> 6) + wib;

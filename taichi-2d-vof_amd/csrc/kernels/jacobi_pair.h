@@ -51,8 +51,7 @@ __device__ __forceinline__ void jacobi_pair_march(const Geom& g, const Consts<T>
   // LDS): it runs at priority 1 -- 4096^2 fp64: 146 -> 135 us per launch inside the front, 149 -> 141 behind it
   // (tools/probes/pair_bound.py; the other way round: 142 / 148).  ABL_PRIO0 of the diagnostic build = without it.
   if constexpr ((ROLE == 0 && !(ABL & ABL_PRIO0)) || (ROLE == 1 && (ABL & ABL_PRIO1))) __builtin_amdgcn_s_setprio(1);
-  constexpr int W = 64 * V;
-  constexpr int H = ((2 * TS + V - 1) / V) * V;   // TS invalid columns per side and march (TS - 1 cross-lane sweeps + the first sweep's DPP neighbours)
+  constexpr int W = JacobiPairGeom<V, TS>::W, H = JacobiPairGeom<V, TS>::H;
   const int j0 = c0 + lane * V;
   const int nx = g.nx, ny = g.ny;
   const int jlo = c0 + H > 1 ? c0 + H : 1;
@@ -265,9 +264,7 @@ template <typename T, int V, int TS, bool BS, int ABL = 0>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void k_jacobi_pair(Geom g, Consts<T> c, const T* __restrict__ p,
                                                      const T* __restrict__ rhs, T* __restrict__ pn, int R, int ntt,
                                                      TbPlan tp, int first, int last) {
-  constexpr int W = 64 * V;
-  constexpr int H = ((2 * TS + V - 1) / V) * V;   // TS invalid columns per side and march (TS - 1 cross-lane sweeps + the first sweep's DPP neighbours)
-  constexpr int STRIDE = W - 2 * H;
+  constexpr int H = JacobiPairGeom<V, TS>::H, STRIDE = JacobiPairGeom<V, TS>::STRIDE;
   __shared__ __attribute__((aligned(16))) JpRing<T, V> lds;
   WaveTimer wt_(WT_JACOBI_PAIR);
   if (last < first) { first = g.ilo; last = g.ihi; }

@@ -309,11 +309,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
   // virt (full-domain fused steps, DESIGN.md "virtual ghosts"): the previous step did not run
   // set_BC; the ghost cells this kernel reads -- F's ghost rows and columns, v's ghost rows, u's
   // ghost columns -- are formed from the interior cells set_BC would have copied (:164-189).
-  constexpr int W = 64 * V;
-  constexpr int H = TileHalo::momentum;
+  typedef MomentumGeom<V> TG;
+  constexpr int W = TG::W, H = TG::H, STRIDE = TG::STRIDE;
   static_assert(H >= 2 && H % V == 0, "two columns of each side are invalid after the cross-lane stages");
   WaveTimer wt_(WT_MOMENTUM);
-  constexpr int STRIDE = W - 2 * H;
   const int wave = ((int)blockIdx.x - plan_blocks) * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int tj = wave % ntt, ch = wave / ntt;

@@ -502,7 +502,7 @@ __global__ __launch_bounds__(256) void k_fct_y(Geom g, Consts<T> c, const T* __r
                                                 const T* __restrict__ us, const T* __restrict__ vs,
                                                 const T* __restrict__ p, T* __restrict__ Uo, T* __restrict__ Vo,
                                                 unsigned long long* __restrict__ courant, int rfirst, int rlast) {
-  constexpr int W = 64 * V, HT = TileHalo::transport, STRIDE = W - 2 * HT;
+  constexpr int W = TransportGeom<V>::W, HT = TransportGeom<V>::H, STRIDE = TransportGeom<V>::STRIDE;
   static_assert(HT >= 4 && HT % V == 0, "the y sweep's +-3 dependency is resolved across lanes");
   WaveTimer wt_(WT_FCT_Y);
   const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // SGPR: rows are wave-uniform
@@ -637,7 +637,7 @@ __global__ __launch_bounds__(256) void k_transport(Geom g, Consts<T> c, const T*
   // rr: all computable rows of a full domain; on a strip the owned rows -- as one range, or the two
   // edge bands (what the neighbours wait for) first and then the rest, in one launch or in two.
   // The sweeps' domain stays [ilo, ihi].
-  constexpr int W = 64 * V, HT = TileHalo::transport, STRIDE = W - 2 * HT;
+  constexpr int W = TransportGeom<V>::W, HT = TransportGeom<V>::H, STRIDE = TransportGeom<V>::STRIDE;
   static_assert(HT >= 4 && HT % V == 0, "the y sweep's +-3 dependency is resolved across lanes");
   WaveTimer wt_(WT_TRANSPORT);
   const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

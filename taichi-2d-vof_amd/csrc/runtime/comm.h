@@ -139,6 +139,23 @@ int comm_join(vof2d_ctx* h) {
 }
 
 
+// The end of a step whose p is final, by the fused transport (update_uv + both sweeps in one pass), edge bands first:
+// p, u, v and F (from the twin buffer) leave as soon as the bands exist and travel under the transport of the
+// remaining rows.  One group for all four fields: p has been final since the pressure solve, but a separate fork for
+// it costs more (a 6-12 us gap on the compute queue) than its 1/4 of the bytes.
+template <typename T>
+int enqueue_transport_exchange(vof2d_ctx* h) {
+  int rc;
+  const bool y_first = (h->istep % 2 == 0);
+  transport_part<T>(h, y_first, kEdgeBands);
+  if ((rc = comm_post(h, VOF_XCHG_P | VOF_XCHG_F | VOF_XCHG_U | VOF_XCHG_V, /*f_in_twin=*/true, 1))) return rc;
+  transport_part<T>(h, y_first, kRest);
+  swap_F(h);
+  if ((rc = comm_join(h))) return rc;
+  if (!h->virtual_ghosts) L<T>::template set_bc<BC_ALL>(h);
+  return VOF_OK;
+}
+
 // One step with its exchanges on (compute stream, communication stream).  mode 0: one exchange of
 // all four fields after the step; 1: each field leaves as soon as it is final (p after phase 0,
 // u, v after phase 1, F after phase 2); 3: p, u, v together after phase 1, F after phase 2 (one fork
@@ -155,21 +172,7 @@ int enqueue_step_exchange(vof2d_ctx* h, int mode) {
   const bool lean = true;
   const bool virt = h->virtual_ghosts != 0;
   enqueue_phase<T>(h, 0, h->istep, false, lean, virt, (int)(h->istep & 1));
-  if (mode == 4) {
-    // fused transport (update_uv + both sweeps in one pass), edge bands first: p, u, v and F (from
-    // the twin buffer) leave as soon as the bands exist and travel under the transport of the
-    // remaining rows
-    const bool y_first = (h->istep % 2 == 0);
-    transport_part<T>(h, y_first, kEdgeBands);
-    // one group for all four fields: p has been final since the pressure solve, but a separate
-    // fork for it costs more (a 6-12 us gap on the compute queue) than its 1/4 of the bytes
-    if ((rc = comm_post(h, VOF_XCHG_P | VOF_XCHG_F | VOF_XCHG_U | VOF_XCHG_V, /*f_in_twin=*/true, 1))) return rc;
-    transport_part<T>(h, y_first, kRest);
-    swap_F(h);
-    if ((rc = comm_join(h))) return rc;
-    if (!virt) L<T>::template set_bc<BC_ALL>(h);
-    return VOF_OK;
-  }
+  if (mode == 4) return enqueue_transport_exchange<T>(h);
   if (mode == 1 && (rc = comm_post(h, VOF_XCHG_P, false, 0))) return rc;   // p is final
   enqueue_phase<T>(h, 1, h->istep, false, lean);
   if (mode && (rc = comm_post(h, mode == 3 ? (VOF_XCHG_P | VOF_XCHG_U | VOF_XCHG_V) : (VOF_XCHG_U | VOF_XCHG_V), false, 1))) return rc;  // u, v are final
@@ -181,18 +184,6 @@ int enqueue_step_exchange(vof2d_ctx* h, int mode) {
 }
 
 // ---- overlap mode 5: the strips run the pair kernels (include/vof2d.h, vof_step_exchange) ----
-// owned rows of the handle inside the computable rows, and the two W-row bands at its interior edges
-struct OwnedRows { int lo, hi, in_lo, in_hi; bool band_lo, band_hi; };
-inline OwnedRows owned_rows(const vof2d_ctx* h) {
-  const int W = VOF_HALO_ROWS(h->d.jacobi_iters);
-  OwnedRows o;
-  o.lo = h->d.own_lo > h->g.ilo ? h->d.own_lo : h->g.ilo;
-  o.hi = h->d.own_hi < h->g.ihi ? h->d.own_hi : h->g.ihi;
-  o.band_lo = !h->g.wall_lo; o.band_hi = !h->g.wall_hi;
-  o.in_lo = o.band_lo ? o.lo + W : o.lo;
-  o.in_hi = o.band_hi ? o.hi - W : o.hi;
-  return o;
-}
 // the first step's k_momentum: u*, v*, rhs of the owned rows (their halo rows arrive by exchange: mode 5's state)
 template <typename T>
 void tm5_head(vof2d_ctx* h) {
@@ -204,9 +195,9 @@ void tm5_head(vof2d_ctx* h) {
     (void)hipMemsetAsync(h->fld[fMY], 0, h->field_elems * h->esz, h->stream);
     h->alt_dirty = false;
   }
-  const OwnedRows o = owned_rows(h);
+  const RowRange o = strip_rows(h).owned;
   h->jpair_active = L<T>::jacobi_pair_ok(h);    // (the planner block plans the geometry of the kernel that will run)
-  L<T>::momentum(h, true, (int)((h->istep + 1) & 1), o.lo, o.hi);
+  L<T>::momentum(h, true, (int)((h->istep + 1) & 1), o.first, o.last);
   h->jpair_active = false;
 }
 // the ten sweeps of a middle step on all stored rows
@@ -225,28 +216,17 @@ void tm5_jacobi(vof2d_ctx* h, int par) {
     jacobi_n<T>(h, h->d.jacobi_iters, false, -1);
   }
 }
-// k_tm on the owned rows: part 0 = all, 1 = the edge bands (short chunks), 2 = the rest (carries the planner block)
+// k_tm on one part of the owned rows (runtime/rows.h); the launch of the body carries the planner block
 template <typename T>
 void tm5_tm(vof2d_ctx* h, int64_t istep, int part) {
-  const OwnedRows o = owned_rows(h);
+  const PartRows pr = part_rows(strip_rows(h), part);
   const bool y_first = (istep % 2 == 0);
-  const int par_next = (int)((istep + 1) & 1);
   h->jpair_active = L<T>::jacobi_pair_ok(h);
-  auto run = [&](int a, int b, int par, int rows_forced, int a2 = 1, int b2 = 0) {
-    if (b < a) { a = a2; b = b2; a2 = 1; b2 = 0; }
-    if (b < a) return;
-    if (y_first) L<T>::template tm<true, false>(h, par, a, b, rows_forced, a2, b2); else L<T>::template tm<false, false>(h, par, a, b, rows_forced, a2, b2);
-  };
-  const bool split = o.in_lo <= o.in_hi && (o.band_lo || o.band_hi);
-  if (part == 0 || !split) {
-    if (part == 0 || (part == 1 && (o.band_lo || o.band_hi)) || (part == 2 && !(o.band_lo || o.band_hi))) run(o.lo, o.hi, par_next, 0);   // (one launch for the step: it carries the planner block)
-  } else if (part == 1) {
-    // both bands in ONE launch, in short chunks (a pair's march is its rows + 14 steps whatever its rows: the bands are
-    // what the send / recv group waits for -- 8192-wide interior strip of 8: two launches of 18-row chunks 56 + 69 us)
-    run(o.band_lo ? o.lo : 1, o.band_lo ? o.in_lo - 1 : 0, -1, kTmBandRows, o.band_hi ? o.in_hi + 1 : 1, o.band_hi ? o.hi : 0);
-  } else {
-    run(o.in_lo, o.in_hi, par_next, 0);
-  }
+  if (!pr.body.empty()) L<T>::tm(h, y_first, false, (int)((istep + 1) & 1), pr.body.first, pr.body.last);
+  // both bands in ONE launch, in short chunks (a pair's march is its rows + 14 steps whatever its rows: the bands are
+  // what the send / recv group waits for -- 8192-wide interior strip of 8: two launches of 18-row chunks 56 + 69 us)
+  const RowRange b1 = pr.band_lo.empty() ? pr.band_hi : pr.band_lo, b2 = pr.band_lo.empty() ? kNoRows : pr.band_hi;
+  if (!b1.empty()) L<T>::tm(h, y_first, false, -1, b1.first, b1.last, kTmBandRows, b2.first, b2.last);
   h->jpair_active = false;
 }
 // one middle step with its exchange: the edge bands on the communication stream in front of the send / recv group,
@@ -271,16 +251,8 @@ int enqueue_mid_step5(vof2d_ctx* h) {
 // the last step of a call: mode 4's step without its k_momentum (u, v reach memory here)
 template <typename T>
 int enqueue_tail_step5(vof2d_ctx* h) {
-  int rc;
   jacobi_n<T>(h, h->d.jacobi_iters, false, -1);     // (uniform chunks: the plan in memory is of the pairs' geometry)
-  const bool y_first = (h->istep % 2 == 0);
-  transport_part<T>(h, y_first, kEdgeBands);
-  if ((rc = comm_post(h, VOF_XCHG_P | VOF_XCHG_F | VOF_XCHG_U | VOF_XCHG_V, /*f_in_twin=*/true, 1))) return rc;
-  transport_part<T>(h, y_first, kRest);
-  swap_F(h);
-  if ((rc = comm_join(h))) return rc;
-  if (!h->virtual_ghosts) L<T>::template set_bc<BC_ALL>(h);
-  return VOF_OK;
+  return enqueue_transport_exchange<T>(h);
 }
 
 // ---- the steps of a strip with their exchanges (vof_step_exchange)

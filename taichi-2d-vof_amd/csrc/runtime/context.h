@@ -279,7 +279,6 @@ struct vof2d_ctx {
   // against round 4's rows)
   int pair_slow10 = 32;
   int tb_slow10 = 20;
-  int pair_vec4 = 0;         // knob "pair_vec4": fp32 pair kernels with four columns per lane (256-column tiles)
   bool jpair_active = false; // the launches being enqueued are k_jacobi_pair's (tb_plan describes their geometry)
   bool jpair_captured = false;   // the k_tm batch graphs the handle holds contain k_jacobi_pair launches
   int64_t pair_launches = 0; // k_jacobi_pair launches replayed (counter "pair_launches")
@@ -306,7 +305,7 @@ struct vof2d_ctx {
   int tkid[kMaxTimed];        // kernel id of each recorded launch
   double prof_sum_ms[24] = {};   // (>= NKERNELS of launches.h)
   long prof_cnt[24] = {};
-  std::map<const void*, long> occ_cache;  // resident waves per kernel function (resident_waves)
+  std::map<const void*, long> occ_cache;  // what the chip holds of a kernel function at once (resident, runtime/launches.h)
   // strip halo exchange over RCCL (vof_comm_init): own communicator, stream and events
   void* comm = nullptr;          // ncclComm_t
   hipStream_t cstream = nullptr; // RCCL's kernels run here, next to the compute stream

@@ -22,9 +22,8 @@ void dbg_pair(vof2d_ctx* h, int plan) {
 template <bool YFIRST, int ABL>
 void dbg_tm(vof2d_ctx* h) {
   typedef double T; constexpr int V = VecWidth<T>::V;
-  constexpr int ST = 64 * V - 2 * TmGeom::HF;
-  const int ntf = (h->g.ny + ST - 1) / ST, first = h->g.ilo, last = h->g.ihi;
-  const int R = L<T>::tm_chunk_rows(h, last - first + 1, ntf, resident_blocks(h, k_tm<T, V, YFIRST, false, true, ABL>, 128));
+  const int ntf = TmGeom<V>::tiles(h->g.ny), first = h->g.ilo, last = h->g.ihi;
+  const int R = L<T>::tm_chunk_rows(h, last - first + 1, ntf, resident(h, k_tm<T, V, YFIRST, false, true, ABL>, 128));
   const TbPlan tp{nullptr, nullptr, 0, 0, 0, 0, 0};
   const unsigned pairs = (unsigned)(((last - first + R) / R) * ntf);
   launch_block(h, kTM, k_tm<T, V, YFIRST, false, true, ABL>, dim3(pairs), 128u, 0, h->g, L<T>::C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,

@@ -21,49 +21,33 @@ namespace {
 // Used for the two register-heavy, long-lived-wave kernels (k_jacobi_tb: -15 us per step at
 // 4096^2, k_momentum: -3 us); the HBM-bound kernels with short-lived waves measured best with the
 // plain cells-per-wave rule (chunk_rows) and keep it.
-// (blocks of `threads` threads that fit the chip at once)
+// What the chip holds of `kernel` at once, in the unit its launch is counted in (cached per handle; one host thread per
+// handle): waves of the kernels with blocks of four waves (256 threads; 8 blocks, 32 waves, per CU at most), blocks of
+// the pair kernels (128 threads).  Without an answer from the runtime: three waves per SIMD / six pairs per CU of 256 CUs.
 template <typename K>
-long resident_blocks(vof2d_ctx* h, K kernel, int threads) {
+long resident(vof2d_ctx* h, K kernel, int threads) {
   std::map<const void*, long>& cache = h->occ_cache;
   const void* key = reinterpret_cast<const void*>(kernel);
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
+  const bool pairs = threads == 128;
   int blocks_per_cu = 0;
-  long cap = 6L * 256;
+  long cap = pairs ? 6L * 256 : 3L * 256 * 4;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, threads, 0) == hipSuccess && blocks_per_cu > 0) {
     int cus = 256;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    cap = (long)blocks_per_cu * cus;
+    if (!pairs && blocks_per_cu > 8) blocks_per_cu = 8;
+    cap = (long)blocks_per_cu * cus * (pairs ? 1 : 4);
   } else {
     (void)hipGetLastError();
   }
   cache[key] = cap;
   return cap;
 }
-template <typename K>
-long resident_waves(vof2d_ctx* h, K kernel) {
-  std::map<const void*, long>& cache = h->occ_cache;  // per handle (one host thread per handle)
-  const void* key = reinterpret_cast<const void*>(kernel);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int blocks_per_cu = 0;
-  long cap = 3L * 256 * 4;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, 256, 0) == hipSuccess && blocks_per_cu > 0) {
-    int cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-    if (blocks_per_cu > 8) blocks_per_cu = 8;  // 32 waves per CU
-    cap = (long)blocks_per_cu * cus * 4;
-  } else {
-    (void)hipGetLastError();
-  }
-  cache[key] = cap;
-  return cap;
-}
+inline int interior_rows(const vof2d_ctx* h) { return h->g.ihi - h->g.ilo + 1; }
 int chunk_rows_fit(const vof2d_ctx* h, int ntiles, long capacity, int rmin, int rmax) {
-  const long rows = h->g.ihi - h->g.ilo + 1;
+  const long rows = interior_rows(h);
   const long cap = capacity * 95 / 100;
   int R_out = rmin;
   for (int k = 1; k <= 64; ++k) {
@@ -80,7 +64,7 @@ int chunk_rows_fit(const vof2d_ctx* h, int ntiles, long capacity, int rmin, int 
 // cells-per-wave rule (~4096 waves, chunk length a power of two), used by the x sweep, whose 6
 // lead-in rows per chunk want long chunks (16 rows at 4096^2: 143 us; 8 rows 157 us, 4 rows 200 us)
 int chunk_rows(const vof2d_ctx* h, int ntiles, int rmin, int rmax) {
-  const long rows = h->g.ihi - h->g.ilo + 1;
+  const long rows = interior_rows(h);
   long R = rows * ntiles / 4096;
   if (R < rmin) R = rmin;
   if (R > rmax) R = rmax;
@@ -103,11 +87,14 @@ inline unsigned blocks_rows(int rows, int ntiles, int R) {
   const long waves = (long)((rows + R - 1) / R) * ntiles;
   return (unsigned)((waves + 3) / 4);
 }
-inline unsigned blocks_for(const vof2d_ctx* h, int ntiles, int R) {
-  const int rows = h->g.ihi - h->g.ilo + 1;
-  const long chunks = (rows + R - 1) / R;
-  const long waves = chunks * ntiles;
-  return (unsigned)((waves + 3) / 4);
+// Runtime flags as template arguments: f(std::bool_constant<flags>...).  A launch whose kernel comes in several
+// instantiations (store form, sweep order, ...) is written once, in a generic lambda.
+template <typename F>
+void dispatch(F&& f) { f(); }
+template <typename F, typename... Flags>
+void dispatch(F&& f, bool flag, Flags... flags) {
+  if (flag) dispatch([&](auto... rest) { f(std::true_type{}, rest...); }, flags...);
+  else dispatch([&](auto... rest) { f(std::false_type{}, rest...); }, flags...);
 }
 
 // The BS form of k_momentum (range-checked buffer stores, see store_buf_nt): a lane's V columns must be stored or
@@ -187,132 +174,96 @@ struct L {
   }
   static void normals(vof2d_ctx* h) {
     const int R = pick_rows(h, h->g.ntj);
-    launch(h, kNormals, k_normals<T, V>, dim3(blocks_for(h, h->g.ntj, R)), 0, h->g, C(h), (const T*)F_<T>(h, fF),
+    launch(h, kNormals, k_normals<T, V>, dim3(blocks_rows(interior_rows(h), h->g.ntj, R)), 0, h->g, C(h), (const T*)F_<T>(h, fF),
            F_<T>(h, fMX), F_<T>(h, fMY), R);
   }
   static void kappa(vof2d_ctx* h) {
     const int R = pick_rows(h, h->g.ntj);
-    launch(h, kKappa, k_kappa<T, V>, dim3(blocks_for(h, h->g.ntj, R)), 0, h->g, C(h), (const T*)F_<T>(h, fMX),
+    launch(h, kKappa, k_kappa<T, V>, dim3(blocks_rows(interior_rows(h), h->g.ntj, R)), 0, h->g, C(h), (const T*)F_<T>(h, fMX),
            (const T*)F_<T>(h, fMY), F_<T>(h, fKAPPA), R);
   }
   template <bool STORED>
   static void predictor(vof2d_ctx* h) {
     const int R = pick_rows(h, h->g.ntj);
-    launch(h, kPredictor, k_predictor<T, V, STORED>, dim3(blocks_for(h, h->g.ntj, R)), 0, h->g, C(h),
+    launch(h, kPredictor, k_predictor<T, V, STORED>, dim3(blocks_rows(interior_rows(h), h->g.ntj, R)), 0, h->g, C(h),
            (const T*)F_<T>(h, fU), (const T*)F_<T>(h, fV), (const T*)F_<T>(h, fKAPPA), (const T*)F_<T>(h, fF),
            (const T*)F_<T>(h, fRHO), (const T*)F_<T>(h, fNU), F_<T>(h, fUS), F_<T>(h, fVS), R);
   }
   // fused normals + kappa + predictor + rhs (vof_step only)
   // rows [first, last] of the predictor and the rhs (last < first: all computable rows)
   static void momentum(vof2d_ctx* h, bool virt = false, int adapt_par = -1, int first = 1, int last = 0) {
-    constexpr int Wt = 64 * V, Ht = TileHalo::momentum, ST = Wt - 2 * Ht;   // must match the kernel
-    const int ntt = (h->g.ny + ST - 1) / ST;
+    const int ntt = MomentumGeom<V>::tiles(h->g.ny);
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
-    // one residency round while that keeps the chunks short (strips, small grids); on large grids
-    // several rounds of 14-row chunks beat one round of long ones (4096^2: 184 vs 195 us, 8192^2:
-    // 665 vs 758 us) -- the halo rows of adjacent, simultaneously resident chunks are L2 hits
-    const bool bs = buffer_stores_ok(h) && (h->buf_stores & 1);
-    int R = h->mom_rows > 0 ? h->mom_rows : chunk_rows_fit(h, ntt, bs ? resident_waves(h, k_momentum<T, V, true>) : resident_waves(h, k_momentum<T, V, false>), 4, 64);
-    if (h->mom_rows <= 0 && R > 32) R = 14;
     const TbPlan tp = tb_plan(h, adapt_par);   // (one extra block: the planner wave)
-    const unsigned mom_blocks = blocks_rows(last - first + 1, ntt, R);
-    if (bs)
-      launch(h, kMomentum, k_momentum<T, V, true>, dim3(mom_blocks + (tp.masks ? 1u : 0u)), 0, h->g, C(h), (const T*)F_<T>(h, fF),
-             (const T*)F_<T>(h, fU), (const T*)F_<T>(h, fV), F_<T>(h, fUS), F_<T>(h, fVS), F_<T>(h, fRHS), R, ntt,
+    dispatch([&](auto BS) {
+      // one residency round while that keeps the chunks short (strips, small grids); on large grids
+      // several rounds of 14-row chunks beat one round of long ones (4096^2: 184 vs 195 us, 8192^2:
+      // 665 vs 758 us) -- the halo rows of adjacent, simultaneously resident chunks are L2 hits
+      int R = h->mom_rows > 0 ? h->mom_rows : chunk_rows_fit(h, ntt, resident(h, k_momentum<T, V, BS()>, 256), 4, 64);
+      if (h->mom_rows <= 0 && R > 32) R = 14;
+      launch(h, kMomentum, k_momentum<T, V, BS()>, dim3(blocks_rows(last - first + 1, ntt, R) + (tp.masks ? 1u : 0u)), 0, h->g, C(h),
+             (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fU), (const T*)F_<T>(h, fV), F_<T>(h, fUS), F_<T>(h, fVS), F_<T>(h, fRHS), R, ntt,
              virt ? 1 : 0, tp, first, last);
-    else
-      launch(h, kMomentum, k_momentum<T, V, false>, dim3(mom_blocks + (tp.masks ? 1u : 0u)), 0, h->g, C(h), (const T*)F_<T>(h, fF),
-             (const T*)F_<T>(h, fU), (const T*)F_<T>(h, fV), F_<T>(h, fUS), F_<T>(h, fVS), F_<T>(h, fRHS), R, ntt,
-             virt ? 1 : 0, tp, first, last);
+    }, buffer_stores_ok(h) && (h->buf_stores & 1));
   }
   template <bool STORED>
   static void rhs(vof2d_ctx* h) {
     const int R = pick_rows(h, h->g.ntj);
-    launch(h, kRhs, k_rhs<T, V, STORED>, dim3(blocks_for(h, h->g.ntj, R)), 0, h->g, C(h), (const T*)F_<T>(h, fUS),
+    launch(h, kRhs, k_rhs<T, V, STORED>, dim3(blocks_rows(interior_rows(h), h->g.ntj, R)), 0, h->g, C(h), (const T*)F_<T>(h, fUS),
            (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fRHO), F_<T>(h, fRHS), R);
   }
   // one sweep src -> dst
   template <bool RESID>
   static void jacobi(vof2d_ctx* h, int src, int dst) {
     const int R = pick_rows(h, h->g.ntj);
-    launch(h, kJacobi, k_jacobi<T, V, 2, RESID>, dim3(blocks_for(h, h->g.ntj, R)), 0, h->g, C(h),
+    launch(h, kJacobi, k_jacobi<T, V, 2, RESID>, dim3(blocks_rows(interior_rows(h), h->g.ntj, R)), 0, h->g, C(h),
            (const T*)F_<T>(h, src), (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, h->d_courant + 1);
   }
-  // TS sweeps src -> dst in one launch, with VV columns per lane
-  template <int TS, int VV>
+  // TS sweeps src -> dst in one launch: tile count and rows per chunk.  RESID: the instantiation that reduces the norms
+  // of its last sweep needs a few registers more, so its own occupancy decides the chunk length.
+  static bool square_cells(vof2d_ctx* h) {   // square cells: the product-carrying pipeline
+    const Consts<T> cc = C(h);
+    return cc.dxi2 == cc.dyi2 && !h->tb_general;
+  }
+  template <int TS, bool RESID = false>
   static int jacobi_tb_plan(vof2d_ctx* h, bool sq, int& ntt) {
-    constexpr int Wt = 64 * VV;
-    const int Ht = ((TS - 1 + (sq ? 1 : 0) + VV - 1) / VV) * VV, ST = Wt - 2 * Ht;  // must match the kernel
-    ntt = (h->g.ny + ST - 1) / ST;
-    const long cap = sq ? resident_waves(h, k_jacobi_tb<T, VV, TS, true, false>) : resident_waves(h, k_jacobi_tb<T, VV, TS, false, false>);
-    return h->tb_rows > 0 ? h->tb_rows : chunk_rows_fit(h, ntt, cap, 4, 96);
+    ntt = sq ? JacobiTbGeom<V, TS, true>::tiles(h->g.ny) : JacobiTbGeom<V, TS, false>::tiles(h->g.ny);
+    if (h->tb_rows > 0) return h->tb_rows;
+    int R = 0;
+    dispatch([&](auto SQ) { R = chunk_rows_fit(h, ntt, resident(h, k_jacobi_tb<T, V, TS, SQ(), RESID>, 256), 4, 96); }, sq);
+    return R;
   }
   // k_jacobi_pair (two five-sweep launches as one, kernels/jacobi_pair.h): square cells, ten sweeps per step at least
   static bool jacobi_pair_ok(vof2d_ctx* h) {
-    const Consts<T> cc = C(h);
     // (both precisions since the chained batches: 4096^2 fp32 dam-break 0.268 ms/step in the k_tm form with the pairs, 0.343 in
     //  chains; knob values 1 and 2 are the same now)
-    return h->jpair >= 1 && cc.dxi2 == cc.dyi2 && !h->tb_general && h->tb >= 5 &&
-           h->d.jacobi_iters % 10 == 0;
+    return h->jpair >= 1 && square_cells(h) && h->tb >= 5 && h->d.jacobi_iters % 10 == 0;
   }
-  // Columns per lane of the pair kernels: 2, or -- fp32, knob "pair_vec4" -- 4: a lane then moves the 16 bytes per row the fp64
-  // kernels move, a tile is 256 columns (232 / 240 of them stored instead of 108 / 112 of 128), and the cross-lane moves and the
-  // scalar bookkeeping of a row serve twice the cells.
-  // EXPERIMENT (make variant NAME=vec4 EXTRA=-DVOF_PAIR_VEC4, then knob pair_vec4 = 1; tools/probes/forms_ab.py): same values,
-  // 128 / 135-149 VGPRs (four / three waves per SIMD) -- and 4096^2 fp32 0.62 ms/step against 0.35 with two columns per lane
-  // and 0.33 for the chains: a pair's step lasts as long as its longer wave's instructions, and a wave now carries twice as
-  // many.  The product does not instantiate it.
-  static int pair_vec(const vof2d_ctx* h) {
-#ifdef VOF_PAIR_VEC4
-    return (sizeof(T) == 4 && h->pair_vec4 && h->g.ny % 4 == 0 && buffer_stores_ok(h)) ? 4 : V;
-#else
-    (void)h;
-    return V;
-#endif
-  }
-  template <int VV>
-  static int jacobi_pair_geom_v(vof2d_ctx* h, int& ntt) {
-    constexpr int ST = 64 * VV - 2 * (((2 * 5 + VV - 1) / VV) * VV);   // must match the kernel: 108 columns (232 with four per lane)
-    ntt = (h->g.ny + ST - 1) / ST;
-    const bool bs = buffer_stores_ok(h) && (h->buf_stores & 2);
-    const long cap = bs ? resident_blocks(h, k_jacobi_pair<T, VV, 5, true>, 128) : resident_blocks(h, k_jacobi_pair<T, VV, 5, false>, 128);
-    return h->jpair_rows > 0 ? h->jpair_rows : chunk_rows_fit(h, ntt, cap, 8, 160);
-  }
+  static bool pair_buffer_stores(const vof2d_ctx* h) { return buffer_stores_ok(h) && (h->buf_stores & 2); }
   static int jacobi_pair_geom(vof2d_ctx* h, int& ntt) {
-#ifdef VOF_PAIR_VEC4
-    if constexpr (sizeof(T) == 4) { if (pair_vec(h) == 4) return jacobi_pair_geom_v<4>(h, ntt); }
-#endif
-    return jacobi_pair_geom_v<V>(h, ntt);
+    ntt = JacobiPairGeom<V, 5>::tiles(h->g.ny);
+    if (h->jpair_rows > 0) return h->jpair_rows;
+    int R = 0;
+    dispatch([&](auto BS) { R = chunk_rows_fit(h, ntt, resident(h, k_jacobi_pair<T, V, 5, BS()>, 128), 8, 160); }, pair_buffer_stores(h));
+    return R;
   }
   // ten sweeps src -> dst
-  template <int VV>
-  static void jacobi_pair_v(vof2d_ctx* h, int src, int dst, int adapt_par, int first, int last) {
-    int ntt = 0;
-    const int R = jacobi_pair_geom_v<VV>(h, ntt);
-    const TbPlan tp = tb_plan(h, adapt_par);
-    const unsigned pairs = tp.masks ? (unsigned)tp.waves : (unsigned)(((last - first + R) / R) * ntt);
-    const bool bs = buffer_stores_ok(h) && (h->buf_stores & 2);
-    if (bs)
-      launch_block(h, kJacobiPair, k_jacobi_pair<T, VV, 5, true>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, src),
-                   (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, tp, first, last);
-    else
-      launch_block(h, kJacobiPair, k_jacobi_pair<T, VV, 5, false>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, src),
-                   (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, tp, first, last);
-  }
   static void jacobi_pair(vof2d_ctx* h, int src, int dst, int adapt_par = -1, int first = 1, int last = 0) {
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
-#ifdef VOF_PAIR_VEC4
-    if constexpr (sizeof(T) == 4) { if (pair_vec(h) == 4) return jacobi_pair_v<4>(h, src, dst, adapt_par, first, last); }
-#endif
-    jacobi_pair_v<V>(h, src, dst, adapt_par, first, last);
+    int ntt = 0;
+    const int R = jacobi_pair_geom(h, ntt);
+    const TbPlan tp = tb_plan(h, adapt_par);
+    const unsigned pairs = tp.masks ? (unsigned)tp.waves : (unsigned)(((last - first + R) / R) * ntt);
+    dispatch([&](auto BS) {
+      launch_block(h, kJacobiPair, k_jacobi_pair<T, V, 5, BS()>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, src),
+                   (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, tp, first, last);
+    }, pair_buffer_stores(h));
   }
   // the work plan of the step's five-sweep launches (see tb_make_plan): active on parity-keyed step
-  // sequences (adapt_par = istep & 1), square or not, two columns per lane, up to TB_COLS tile columns
+  // sequences (adapt_par = istep & 1), square or not, up to TB_COLS tile columns
   static TbPlan tb_plan(vof2d_ctx* h, int adapt_par) {
     TbPlan tp{nullptr, nullptr, 0, 0, 0, 0, 0};
     if (adapt_par < 0 || !h->tb_adapt || h->tb < 5 || h->tb_rows > 0) return tp;
-    const Consts<T> cc = C(h);
-    const bool sq = cc.dxi2 == cc.dyi2 && !h->tb_general;
     int ntt = 0;
     int R;
     long waves;
@@ -320,8 +271,8 @@ struct L {
       R = jacobi_pair_geom(h, ntt);
       waves = (long)((h->g.ihi - h->g.ilo + R) / R) * ntt;
     } else {
-      R = jacobi_tb_plan<5, V>(h, sq, ntt);
-      waves = (long)blocks_for(h, ntt, R) * 4;
+      R = jacobi_tb_plan<5>(h, square_cells(h), ntt);
+      waves = (long)blocks_rows(interior_rows(h), ntt, R) * 4;
     }
     if (ntt > TB_COLS || waves > kTbPlanWaves) return tp;
     tp.masks = h->d_tbmask;
@@ -330,74 +281,42 @@ struct L {
     tp.slow10 = h->jpair_active ? h->pair_slow10 : h->tb_slow10;   // (what a row of a reported band costs: per kernel)
     return tp;
   }
-  template <int TS, int VV>
-  static void jacobi_tb_launch(vof2d_ctx* h, const Consts<T>& cc, bool sq, int src, int dst, int R, int ntt, int adapt_par = -1,
-                               int first = 1, int last = 0) {
+  // TS sweeps src -> dst on rows [first, last] (last < first: all computable rows).  RESID: the last sweep also reduces
+  // max|p_new - p| and max|p_new| over the owned rows into d_courant[1..2] (the residual-terminated solve):
+  // same values, uniform chunks, all rows.
+  template <int TS, bool RESID = false>
+  static void jacobi_tb(vof2d_ctx* h, int src, int dst, int adapt_par = -1, int first = 1, int last = 0) {
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
-
-    unsigned long long* none = nullptr;
+    const Consts<T> cc = C(h);
+    const bool sq = square_cells(h);
+    int ntt = 0;
+    const int R = jacobi_tb_plan<TS, RESID>(h, sq, ntt);
     TbPlan tp{nullptr, nullptr, 0, 0, 0, 0, 0};
-    if (TS == 5 && VV == V) tp = tb_plan(h, adapt_par);
+    if (TS == 5 && !RESID) tp = tb_plan(h, adapt_par);
     // (with a plan the launch holds the waves of the whole grid's plan, whatever part of the rows it is for: every
     // wave takes the part of its planned chunk inside [first, last], or nothing)
-    const unsigned nblk = tp.masks ? blocks_for(h, ntt, R) : blocks_rows(last - first + 1, ntt, R);
+    const unsigned all_blocks = blocks_rows(interior_rows(h), ntt, R);
+    const unsigned nblk = tp.masks ? all_blocks : blocks_rows(last - first + 1, ntt, R);
+    unsigned long long* const norms = RESID ? h->d_courant + 1 : nullptr;
+    auto go = [&](auto SQ, auto BS) {
+      launch(h, kJacobiTB, k_jacobi_tb<T, V, TS, SQ(), RESID, BS()>, dim3(nblk), 0, h->g, cc,
+             (const T*)F_<T>(h, src), (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, norms, tp, first, last);
+    };
     // the buffer-store form where the launch is ONE residency round of the chunk plan (4096^2, the strips of a multi-GPU
     // run: 105 -> 103 us, 53.7 -> 49.0 us): it needs 126 VGPRs instead of 129, i.e. four waves per SIMD are resident
     // where the plan counted on three, which breaks the round structure of a multi-round launch (8192^2 on one GPU:
     // 397 -> 435 us)
-    const bool one_round = (long)blocks_for(h, ntt, R) * 4 <= resident_waves(h, k_jacobi_tb<T, VV, TS, true, false>);
-    constexpr bool kBufForm = sizeof(T) * VV == 16 || sizeof(T) * VV == 8;   // (store_buf_nt: one b128 / b64 store per lane)
-    if (kBufForm && sq && one_round && buffer_stores_ok(h) && (h->buf_stores & 2)) {
-      if constexpr (kBufForm)
-        launch(h, kJacobiTB, k_jacobi_tb<T, VV, TS, true, false, true>, dim3(nblk), 0, h->g, cc,
-               (const T*)F_<T>(h, src), (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, none, tp, first, last);
-    } else if (sq)
-      launch(h, kJacobiTB, k_jacobi_tb<T, VV, TS, true, false>, dim3(nblk), 0, h->g, cc,
-             (const T*)F_<T>(h, src), (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, none, tp, first, last);
-    else
-      launch(h, kJacobiTB, k_jacobi_tb<T, VV, TS, false, false>, dim3(nblk), 0, h->g, cc,
-             (const T*)F_<T>(h, src), (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, none, tp, first, last);
-  }
-  // TS sweeps src -> dst, the last of which also reduces max|p_new - p| and max|p_new| over the owned
-  // rows into d_courant[1..2] (the residual-terminated solve): same values as
-  // jacobi_tb<TS>, same launch plan (the RESID instantiation needs a few registers more, so its
-  // own occupancy decides the chunk length)
-  template <int TS>
-  static void jacobi_tb_resid(vof2d_ctx* h, int src, int dst) {
-    const Consts<T> cc = C(h);
-    const bool sq = cc.dxi2 == cc.dyi2 && !h->tb_general;
-    constexpr int Wt = 64 * V;
-    const int Ht = ((TS - 1 + (sq ? 1 : 0) + V - 1) / V) * V, ST = Wt - 2 * Ht;
-    const int ntt = (h->g.ny + ST - 1) / ST;
-    const long cap = sq ? resident_waves(h, k_jacobi_tb<T, V, TS, true, true>) : resident_waves(h, k_jacobi_tb<T, V, TS, false, true>);
-    const int R = h->tb_rows > 0 ? h->tb_rows : chunk_rows_fit(h, ntt, cap, 4, 96);
-    const TbPlan notp{nullptr, nullptr, 0, 0, 0, 0};   // uniform layout
-    if (sq)
-      launch(h, kJacobiTB, k_jacobi_tb<T, V, TS, true, true>, dim3(blocks_for(h, ntt, R)), 0, h->g, cc,
-             (const T*)F_<T>(h, src), (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, h->d_courant + 1, notp, h->g.ilo, h->g.ihi);
-    else
-      launch(h, kJacobiTB, k_jacobi_tb<T, V, TS, false, true>, dim3(blocks_for(h, ntt, R)), 0, h->g, cc,
-             (const T*)F_<T>(h, src), (const T*)F_<T>(h, fRHS), F_<T>(h, dst), R, ntt, h->d_courant + 1, notp, h->g.ilo, h->g.ihi);
-  }
-  template <int TS>
-  static void jacobi_tb(vof2d_ctx* h, int src, int dst, int adapt_par = -1, int first = 1, int last = 0) {
-    const Consts<T> cc = C(h);
-    const bool sq = cc.dxi2 == cc.dyi2 && !h->tb_general;  // square cells: the product-carrying pipeline
-    int ntt = 0;
-#ifdef VOF_TB_VV      // EXPERIMENT: wider tiles for the fused Jacobi kernel
-    if (TS == 5 && sizeof(T) == 8) {
-      const int R = jacobi_tb_plan<TS, VOF_TB_VV>(h, sq, ntt);
-      jacobi_tb_launch<TS, VOF_TB_VV>(h, cc, sq, src, dst, R, ntt, -1, first, last);
-      return;
+    static_assert(sizeof(T) * V == 16 || sizeof(T) * V == 8, "store_buf_nt: one b128 / b64 store per lane");
+    if constexpr (!RESID) {
+      if (sq && (long)all_blocks * 4 <= resident(h, k_jacobi_tb<T, V, TS, true, false>, 256) && pair_buffer_stores(h))
+        return go(std::true_type{}, std::true_type{});
     }
-#endif
-    const int R = jacobi_tb_plan<TS, V>(h, sq, ntt);
-    jacobi_tb_launch<TS, V>(h, cc, sq, src, dst, R, ntt, adapt_par, first, last);
+    if (sq) go(std::true_type{}, std::false_type{}); else go(std::false_type{}, std::false_type{});
   }
   template <bool STORED>
   static void correct(vof2d_ctx* h) {
     const int R = pick_rows(h, h->g.ntj);
-    launch(h, kCorrect, k_correct<T, V, STORED>, dim3(blocks_for(h, h->g.ntj, R)), 0, h->g, C(h),
+    launch(h, kCorrect, k_correct<T, V, STORED>, dim3(blocks_rows(interior_rows(h), h->g.ntj, R)), 0, h->g, C(h),
            (const T*)F_<T>(h, fP), (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fRHO), (const T*)F_<T>(h, fUS),
            (const T*)F_<T>(h, fVS), F_<T>(h, fU), F_<T>(h, fV), R, h->d_courant);
   }
@@ -433,35 +352,23 @@ struct L {
     const long R = (rows + chunks - 1) / chunks;
     return (int)(R < 16 ? 16 : (R > 96 ? 96 : R));
   }
-  template <bool YFIRST, bool STORE_UV>
-  static void tm(vof2d_ctx* h, int adapt_par, int first = 1, int last = 0, int rows_forced = 0, int first2 = 1, int last2 = 0) {
+  // rows [first, last] and, in the same launch, [first2, last2]; store_uv: the last k_tm of a batch
+  static void tm(vof2d_ctx* h, bool y_first, bool store_uv, int adapt_par, int first = 1, int last = 0, int rows_forced = 0, int first2 = 1, int last2 = 0) {
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
-#ifdef VOF_PAIR_VEC4
-    if constexpr (sizeof(T) == 4) { if (pair_vec(h) == 4) return tm_v<4, YFIRST, STORE_UV>(h, adapt_par, first, last, rows_forced, first2, last2); }
-#endif
-    tm_v<V, YFIRST, STORE_UV>(h, adapt_par, first, last, rows_forced, first2, last2);
-  }
-  template <int VV, bool YFIRST, bool STORE_UV>
-  static void tm_v(vof2d_ctx* h, int adapt_par, int first, int last, int rows_forced, int first2, int last2) {
-    constexpr int ST = 64 * VV - 2 * TmGeom::HF;
-    const int ntf = (h->g.ny + ST - 1) / ST;
+    const int ntf = TmGeom<V>::tiles(h->g.ny);
+    const TbPlan tp = tb_plan(h, adapt_par);
     // pair chunks: a whole number of residency rounds, just filled (6 pairs per CU: 24 KB of LDS each) -- a launch that needs a
     // little more than k rounds pays for k + 1 --, as many rounds as keep the chunks near 50 rows (one round of 100-row
     // chunks: every step of every pair takes 3.3 us instead of 1.9).  4096^2, 112-column tiles, us per launch: 40 rows
     // (2.5 rounds) 261 / 281 (inside / behind the front), 48 252 / 282, 52 253 / 280, 54 256 / 277, 56 257 / 284,
     // 100 376 / 381 (tools/probes/pair_bound.py --rows)
-    const int R = rows_forced > 0 ? rows_forced : tm_chunk_rows(h, last - first + 1, ntf, resident_blocks(h, k_tm<T, VV, YFIRST, STORE_UV, true>, 128));
-    const TbPlan tp = tb_plan(h, adapt_par);
-    const unsigned pairs = (unsigned)((((last - first + R) / R) + (last2 >= first2 ? (last2 - first2 + R) / R : 0)) * ntf) + (tp.masks ? 1u : 0u);
-    const bool bs = buffer_stores_ok(h) && (h->buf_stores & 4);
-    if (bs)
-      launch_block(h, STORE_UV ? kTMUV : kTM, k_tm<T, VV, YFIRST, STORE_UV, true>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
-             (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
-             F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, h->tm_rhs_alt ? fKAPPA : fRHS), h->d_courant, R, tp, first, last, first2, last2);
-    else
-      launch_block(h, STORE_UV ? kTMUV : kTM, k_tm<T, VV, YFIRST, STORE_UV, false>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
-             (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
-             F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, h->tm_rhs_alt ? fKAPPA : fRHS), h->d_courant, R, tp, first, last, first2, last2);
+    dispatch([&](auto YF, auto UV, auto BS) {
+      const int R = rows_forced > 0 ? rows_forced : tm_chunk_rows(h, last - first + 1, ntf, resident(h, k_tm<T, V, YF(), UV(), true>, 128));
+      const unsigned pairs = (unsigned)((((last - first + R) / R) + (last2 >= first2 ? (last2 - first2 + R) / R : 0)) * ntf) + (tp.masks ? 1u : 0u);
+      launch_block(h, UV() ? kTMUV : kTM, k_tm<T, V, YF(), UV(), BS()>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
+                   (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
+                   F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, h->tm_rhs_alt ? fKAPPA : fRHS), h->d_courant, R, tp, first, last, first2, last2);
+    }, y_first, store_uv, buffer_stores_ok(h) && (h->buf_stores & 4));
   }
   // ---- conjugate gradients (kernels/cg.h)
   // sum of ap over the interior, in double, of the values the kernels form in T: ap depends on the position through
@@ -575,15 +482,14 @@ struct L {
     return n;
   }
   // the rows of rr (all computable rows by default)
-  template <bool YFIRST>
-  static void transport(vof2d_ctx* h, const RowRanges* ranges = nullptr) {
-    RowRanges rr;
-    if (ranges) rr = *ranges;
-    else rr = RowRanges{{h->g.ilo, 1, 1}, {h->g.ihi, 0, 0}, {transport_rows(h), 1, 1}};
+  static void transport(vof2d_ctx* h, bool y_first, const RowRanges* ranges = nullptr) {
+    const RowRanges rr = ranges ? *ranges : RowRanges{{h->g.ilo, 1, 1}, {h->g.ihi, 0, 0}, {transport_rows(h), 1, 1}};
     const unsigned tr_blocks = (unsigned)((range_chunks(rr) * h->nty + 3) / 4);
-    launch(h, kTransport, k_transport<T, V, YFIRST>, dim3(tr_blocks), 0, h->g, C(h),
-           (const T*)F_<T>(h, fF), F_<T>(h, fF2), h->nty, (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS),
-           (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV), h->d_courant, rr);
+    dispatch([&](auto YF) {
+      launch(h, kTransport, k_transport<T, V, YF()>, dim3(tr_blocks), 0, h->g, C(h),
+             (const T*)F_<T>(h, fF), F_<T>(h, fF2), h->nty, (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS),
+             (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV), h->d_courant, rr);
+    }, y_first);
   }
 };
 

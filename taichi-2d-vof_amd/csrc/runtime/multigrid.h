@@ -12,7 +12,7 @@ namespace {
 int cg_prepare(vof2d_ctx* h) {
   if (h->cg_arena) return VOF_OK;
   const size_t fbytes = h->field_elems * h->esz;
-  const size_t nblocks = blocks_for(h, h->g.ntj, 1);   // (the most blocks a launch can have: one-row chunks, knob "rows_per_wave")
+  const size_t nblocks = blocks_rows(interior_rows(h), h->g.ntj, 1);   // (the most blocks a launch can have: one-row chunks, knob "rows_per_wave")
   const size_t pbytes = (nblocks * kCgPart + CG_NSCAL) * sizeof(double);
   if (hipMalloc(reinterpret_cast<void**>(&h->cg_arena), 4 * fbytes) != hipSuccess) {
     (void)hipGetLastError();

@@ -1,0 +1,61 @@
+// runtime/rows.h -- the rows of a strip: what it owns, the bands at its interior edges, the rest, and which of them
+// a launch of one part gets
+//
+// Plain C++ (no HIP): the host runtime includes it through schedule.h, the CPU tests compile it on its own.
+#pragma once
+#include "../../../include/vof2d.h"
+
+namespace vof {
+
+struct RowRange {
+  int first, last;   // inclusive; last < first: no rows
+  bool empty() const { return last < first; }
+  int rows() const { return empty() ? 0 : last - first + 1; }
+};
+constexpr RowRange kNoRows{1, 0};
+
+// A handle stores rows row_lo .. row_hi of the global rows 0 .. nx + 1 and owns own_lo .. own_hi of them.  It computes
+// the interior rows it has a neighbour row for on both sides; an edge of the strip that is not a wall of the domain
+// is an interior edge, and the W = VOF_HALO_ROWS owned rows next to it are what the neighbour's halo receives: a band.
+struct StripRows {
+  RowRange owned;              // the owned rows inside the computable rows
+  RowRange band_lo, band_hi;   // the W-row bands (none at a wall; none where the bands meet)
+  RowRange rest;               // the owned rows between the bands (none where the bands meet)
+  bool has_bands;              // the strip has an interior edge
+  bool meet;                   // the bands leave no row between them: the strip is not split, all of it counts as bands
+};
+inline StripRows strip_rows(int row_lo, int row_hi, int own_lo, int own_hi, int nx, int jacobi_iters) {
+  const int W = VOF_HALO_ROWS(jacobi_iters);
+  const int ilo = row_lo + 1 > 1 ? row_lo + 1 : 1, ihi = row_hi - 1 < nx ? row_hi - 1 : nx;
+  const bool edge_lo = row_lo != 0, edge_hi = row_hi != nx + 1;
+  StripRows s{{own_lo > ilo ? own_lo : ilo, own_hi < ihi ? own_hi : ihi}, kNoRows, kNoRows, kNoRows, edge_lo || edge_hi, false};
+  const int in_lo = edge_lo ? s.owned.first + W : s.owned.first, in_hi = edge_hi ? s.owned.last - W : s.owned.last;
+  s.meet = s.has_bands && in_lo > in_hi;
+  if (s.meet) return s;
+  if (edge_lo) s.band_lo = {s.owned.first, in_lo - 1};
+  if (edge_hi) s.band_hi = {in_hi + 1, s.owned.last};
+  s.rest = {in_lo, in_hi};
+  return s;
+}
+
+// The kernels that end a step on a strip run on all owned rows at once, or on the bands first (the exchange waits for
+// them alone) and on the rest beside the exchange.
+enum StripPart { kAllOwned = 0, kEdgeBands = 1, kRest = 2 };
+// What the launch of one part gets: the two bands (short chunks, both in one launch) and / or one body range (chunks
+// of the usual length).  A full domain has no bands: everything is "rest".  Where the bands meet there is no rest:
+// everything is "bands", as one body range.  A part with nothing in it gets no launch.
+struct PartRows {
+  RowRange band_lo, band_hi, body;
+  bool empty() const { return band_lo.empty() && band_hi.empty() && body.empty(); }
+};
+inline PartRows part_rows(const StripRows& s, int part) {
+  const bool split = s.has_bands && !s.meet;
+  if (part == kAllOwned || !split) {
+    const bool mine = part == kAllOwned || (part == kEdgeBands) == s.has_bands;
+    return {kNoRows, kNoRows, mine ? s.owned : kNoRows};
+  }
+  if (part == kEdgeBands) return {s.band_lo, s.band_hi, kNoRows};
+  return {kNoRows, kNoRows, s.rest};
+}
+
+}  // namespace vof

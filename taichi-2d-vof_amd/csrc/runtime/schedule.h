@@ -4,6 +4,7 @@
 // context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
 #include "graphs.h"
+#include "rows.h"
 
 namespace {
 
@@ -17,42 +18,28 @@ template <typename T, bool POST, bool CORR = false>
 void sweep_x(vof2d_ctx* h) { L<T>::template fct_x<POST, CORR>(h); swap_F(h); }
 template <typename T, bool POST, bool CORR = false>
 void sweep_y(vof2d_ctx* h) { L<T>::template fct_y<POST, CORR>(h); swap_F(h); }
+inline StripRows strip_rows(const vof2d_ctx* h) {
+  return vof::strip_rows(h->d.row_lo, h->d.row_hi, h->d.own_lo, h->d.own_hi, h->d.nx, h->d.jacobi_iters);
+}
 // The second sweep of a step produces the final F.  On a strip only the owned rows are produced
 // (the halo rows are the neighbours' to send).
 template <typename T>
 void final_sweep(vof2d_ctx* h, bool along_x) {
-  const int lo = h->d.own_lo > h->g.ilo ? h->d.own_lo : h->g.ilo, hi = h->d.own_hi < h->g.ihi ? h->d.own_hi : h->g.ihi;
-  if (hi < lo) return;
-  if (along_x) L<T>::template fct_x<true, false>(h, lo, hi); else L<T>::template fct_y<true, false>(h, lo, hi);
+  const RowRange o = strip_rows(h).owned;
+  if (o.empty()) return;
+  if (along_x) L<T>::template fct_x<true, false>(h, o.first, o.last); else L<T>::template fct_y<true, false>(h, o.first, o.last);
 }
 
-enum TransportPart { kAllOwned = 0, kEdgeBands = 1, kRest = 2 };
-// The fused transport (k_transport) on the owned rows of a strip: all at once (kAllOwned), only the
-// two W-row bands at its interior edges (kEdgeBands: both in ONE launch), or only the rest (kRest).
+// The fused transport (k_transport) on one part of the owned rows of a strip (runtime/rows.h).
 template <typename T>
 void transport_part(vof2d_ctx* h, bool y_first, int part) {
-  const int W = VOF_HALO_ROWS(h->d.jacobi_iters);
-  const int lo = h->d.own_lo > h->g.ilo ? h->d.own_lo : h->g.ilo, hi = h->d.own_hi < h->g.ihi ? h->d.own_hi : h->g.ihi;
-  const bool band_lo = !h->g.wall_lo, band_hi = !h->g.wall_hi;
-  const int in_lo = band_lo ? lo + W : lo, in_hi = band_hi ? hi - W : hi;   // strips are >= W rows thick
-  const bool split = in_lo <= in_hi && (band_lo || band_hi);
+  const PartRows pr = part_rows(strip_rows(h), part);
+  if (pr.empty()) return;
   // the bands are few rows: short chunks, so that they are many short-lived waves (2 x 16 rows of an
   // 8192-wide strip: 31 us with 16-row chunks, 15-18 us with 4-row chunks)
   const int Rb = h->band_rows, R = L<T>::transport_rows(h);
-  RowRanges rr{{1, 1, 1}, {0, 0, 0}, {Rb, Rb, R}};
-  if (part == kAllOwned || !split) {
-    // one range: a full domain has no bands (everything is "rest"); where the bands meet there is
-    // no rest (everything is "bands")
-    if (part == kRest && (band_lo || band_hi)) return;
-    if (part == kEdgeBands && !(band_lo || band_hi)) return;
-    rr.first[2] = lo; rr.last[2] = hi;
-  } else if (part == kEdgeBands) {
-    if (band_lo) { rr.first[0] = lo; rr.last[0] = in_lo - 1; }
-    if (band_hi) { rr.first[1] = in_hi + 1; rr.last[1] = hi; }
-  } else {
-    rr.first[2] = in_lo; rr.last[2] = in_hi;
-  }
-  if (y_first) L<T>::template transport<true>(h, &rr); else L<T>::template transport<false>(h, &rr);
+  const RowRanges rr{{pr.band_lo.first, pr.band_hi.first, pr.body.first}, {pr.band_lo.last, pr.band_hi.last, pr.body.last}, {Rb, Rb, R}};
+  L<T>::transport(h, y_first, &rr);
 }
 
 // interior copy src -> dst (only used to keep p in place for odd sweep counts)
@@ -101,8 +88,8 @@ void jacobi_n(vof2d_ctx* h, int n, bool resid_last, int adapt_par = -1) {
     else { L<T>::template jacobi<false>(h, cur, oth); left -= 1; }
     flip();
   }
-  if (last == 5) { L<T>::template jacobi_tb_resid<5>(h, cur, oth); flip(); }
-  else if (last == 2) { L<T>::template jacobi_tb_resid<2>(h, cur, oth); flip(); }
+  if (last == 5) { L<T>::template jacobi_tb<5, true>(h, cur, oth); flip(); }
+  else if (last == 2) { L<T>::template jacobi_tb<2, true>(h, cur, oth); flip(); }
   else if (last == 1) { L<T>::template jacobi<true>(h, cur, oth); flip(); }
   if (cur != fP) copy_interior<T>(h, fPT, fP);
 }
@@ -177,7 +164,7 @@ void enqueue_step(vof2d_ctx* h, int64_t istep, bool lean = false, bool virt = fa
     L<T>::momentum(h, virt, mg ? -1 : (int)(istep & 1));   // (no Jacobi launches behind it: no work plan to make)
     if (mg) mg_enqueue_step_solve<T>(h, mg->cycles, mg->criterion);
     else jacobi_n<T>(h, h->d.jacobi_iters, false, (int)(istep & 1));
-    if (istep % 2 == 0) L<T>::template transport<true>(h); else L<T>::template transport<false>(h);
+    L<T>::transport(h, istep % 2 == 0);
     swap_F(h);
     if (!virt) L<T>::template set_bc<BC_ALL>(h);
     return;
@@ -321,7 +308,7 @@ bool enqueue_steps_halves(vof2d_ctx* h, int64_t first_step, int K) {
     ok = ok && hipEventRecord(ev_plan[k], st[P - 1]) == hipSuccess;
     all([&](int a, int b, bool) {
       const RowRanges rr{{a, 1, 1}, {b, 0, 0}, {L<T>::transport_rows(h), 1, 1}};
-      if (istep % 2 == 0) L<T>::template transport<true>(h, &rr); else L<T>::template transport<false>(h, &rr);
+      L<T>::transport(h, istep % 2 == 0, &rr);
     });
     swap_F(h);
   }
@@ -367,11 +354,7 @@ void enqueue_steps_tm(vof2d_ctx* h, int64_t first_step, int K) {
     const int64_t istep = first_step + k;
     const int par = (int)(istep & 1);
     batch_jacobi<T>(h, par);
-    if (k < K - 1) {
-      if (istep % 2 == 0) L<T>::template tm<true, false>(h, par ^ 1); else L<T>::template tm<false, false>(h, par ^ 1);
-    } else {
-      if (istep % 2 == 0) L<T>::template tm<true, true>(h, par ^ 1); else L<T>::template tm<false, true>(h, par ^ 1);
-    }
+    L<T>::tm(h, istep % 2 == 0, /*store_uv=*/k == K - 1, par ^ 1);
     swap_SR(h);
     swap_F(h);
   }

@@ -7,9 +7,10 @@
 //
 // This file holds the extern "C" entry points only: null and argument checks, the error messages, settle_ghosts, one
 // call into the runtime, the dirty flags.  The runtime behind them:
-//   runtime/context.h    the handle (with its graph cache), constants, chunk-length heuristics
-//   runtime/launches.h   one launch wrapper per kernel
+//   runtime/context.h    the handle (with its graph cache), constants
+//   runtime/launches.h   chunk-length heuristics, one launch wrapper per kernel (tile counts from the geometry in vof2d_device.h)
 //   runtime/graphs.h     the keys of the graph cache, the one capture helper
+//   runtime/rows.h       plain C++: the owned rows of a strip, its edge bands, the rest; what a launch of one part gets
 //   runtime/schedule.h   the per-step schedule, ghost-cell bookkeeping, dropping graphs
 //   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
@@ -48,7 +49,7 @@ const Knob kKnobs[] = {
   KNOB("fuse_transport", fuse_transport, false), KNOB("virtual_ghosts", virtual_ghosts, false), KNOB("buffer_stores", buf_stores, false),
   KNOB("overlap_halves", halves, false), KNOB("batch_steps", step_batch[0], false), KNOB("fuse_tm", fuse_tm, false),
   KNOB("tm_rows", tm_rows, false), KNOB("jacobi_pair", jpair, false), KNOB("jacobi_pair_rows", jpair_rows, false),
-  KNOB("pair_vec4", pair_vec4, false), KNOB("pair_slow10", pair_slow10, false), KNOB("solve_pairs", solve_pairs, false),
+  KNOB("pair_slow10", pair_slow10, false), KNOB("solve_pairs", solve_pairs, false),
   KNOB("tb_slow10", tb_slow10, false), KNOB("tune_period", tune.period, false),
   KNOB("mg_nu", mg_nu, true), KNOB("mg_levels", mg_levels, true), KNOB("mg_graph", mg_graph, true),
   KNOB("mg_coarse_block", mg_coarse_block, false),
@@ -102,16 +103,12 @@ int vof_create(const vof2d_desc* d, void* stream, vof2d_handle* out) {
   g.own_lo = d->own_lo; g.own_hi = d->own_hi;
   g.wall_lo = d->row_lo == 0; g.wall_hi = d->row_hi == d->nx + 1;
   g.ntj = (d->ny + W - 1) / W;
-  h->nty = (d->ny + (W - 2 * TileHalo::transport) - 1) / (W - 2 * TileHalo::transport);
+  h->nty = d->dtype == VOF_F64 ? TransportGeom<VecWidth<double>::V>::tiles(d->ny) : TransportGeom<VecWidth<float>::V>::tiles(d->ny);
   const int align = 128 / (int)h->esz;  // elements per 128 bytes
   g.col0 = align - 1;                   // j = 1 lands on a 128-byte boundary
   // furthest column any lane touches: the overlapped tiles of k_fct_y / k_jacobi_tb start at most
   // H <= 12 columns left of j = 1 and their last tile may run a full tile past ny.
-#ifdef VOF_PAIR_VEC4   // (experiment: the fp32 pair kernels with four columns per lane, 256-column tiles)
-  long maxcol = (long)d->ny + (d->dtype == VOF_F32 ? 256 : W) + 16;
-#else
-  long maxcol = (long)d->ny + W + 16;
-#endif
+  const long maxcol = (long)d->ny + W + 16;
   g.pitch = ((g.col0 + maxcol + 1 + align - 1) / align) * align;
   const size_t nrows = (size_t)(d->row_hi - d->row_lo + 1);
   h->field_elems = nrows * (size_t)g.pitch + (size_t)align;  // + one 128-byte tail pad
@@ -129,19 +126,10 @@ int vof_create(const vof2d_desc* d, void* stream, vof2d_handle* out) {
     }
     if (const char* ev = getenv("VOF2D_OVERLAP_HALVES")) h->halves = atoi(ev);   // (profiling runs: per-kernel counters want one kernel at a time)
     if (const char* ev = getenv("VOF2D_FUSE_TM")) h->fuse_tm = atoi(ev);
-#ifdef VOF_ARENA_EXP   // placement experiment (tools/probes/arena_modes.py): shift of the whole arena, extra bytes between fields
-    const size_t shift_ = getenv("VOF2D_ARENA_SHIFT") ? (size_t)atoll(getenv("VOF2D_ARENA_SHIFT")) : 0;
-    const size_t skew_ = getenv("VOF2D_FIELD_SKEW") ? (size_t)atoll(getenv("VOF2D_FIELD_SKEW")) : 0;
-    const size_t bytes = (h->field_elems * h->esz + skew_) * NFIELDS + shift_;
-    if (hipMalloc(reinterpret_cast<void**>(&h->arena), bytes) != hipSuccess) { rc = VOF_ENOMEM; break; }
-    if (hipMemsetAsync(h->arena, 0, bytes, h->stream) != hipSuccess) { rc = VOF_EHIP; break; }
-    for (int k = 0; k < NFIELDS; ++k) h->fld[k] = h->arena + shift_ + (size_t)k * (h->field_elems * h->esz + skew_);
-#else
     const size_t bytes = h->field_elems * h->esz * NFIELDS;
     if (hipMalloc(reinterpret_cast<void**>(&h->arena), bytes) != hipSuccess) { rc = VOF_ENOMEM; break; }
     if (hipMemsetAsync(h->arena, 0, bytes, h->stream) != hipSuccess) { rc = VOF_EHIP; break; }
     for (int k = 0; k < NFIELDS; ++k) h->fld[k] = h->arena + (size_t)k * h->field_elems * h->esz;
-#endif
     h->f_home = h->fld[fF];
     h->us_home = h->fld[fUS];
     h->p_home = h->fld[fP];

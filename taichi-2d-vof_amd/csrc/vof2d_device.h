@@ -14,8 +14,54 @@
 // cross-lane shuffles.  Waves never synchronise with each other (no LDS, no
 // barriers), so a 256-thread block is just four independent adjacent tiles.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+namespace vof {
+
+// Elements per lane and row: 2 for both precisions, i.e. a wave tile is 128 columns.  (16 bytes per
+// lane -- 4 floats, 256-column tiles -- halves the number of tiles, and with it the chunk length a
+// residency round allows, so the lead-in rows of every chunk weigh twice as much: fp32 at 4096^2
+// 601 us/step with V = 4, 443 us/step with V = 2; 2048^2 249 -> 174 us.  The same in the pair kernels
+// alone -- the kernels keep their V parameter, the runtime never asked for 4 outside experiments:
+// k_jacobi_pair / k_tm<float, 4> need 128 / 135-149 VGPRs and ran 4096^2 fp32 at 0.62 ms/step against
+// 0.35 with V = 2; wider tiles for k_jacobi_tb<double> lost the same way.  tools/probes/README.md.)
+template <typename T> struct VecWidth { static constexpr int V = 2; };
+
+// ------------------------------------------------------------------ tile geometry
+// A marching kernel's wave loads and computes a tile of 64*V columns and stores all of it but H columns on either
+// side (the neighbouring tiles do): tiles advance by STRIDE = 64*V - 2*H columns, the first one starts at column
+// 1 - H, and tiles(ny) of them cover j = 1 .. ny.  The kernel takes H and STRIDE, the launch wrapper its tile count,
+// from the one definition of its family below.  (Plain C++: this part of the file also compiles without HIP.)
+template <int V, int HALO>
+struct TileGeom {
+  static constexpr int W = 64 * V, H = HALO, STRIDE = W - 2 * H;
+  static constexpr int tiles(int ny) { return (ny + STRIDE - 1) / STRIDE; }
+};
+// Columns on each side of a tile that k_momentum / the FCT y stage load and compute but do not store.  The stencils
+// need 2 and 4; 8 makes the tile stride 112 columns = 7 cache lines of doubles, so every tile's stored segment starts
+// and ends on a 128-byte line (on a 64-byte sector in fp32).  With strides of 124 / 120 columns two waves -- often on
+// different CUs -- each write part of the line between their tiles: the compute-free skeletons of the two kernels
+// (tools/probes/stream_pattern.hip) run 11 % / 7 % faster at 112.
+struct TileHalo { static constexpr int momentum = 2, transport = 8; };
+template <int V> using MomentumGeom = TileGeom<V, TileHalo::momentum>;     // k_momentum
+template <int V> using TransportGeom = TileGeom<V, TileHalo::transport>;   // k_fct_y, k_transport
+// k_tm: 4 (transport) + 3 (momentum) invalid columns per side of the fused march, rounded up to even
+template <int V> using TmGeom = TileGeom<V, 8>;
+// k_jacobi_tb: TS - 1 from the cross-lane exchange of sweeps 2 .. TS, plus 1 where the first sweep also takes its
+// j-neighbours from adjacent lanes (SQ), rounded up to V
+template <int V, int TS, bool SQ> using JacobiTbGeom = TileGeom<V, ((TS - 1 + (SQ ? 1 : 0) + V - 1) / V) * V>;
+// k_jacobi_pair: TS per side and march (TS - 1 cross-lane sweeps + the first sweep's DPP neighbours), two marches
+template <int V, int TS> using JacobiPairGeom = TileGeom<V, ((2 * TS + V - 1) / V) * V>;
+
+static_assert(MomentumGeom<2>::STRIDE == 124 && TransportGeom<2>::STRIDE == 112 && TmGeom<2>::STRIDE == 112, "tile strides");
+static_assert(JacobiTbGeom<2, 5, true>::STRIDE == 116 && JacobiTbGeom<2, 5, false>::STRIDE == 120, "tile strides");
+static_assert(JacobiTbGeom<2, 2, true>::STRIDE == 124 && JacobiTbGeom<2, 2, false>::STRIDE == 124, "tile strides");
+static_assert(JacobiPairGeom<2, 5>::STRIDE == 108, "tile strides");
+
+}  // namespace vof
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 
 namespace vof {
 
@@ -40,19 +86,6 @@ struct Consts {
   // set_init_F literals (2dvof.py:141-159), folded in double then rounded
   T ic1_x2, ic1_y2, ic_r, ic_cx, ic2_cy, ic3_cy, ic3_pool;
 };
-
-// Elements per lane and row: 2 for both precisions, i.e. a wave tile is 128 columns.  (16 bytes per
-// lane -- 4 floats, 256-column tiles -- halves the number of tiles, and with it the chunk length a
-// residency round allows, so the lead-in rows of every chunk weigh twice as much: fp32 at 4096^2
-// 601 us/step with V = 4, 443 us/step with V = 2; 2048^2 249 -> 174 us.)
-template <typename T> struct VecWidth { static constexpr int V = 2; };
-
-// Columns on each side of a 64*V-column tile that k_momentum / the FCT y stage load and compute but do not store
-// (the neighbouring tile does).  The stencils need 2 and 4; 8 makes the tile stride 112 columns = 7 cache lines of
-// doubles, so every tile's stored segment starts and ends on a 128-byte line (on a 64-byte sector in fp32).  With
-// strides of 124 / 120 columns two waves -- often on different CUs -- each write part of the line between their tiles:
-// the compute-free skeletons of the two kernels (tools/probes/stream_pattern.hip) run 11 % / 7 % faster at 112.
-struct TileHalo { static constexpr int momentum = 2, transport = 8; };
 
 template <typename T, int V>
 struct alignas(sizeof(T) * V) Pack {
@@ -92,3 +125,4 @@ template <> __device__ __forceinline__ double dabs<double>(double x) { return __
 template <> __device__ __forceinline__ float dabs<float>(float x) { return __builtin_fabsf(x); }
 
 }  // namespace vof
+#endif  // __HIPCC__
