@@ -1,7 +1,7 @@
 // runtime/comm.h -- strips over RCCL: run-time binding (dlopen), the halo send/recv groups, the step with its exchanges
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
 #include "step.h"
 
@@ -190,44 +190,28 @@ void tm5_head(vof2d_ctx* h) {
   // The middle steps alternate u*, v* between their own arrays and mx, my, and a call may end with the host's view on
   // the second pair: the cells the predictor never writes (u* on i = 1, v* on j = 1, ny + 1, the ghost cells) must hold
   // the zeros the reference's never-written entries hold (S5), not what a verb (get_normal_young) left there.
-  if (h->alt_dirty) {
+  if (h->state.alt_dirty) {
     (void)hipMemsetAsync(h->fld[fMX], 0, h->field_elems * h->esz, h->stream);
     (void)hipMemsetAsync(h->fld[fMY], 0, h->field_elems * h->esz, h->stream);
-    h->alt_dirty = false;
+    h->state.alt_dirty = false;
   }
   const RowRange o = strip_rows(h).owned;
-  h->jpair_active = L<T>::jacobi_pair_ok(h);    // (the planner block plans the geometry of the kernel that will run)
-  L<T>::momentum(h, true, (int)((h->istep + 1) & 1), o.first, o.last);
-  h->jpair_active = false;
+  L<T>::momentum(h, true, (int)((h->istep + 1) & 1), L<T>::plan_for_tm(h), o.first, o.last);    // (the planner block plans the geometry of the kernel that will run)
 }
-// the ten sweeps of a middle step on all stored rows
+// the sweeps of a middle step on all stored rows: batch_jacobi (runtime/schedule.h), in uniform chunks where the pair kernel does not apply
 template <typename T>
-void tm5_jacobi(vof2d_ctx* h, int par) {
-  if (L<T>::jacobi_pair_ok(h)) {
-    // jacobi_iters / 10 launches of ten sweeps each, like batch_jacobi (an odd count leaves the host's view of the p / pt
-    // pair swapped: the exchange graphs are keyed by it)
-    h->jpair_active = true;
-    for (int j = 0; j < h->d.jacobi_iters / 10; ++j) {
-      L<T>::jacobi_pair(h, fP, fPT, par);
-      swap_P(h);
-    }
-    h->jpair_active = false;
-  } else {
-    jacobi_n<T>(h, h->d.jacobi_iters, false, -1);
-  }
-}
+void tm5_jacobi(vof2d_ctx* h, int par) { batch_jacobi<T>(h, par, -1); }
 // k_tm on one part of the owned rows (runtime/rows.h); the launch of the body carries the planner block
 template <typename T>
 void tm5_tm(vof2d_ctx* h, int64_t istep, int part) {
   const PartRows pr = part_rows(strip_rows(h), part);
   const bool y_first = (istep % 2 == 0);
-  h->jpair_active = L<T>::jacobi_pair_ok(h);
-  if (!pr.body.empty()) L<T>::tm(h, y_first, false, (int)((istep + 1) & 1), pr.body.first, pr.body.last);
+  const PlanFor plan_for = L<T>::plan_for_tm(h);
+  if (!pr.body.empty()) L<T>::tm(h, y_first, false, (int)((istep + 1) & 1), plan_for, fRHS, pr.body.first, pr.body.last);
   // both bands in ONE launch, in short chunks (a pair's march is its rows + 14 steps whatever its rows: the bands are
   // what the send / recv group waits for -- 8192-wide interior strip of 8: two launches of 18-row chunks 56 + 69 us)
   const RowRange b1 = pr.band_lo.empty() ? pr.band_hi : pr.band_lo, b2 = pr.band_lo.empty() ? kNoRows : pr.band_hi;
-  if (!b1.empty()) L<T>::tm(h, y_first, false, -1, b1.first, b1.last, kTmBandRows, b2.first, b2.last);
-  h->jpair_active = false;
+  if (!b1.empty()) L<T>::tm(h, y_first, false, -1, plan_for, fRHS, b1.first, b1.last, kTmBandRows, b2.first, b2.last);
 }
 // one middle step with its exchange: the edge bands on the communication stream in front of the send / recv group,
 // the other rows on the compute stream beside them (launches of k_tm on disjoint rows read the old arrays and write
@@ -238,10 +222,7 @@ int enqueue_mid_step5(vof2d_ctx* h) {
   tm5_jacobi<T>(h, (int)(h->istep & 1));
   HIPCHK(h, hipEventRecord(h->ev_fork[1], h->stream));
   HIPCHK(h, hipStreamWaitEvent(h->cstream, h->ev_fork[1], 0));
-  hipStream_t st = h->stream;
-  h->stream = h->cstream;
-  tm5_tm<T>(h, h->istep, 1);
-  h->stream = st;
+  { StreamScope on(h, h->cstream); tm5_tm<T>(h, h->istep, 1); }
   if ((rc = comm_post(h, VOF_XCHG_F | VOF_XCHG_US | VOF_XCHG_VS | VOF_XCHG_RHS | VOF_XCHG_P, /*f_in_twin=*/true, 1, /*s_in_alt=*/true, /*on_cstream=*/true, /*shallow=*/true))) return rc;
   tm5_tm<T>(h, h->istep, 2);
   swap_F(h);
@@ -293,6 +274,15 @@ int capture_exchange_or_switch_off(vof2d_ctx* h, hipGraphExec_t* slot, int* form
 
 // the kernels of mode 5 need: two-column tiles whose lanes are stored or skipped together, square cells or not (k_jacobi_pair
 // falls back to two k_jacobi_tb launches), the fused transport and its virtual ghosts
+// plan_step for the steps of a strip with their exchanges.  The difference: a captured step runs lean with the boundary launch
+// left out wherever the knob says so, whatever the transport (enqueue_step_exchange) -- virt does not ask for a full domain
+// or the fused transport as plan_step's does.  The steps of mode 5 and of vof_step_tm_piece are of this kind too, captured or
+// not (graphs = true): both entry points have seen to it that nothing is dirty.
+StepPlan strip_step_plan(const vof2d_ctx* h, bool graphs) {
+  StepPlan p = plan_step(h->state, step_caps(h, graphs));
+  p.virt = p.captured && h->virtual_ghosts;
+  return p;
+}
 bool mode5_ok(const vof2d_ctx* h) {
   return h->fuse_transport && h->tb >= 5 && h->d.jacobi_iters % 5 == 0 && h->d.jacobi_iters >= 5 && h->g.nx >= 16;
 }
@@ -303,7 +293,7 @@ int step_exchange_mode5(vof2d_ctx* h, int64_t nsteps) {
   int rc;
   if (!mode5_ok(h)) return fail(h, VOF_ESTATE, "overlap mode 5 needs the fused transport and five-sweep Jacobi launches");
   if (nsteps == 0) return VOF_OK;
-  if (h->f_ghosts_dirty || h->uv_ghosts_dirty || h->xchg_steps == 0) {
+  if (!clean_ghosts(h->state) || h->xchg_steps == 0) {
     // the first step after set_init_F / set_field (the reference's intermediate set_BC calls), and the first of a
     // communicator (RCCL connects on first use): a step of mode 1
     if ((rc = vof_step_exchange(h, 1, 1))) return rc;
@@ -343,7 +333,7 @@ int step_exchange_mode5(vof2d_ctx* h, int64_t nsteps) {
   DISPATCH_T(h, rc = enqueue_tail_step5<double>(h), rc = enqueue_tail_step5<float>(h));
   if (rc) return rc;
   h->xchg_steps += 1;
-  h->ghosts_virtual = h->virtual_ghosts != 0;
+  finish_step(h->state, strip_step_plan(h, true));   // (nothing was dirty: the first step of the call saw to that)
   return ensure_ok(h);
 }
 
@@ -359,10 +349,9 @@ int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
   for (int64_t s = 0; s < nsteps; ++s) {
     // the captured step leaves the ghost cells virtual (if the handle does that at all); every other
     // way through this loop wants them settled first
-    const bool captured_path = want_graph && h->xchg_graph && h->xchg_steps > 0 && !h->f_ghosts_dirty && !h->uv_ghosts_dirty;
-    const bool virt = captured_path && h->virtual_ghosts;
-    if (!virt) settle_ghosts(h);
-    h->istep += 1;
+    const StepPlan p = strip_step_plan(h, want_graph && h->xchg_graph && h->xchg_steps > 0);
+    if (!p.virt) settle_ghosts(h);
+    h->istep += 1;   // (behind settle_ghosts here, in front of it in step_loop: settle_ghosts does not look at istep)
     const int par = (int)(h->istep & 1), ori = ori_F(h);
     int rc;
     // The first step of a communicator runs eagerly: RCCL sets its peer connections up on first
@@ -373,7 +362,7 @@ int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
     // Two mode-4 steps per graph launch (a graph launch leaves ~9 us of idle queue behind it, see step.h):
     // only once both single-step graphs of this handle exist, i.e. this RCCL has shown that it can be
     // captured; two steps return the F / twin pair and the parity to where they were.
-    if (captured_path && overlap == 4 && h->xchg_pair && virt && nsteps - s >= 2 && G.xchg[par][4][ori] && G.xchg[par ^ 1][4][ori ^ 1]) {
+    if (p.captured && overlap == 4 && h->xchg_pair && p.virt && nsteps - s >= 2 && G.xchg[par][4][ori] && G.xchg[par ^ 1][4][ori ^ 1]) {
       if (!G.xchg2[par][ori] &&
           (rc = capture_exchange_or_switch_off(h, &G.xchg2[par][ori], &h->xchg_pair, "two steps + exchanges", "one step per launch (those graphs are known to work)", [&] {
              const int r2 = one_step();
@@ -387,11 +376,11 @@ int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
         s += 1;
         h->xchg_steps += 2;
         h->xchg_graph_steps += 2;
-        h->ghosts_virtual = virt;
+        finish_step(h->state, p);
         continue;
       }
     }
-    if (captured_path) {
+    if (p.captured) {
       hipGraphExec_t& exec = G.xchg[par][overlap][ori];
       if (!exec && (rc = capture_exchange_or_switch_off(h, &exec, &h->xchg_graph, "step + exchanges", "eager", one_step))) return rc;
       if (exec) {
@@ -399,7 +388,7 @@ int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
         if (overlap == 4) swap_F(h);   // the fused transport swaps the F / twin pair once per step
         h->xchg_steps += 1;
         h->xchg_graph_steps += 1;
-        h->ghosts_virtual = virt;
+        finish_step(h->state, p);
         continue;
       }
     }

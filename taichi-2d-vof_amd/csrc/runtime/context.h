@@ -1,8 +1,8 @@
 // runtime/context.h -- field ids, constants folded like the reference does, the handle (vof2d_ctx), error helpers
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h (and diag.h in the diagnostic build).  Everything
-// here has internal linkage.
+// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h (and diag.h in the diagnostic
+// build).  Everything here has internal linkage.
 #pragma once
 #include <vector>
 
@@ -20,6 +20,7 @@
 
 #include "../../../include/vof2d.h"
 #include "../vof2d_kernels.h"
+#include "state.h"
 
 using namespace vof;
 
@@ -27,7 +28,6 @@ struct RcclId { char internal[VOF_COMM_ID_BYTES]; };  // ncclUniqueId, passed by
 
 namespace {
 
-enum FieldId { fF = 0, fF2, fU, fV, fP, fPT, fUS, fVS, fMX, fMY, fKAPPA, fRHO, fNU, fRHS, NFIELDS };
 const char* const kFieldNames[NFIELDS] = {"F", "F2", "u", "v", "p", "pt", "u_star", "v_star",
                                           "mx", "my", "kappa", "rho", "nu", "rhs"};
 
@@ -266,9 +266,6 @@ struct vof2d_ctx {
   hipEvent_t ev_gas = nullptr;           // ... recorded behind the copy
   bool gas_pending = false;              // a count of the current F is in flight or has landed, not yet read
   bool tm_broken = false;    // the k_tm batch graphs could not be captured: the other form stays
-  bool alt_dirty = false;    // a verb or a field write left something in mx / my (the second u*, v* pair of the k_tm forms): cleared at the head of a strip call (tm5_head)
-  bool ahead = false;        // u*, v*, rhs hold the predictor of step istep + 1 (the chained k_tm batches; settle_ahead)
-  bool tm_rhs_alt = false;   // the k_tm launches being enqueued write rhs into the kappa array (the caller swaps the views)
   int64_t tm_chained = 0;    // k_tm batches that started without a k_momentum launch (counter "tm_chained_batches")
   int jpair = 1;             // knob "jacobi_pair": the k_tm batch graphs run each two five-sweep launches as one k_jacobi_pair launch
   int jpair_rows = 0;        // rows per pair chunk (0 = one residency round of pairs)
@@ -279,8 +276,6 @@ struct vof2d_ctx {
   // against round 4's rows)
   int pair_slow10 = 32;
   int tb_slow10 = 20;
-  bool jpair_active = false; // the launches being enqueued are k_jacobi_pair's (tb_plan describes their geometry)
-  bool jpair_captured = false;   // the k_tm batch graphs the handle holds contain k_jacobi_pair launches
   int64_t pair_launches = 0; // k_jacobi_pair launches replayed (counter "pair_launches")
   TuneState tune;
   int64_t tm_steps = 0;      // steps replayed from k_tm batch graphs (counter "tm_steps")
@@ -291,11 +286,7 @@ struct vof2d_ctx {
   int64_t halves_steps = 0;       // steps replayed from them (counter "halves_steps")
   std::vector<hipEvent_t> hev;
   bool batching = true;         // false after a failed capture of a batch: one graph launch per step from then on (build_step_batches)
-  int next_phase = 0;
-  bool f_ghosts_dirty = true;  // F's ghost cells may not satisfy set_BC (after set_init_F / from_numpy / a single verb)
-  bool uv_ghosts_dirty = false; // u / v were written without a set_BC since (update_uv verb, from_numpy): their ghost cells are not mirror images
-  bool ghosts_virtual = false; // the last fused step skipped its set_BC launch: the ghost cells in memory are stale
-                               // (k_momentum forms the ones it reads; everything else goes through settle_ghosts)
+  FieldState state;             // what the fields and ghost cells hold, the phase order (runtime/state.h)
   void* vis = nullptr;      // scratch for the display fields (vof_get_vis_field / vof_interp_velocity)
   size_t vis_bytes = 0;
   // built-in in-situ profiler (vof_profile_steps): every launch carries a start/stop event pair
@@ -347,5 +338,15 @@ int field_id(const char* name) {
 }
 
 template <typename T> T* F_(vof2d_ctx* h, int id) { return reinterpret_cast<T*>(h->fld[id]); }
+
+// The launches enqueued while one of these lives go to `st` instead of the handle's stream (a chain of the batch graphs,
+// the communication stream of a strip); the handle's stream is back on every way out of the scope.
+struct StreamScope {
+  vof2d_ctx* const h;
+  hipStream_t const saved;
+  StreamScope(vof2d_ctx* h_, hipStream_t st) : h(h_), saved(h_->stream) { h->stream = st; }
+  ~StreamScope() { h->stream = saved; }
+  StreamScope(const StreamScope&) = delete;
+};
 
 }  // namespace

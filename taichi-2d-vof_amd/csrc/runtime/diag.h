@@ -10,11 +10,9 @@ namespace {
 template <int ABL>
 void dbg_pair(vof2d_ctx* h, int plan) {
   typedef double T; constexpr int V = VecWidth<T>::V;
-  h->jpair_active = true;
   int ntt = 0;
   const int R = L<T>::jacobi_pair_geom(h, ntt);
-  const TbPlan tp = L<T>::tb_plan(h, plan ? (int)(h->istep & 1) : -1);
-  h->jpair_active = false;
+  const TbPlan tp = L<T>::tb_plan(h, plan ? (int)(h->istep & 1) : -1, PlanFor::kJacobiPair);
   const unsigned pairs = tp.masks ? (unsigned)tp.waves : (unsigned)(((h->g.ihi - h->g.ilo + R) / R) * ntt);
   launch_block(h, kJacobiPair, k_jacobi_pair<T, V, 5, true, ABL>, dim3(pairs), 128u, 0, h->g, L<T>::C(h), (const T*)F_<T>(h, fP),
                (const T*)F_<T>(h, fRHS), F_<T>(h, fPT), R, ntt, tp, h->g.ilo, h->g.ihi);
@@ -142,11 +140,8 @@ extern "C" int vof_debug_time_overlap(vof2d_handle h, int32_t mode, int32_t reps
     HIPCHK(h, hipEventRecord(e0, st));
     HIPCHK(h, hipStreamWaitEvent(s_tm, e0, 0));
     HIPCHK(h, hipStreamWaitEvent(s_j, e0, 0));
-    h->stream = s_tm;
-    if (yf) dbg_tm<true, 0>(h); else dbg_tm<false, 0>(h);
-    h->stream = s_j;
-    dbg_pair<0>(h, 0);
-    h->stream = st;
+    { StreamScope on(h, s_tm); if (yf) dbg_tm<true, 0>(h); else dbg_tm<false, 0>(h); }
+    { StreamScope on(h, s_j); dbg_pair<0>(h, 0); }
     HIPCHK(h, hipEventRecord(ea, s_tm));
     HIPCHK(h, hipEventRecord(eb, s_j));
     HIPCHK(h, hipStreamWaitEvent(st, ea, 0));

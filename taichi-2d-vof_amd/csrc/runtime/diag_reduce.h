@@ -1,7 +1,7 @@
 // runtime/diag_reduce.h -- vof_diagnostics and vof_step_diag: the handle's buffers, the launch of k_diag + k_diag_finish, the stepping loop that records rows
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, graphs.h, schedule.h, multigrid.h, step.h, diag_reduce.h, comm.h, selftest.h.  Everything here has
+// context.h (with state.h), launches.h, graphs.h, schedule.h, multigrid.h, step.h, diag_reduce.h, comm.h, selftest.h.  Everything here has
 // internal linkage.  (runtime/diag.h is something else: the vof_debug_* entry points of the diagnostic build.)
 #pragma once
 #include "step.h"

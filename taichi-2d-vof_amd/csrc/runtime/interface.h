@@ -1,7 +1,7 @@
 // runtime/interface.h -- vof_interface: the handle's buffers, the launches of k_iface (count), k_iface_scan, k_iface (emit), the copies out
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, graphs.h, schedule.h, multigrid.h, step.h, diag_reduce.h, interface.h, comm.h, selftest.h.  Everything
+// context.h (with state.h), launches.h, graphs.h, schedule.h, multigrid.h, step.h, diag_reduce.h, interface.h, comm.h, selftest.h.  Everything
 // here has internal linkage.
 #pragma once
 #include "diag_reduce.h"

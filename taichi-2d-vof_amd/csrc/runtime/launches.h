@@ -1,7 +1,7 @@
 // runtime/launches.h -- chunk-length heuristics and L<T>: one launch wrapper per kernel (grid shape, chunk length, arguments), through the single launch() helper
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, schedule.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h (with state.h), launches.h, schedule.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
 #include "context.h"
 
@@ -112,6 +112,9 @@ inline bool buffer_stores_ok(const vof2d_ctx* h) {
 // (round 5, before the branch-free division tier: ties at 4096^2, hence 20 M then); 5120^2 0.78-0.83 / 0.89-0.92, 8192^2 1.67-1.71 / 2.17-2.20
 constexpr long kTmAlwaysCells = 16000000L;
 constexpr long kTbPlanWaves = 16384;   // waves of a k_jacobi_tb launch the work plan can describe
+// which kernel a work plan is for: the step's Jacobi launches are k_jacobi_tb's, or (the k_tm forms where the handle allows:
+// jacobi_pair_ok) k_jacobi_pair's -- the tile columns, chunk lengths and wave counts differ (L<T>::tb_plan)
+enum class PlanFor { kJacobiTb, kJacobiPair };
 enum KernelId { kMomentum = 0, kSetBC, kJacobi, kJacobiTB, kCorrect, kFctX, kFctY, kNormals, kKappa, kPredictor,
                 kRhs, kOther, kTransport, kJacobiPair, kTM, kTMUV, kCgApply, kCgUpdate, kCgResidual, kCgFinish, kMgSmooth, kMgRestrict, kMgProlong, kMgCoarseBlock, NKERNELS };
 static_assert(NKERNELS <= 24, "vof2d_ctx::prof_sum_ms / prof_cnt");
@@ -191,10 +194,11 @@ struct L {
   }
   // fused normals + kappa + predictor + rhs (vof_step only)
   // rows [first, last] of the predictor and the rhs (last < first: all computable rows)
-  static void momentum(vof2d_ctx* h, bool virt = false, int adapt_par = -1, int first = 1, int last = 0) {
+  // plan_for: the kernel the step's Jacobi launches are (the planner block plans its geometry)
+  static void momentum(vof2d_ctx* h, bool virt, int adapt_par, PlanFor plan_for, int first = 1, int last = 0) {
     const int ntt = MomentumGeom<V>::tiles(h->g.ny);
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
-    const TbPlan tp = tb_plan(h, adapt_par);   // (one extra block: the planner wave)
+    const TbPlan tp = tb_plan(h, adapt_par, plan_for);   // (one extra block: the planner wave)
     dispatch([&](auto BS) {
       // one residency round while that keeps the chunks short (strips, small grids); on large grids
       // several rounds of 14-row chunks beat one round of long ones (4096^2: 184 vs 195 us, 8192^2:
@@ -239,6 +243,8 @@ struct L {
     //  chains; knob values 1 and 2 are the same now)
     return h->jpair >= 1 && square_cells(h) && h->tb >= 5 && h->d.jacobi_iters % 10 == 0;
   }
+  // the Jacobi kernel of the k_tm forms (the batches of a full domain, the middle steps of overlap mode 5): what their plans are for
+  static PlanFor plan_for_tm(vof2d_ctx* h) { return jacobi_pair_ok(h) ? PlanFor::kJacobiPair : PlanFor::kJacobiTb; }
   static bool pair_buffer_stores(const vof2d_ctx* h) { return buffer_stores_ok(h) && (h->buf_stores & 2); }
   static int jacobi_pair_geom(vof2d_ctx* h, int& ntt) {
     ntt = JacobiPairGeom<V, 5>::tiles(h->g.ny);
@@ -252,7 +258,7 @@ struct L {
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
     int ntt = 0;
     const int R = jacobi_pair_geom(h, ntt);
-    const TbPlan tp = tb_plan(h, adapt_par);
+    const TbPlan tp = tb_plan(h, adapt_par, PlanFor::kJacobiPair);
     const unsigned pairs = tp.masks ? (unsigned)tp.waves : (unsigned)(((last - first + R) / R) * ntt);
     dispatch([&](auto BS) {
       launch_block(h, kJacobiPair, k_jacobi_pair<T, V, 5, BS()>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, src),
@@ -260,14 +266,14 @@ struct L {
     }, pair_buffer_stores(h));
   }
   // the work plan of the step's five-sweep launches (see tb_make_plan): active on parity-keyed step
-  // sequences (adapt_par = istep & 1), square or not, up to TB_COLS tile columns
-  static TbPlan tb_plan(vof2d_ctx* h, int adapt_par) {
+  // sequences (adapt_par = istep & 1), square or not, up to TB_COLS tile columns; planned for the kernel that will read it
+  static TbPlan tb_plan(vof2d_ctx* h, int adapt_par, PlanFor plan_for) {
     TbPlan tp{nullptr, nullptr, 0, 0, 0, 0, 0};
     if (adapt_par < 0 || !h->tb_adapt || h->tb < 5 || h->tb_rows > 0) return tp;
     int ntt = 0;
     int R;
     long waves;
-    if (h->jpair_active) {   // the step's Jacobi launches are k_jacobi_pair's: the plan's "waves" are pairs on 108-column tiles (jacobi_pair_geom); a plan is only ever read by the kernel it was planned for -- enqueue_tm_head, tm5_head
+    if (plan_for == PlanFor::kJacobiPair) {   // the plan's "waves" are pairs on 108-column tiles (jacobi_pair_geom); a plan is only ever read by the kernel it was planned for -- enqueue_tm_head, tm5_head
       R = jacobi_pair_geom(h, ntt);
       waves = (long)((h->g.ihi - h->g.ilo + R) / R) * ntt;
     } else {
@@ -278,7 +284,7 @@ struct L {
     tp.masks = h->d_tbmask;
     tp.plan = h->d_tbmask + 2 * TB_BANDS * (TB_COLS / 64);
     tp.ntt = ntt; tp.R = R; tp.waves = (int)waves; tp.par = adapt_par;
-    tp.slow10 = h->jpair_active ? h->pair_slow10 : h->tb_slow10;   // (what a row of a reported band costs: per kernel)
+    tp.slow10 = plan_for == PlanFor::kJacobiPair ? h->pair_slow10 : h->tb_slow10;   // (what a row of a reported band costs: per kernel)
     return tp;
   }
   // TS sweeps src -> dst on rows [first, last] (last < first: all computable rows).  RESID: the last sweep also reduces
@@ -292,7 +298,7 @@ struct L {
     int ntt = 0;
     const int R = jacobi_tb_plan<TS, RESID>(h, sq, ntt);
     TbPlan tp{nullptr, nullptr, 0, 0, 0, 0, 0};
-    if (TS == 5 && !RESID) tp = tb_plan(h, adapt_par);
+    if (TS == 5 && !RESID) tp = tb_plan(h, adapt_par, PlanFor::kJacobiTb);
     // (with a plan the launch holds the waves of the whole grid's plan, whatever part of the rows it is for: every
     // wave takes the part of its planned chunk inside [first, last], or nothing)
     const unsigned all_blocks = blocks_rows(interior_rows(h), ntt, R);
@@ -352,11 +358,12 @@ struct L {
     const long R = (rows + chunks - 1) / chunks;
     return (int)(R < 16 ? 16 : (R > 96 ? 96 : R));
   }
-  // rows [first, last] and, in the same launch, [first2, last2]; store_uv: the last k_tm of a batch
-  static void tm(vof2d_ctx* h, bool y_first, bool store_uv, int adapt_par, int first = 1, int last = 0, int rows_forced = 0, int first2 = 1, int last2 = 0) {
+  // rows [first, last] and, in the same launch, [first2, last2]; store_uv: the last k_tm of a batch; rhs_id: the array the
+  // next step's rhs goes to (fRHS, or fKAPPA where the caller alternates the two: enqueue_steps_tm)
+  static void tm(vof2d_ctx* h, bool y_first, bool store_uv, int adapt_par, PlanFor plan_for, int rhs_id, int first = 1, int last = 0, int rows_forced = 0, int first2 = 1, int last2 = 0) {
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
     const int ntf = TmGeom<V>::tiles(h->g.ny);
-    const TbPlan tp = tb_plan(h, adapt_par);
+    const TbPlan tp = tb_plan(h, adapt_par, plan_for);
     // pair chunks: a whole number of residency rounds, just filled (6 pairs per CU: 24 KB of LDS each) -- a launch that needs a
     // little more than k rounds pays for k + 1 --, as many rounds as keep the chunks near 50 rows (one round of 100-row
     // chunks: every step of every pair takes 3.3 us instead of 1.9).  4096^2, 112-column tiles, us per launch: 40 rows
@@ -367,7 +374,7 @@ struct L {
       const unsigned pairs = (unsigned)((((last - first + R) / R) + (last2 >= first2 ? (last2 - first2 + R) / R : 0)) * ntf) + (tp.masks ? 1u : 0u);
       launch_block(h, UV() ? kTMUV : kTM, k_tm<T, V, YF(), UV(), BS()>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
                    (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
-                   F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, h->tm_rhs_alt ? fKAPPA : fRHS), h->d_courant, R, tp, first, last, first2, last2);
+                   F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, rhs_id), h->d_courant, R, tp, first, last, first2, last2);
     }, y_first, store_uv, buffer_stores_ok(h) && (h->buf_stores & 4));
   }
   // ---- conjugate gradients (kernels/cg.h)

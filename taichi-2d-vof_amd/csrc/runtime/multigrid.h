@@ -1,7 +1,7 @@
 // runtime/multigrid.h -- the hierarchy of vof_solve_p_mg, one V-cycle (enqueued, or captured once and replayed), the driver loop
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, graphs.h, schedule.h, multigrid.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h (with state.h), launches.h, graphs.h, schedule.h, multigrid.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
 #include "schedule.h"
 

@@ -1,7 +1,7 @@
 // runtime/schedule.h -- the per-step launch schedule (2dvof.py:506-528): sweeps, phases, the fused full-domain step, ghost-cell bookkeeping, graph housekeeping
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
 #include "graphs.h"
 #include "rows.h"
@@ -132,7 +132,7 @@ void enqueue_phase(vof2d_ctx* h, int phase, int64_t istep, bool merge_bc = false
   if (phase == 0) {
     // cal_nu_rho (:513) is folded into its consumers: rho/nu = f(F[i,j]) recomputed per cell;
     // :514, :517 and the (sweep-invariant, BC-independent) rhs of :239-241 in one pass
-    L<T>::momentum(h, virt, mg ? -1 : adapt_par);     // virt: the previous step's set_BC launch was left out (see enqueue_step)
+    L<T>::momentum(h, virt, mg ? -1 : adapt_par, PlanFor::kJacobiTb);     // virt: the previous step's set_BC launch was left out (see enqueue_step)
     if (mg) mg_enqueue_step_solve<T>(h, mg->cycles, mg->criterion);
     else jacobi_n<T>(h, h->d.jacobi_iters, false, adapt_par);  // :521-522
     if (!lean) L<T>::template set_bc<BC_P | BC_F>(h);  // p part of :525 / :528; F part of :518 (first step)
@@ -161,7 +161,7 @@ void enqueue_step(vof2d_ctx* h, int64_t istep, bool lean = false, bool virt = fa
     // wall velocity is zero, update_uv overwrites what p's ghosts would enter, the Jacobi stencil
     // multiplies them by zero coefficients), and that kernel forms them from the interior cells
     // itself.  Whoever else looks at the fields goes through settle_ghosts first.
-    L<T>::momentum(h, virt, mg ? -1 : (int)(istep & 1));   // (no Jacobi launches behind it: no work plan to make)
+    L<T>::momentum(h, virt, mg ? -1 : (int)(istep & 1), PlanFor::kJacobiTb);   // (mg: no Jacobi launches behind it: no work plan to make)
     if (mg) mg_enqueue_step_solve<T>(h, mg->cycles, mg->criterion);
     else jacobi_n<T>(h, h->d.jacobi_iters, false, (int)(istep & 1));
     L<T>::transport(h, istep % 2 == 0);
@@ -273,11 +273,9 @@ bool enqueue_steps_halves(vof2d_ctx* h, int64_t first_step, int K) {
   auto all = [&](auto&& fn) {
     for (int p = 0; p < P; ++p) {
       if (p > 0 && n > 0) ok = ok && hipStreamWaitEvent(st[p], ev_done[(p - 1) * total + n - 1], 0) == hipSuccess;
-      h->stream = st[p];
-      fn(p == 0 ? 1 : s[p - 1] + 1, p == P - 1 ? nx : s[p], p == 0);
+      { StreamScope on(h, st[p]); fn(p == 0 ? 1 : s[p - 1] + 1, p == P - 1 ? nx : s[p], p == 0); }
       if (p < P - 1) ok = ok && hipEventRecord(ev_done[p * total + n], st[p]) == hipSuccess;
     }
-    h->stream = st[0];
     for (int p = 0; p < P - 1; ++p) s[p] -= kHalvesDrift;
     ++n;
   };
@@ -295,7 +293,7 @@ bool enqueue_steps_halves(vof2d_ctx* h, int64_t first_step, int K) {
       ok = ok && hipStreamWaitEvent(st[0], ev_plan[k - 1], 0) == hipSuccess;
     }
     const int n_mom = n;
-    all([&](int a, int b, bool first) { L<T>::momentum(h, true, first ? par : -1, a, b); });
+    all([&](int a, int b, bool first) { L<T>::momentum(h, true, first ? par : -1, PlanFor::kJacobiTb, a, b); });
     // ... and no chain reads the plan before the planner of ITS step has written it: chain 1's first Jacobi launch is
     // ordered behind chain 0's k_momentum by the chain edge, chains 2 .. only behind chain 1's k_momentum
     for (int p = 2; p < P; ++p) ok = ok && hipStreamWaitEvent(st[p], ev_done[n_mom], 0) == hipSuccess;
@@ -328,54 +326,40 @@ bool enqueue_steps_halves(vof2d_ctx* h, int64_t first_step, int K) {
 inline void swap_P(vof2d_ctx* h) { void* t = h->fld[fP]; h->fld[fP] = h->fld[fPT]; h->fld[fPT] = t; }
 // the step's Jacobi sweeps inside a batch: pairs of five-sweep launches as k_jacobi_pair where the handle allows (each
 // leaves its result in the other array of the p / pt pair: the host's view is swapped along, an even number of times
-// per batch of an even number of steps), else k_jacobi_tb launches ending in fld[fP]
+// per batch of an even number of steps; an odd count per step -- the middle steps of a strip in overlap mode 5 -- leaves it
+// swapped: the exchange graphs are keyed by it), else the k_jacobi_tb launches of jacobi_n, ending in fld[fP], on the work plan
+// of parity tb_par (-1: uniform chunks)
 template <typename T>
-void batch_jacobi(vof2d_ctx* h, int par) {
-  const int nj = h->d.jacobi_iters / 5;
-  if (L<T>::jacobi_pair_ok(h)) {
-    for (int j = 0; j < nj / 2; ++j) {
-      L<T>::jacobi_pair(h, fP, fPT, par);
-      swap_P(h);
-    }
-    return;
-  }
-  int cur = fP, oth = fPT;
-  for (int j = 0; j < nj; ++j) {
-    L<T>::template jacobi_tb<5>(h, cur, oth, par);
-    const int t = cur; cur = oth; oth = t;
+void batch_jacobi(vof2d_ctx* h, int par, int tb_par) {
+  if (!L<T>::jacobi_pair_ok(h)) return jacobi_n<T>(h, h->d.jacobi_iters, false, tb_par);
+  for (int j = 0; j < h->d.jacobi_iters / 10; ++j) {
+    L<T>::jacobi_pair(h, fP, fPT, par);
+    swap_P(h);
   }
 }
 template <typename T>
 void enqueue_steps_tm(vof2d_ctx* h, int64_t first_step, int K) {
-  h->jpair_active = L<T>::jacobi_pair_ok(h);
-  h->jpair_captured = h->jpair_active;
-  h->tm_rhs_alt = true;
+  const PlanFor plan_for = L<T>::plan_for_tm(h);
   for (int k = 0; k < K; ++k) {
     const int64_t istep = first_step + k;
     const int par = (int)(istep & 1);
-    batch_jacobi<T>(h, par);
-    L<T>::tm(h, istep % 2 == 0, /*store_uv=*/k == K - 1, par ^ 1);
+    batch_jacobi<T>(h, par, par);
+    L<T>::tm(h, istep % 2 == 0, /*store_uv=*/k == K - 1, par ^ 1, plan_for, /*rhs_id=*/fKAPPA);   // (swap_SR alternates rhs with the kappa array)
     swap_SR(h);
     swap_F(h);
   }
-  h->tm_rhs_alt = false;
-  if (h->jpair_active && ((K * (h->d.jacobi_iters / 10)) & 1)) swap_P(h);   // (never: K is even)
-  h->jpair_active = false;
+  if (plan_for == PlanFor::kJacobiPair && ((K * (h->d.jacobi_iters / 10)) & 1)) swap_P(h);   // (never: K is even)
   // (K swaps, an even number: the host's view of the pairs is back where it was)
 }
 // the one k_momentum launch in front of the first batch of a chain (its planner block plans the geometry of the Jacobi
 // kernel the batch will run)
 template <typename T>
-void enqueue_tm_head(vof2d_ctx* h, int par) {
-  h->jpair_active = L<T>::jacobi_pair_ok(h);
-  L<T>::momentum(h, true, par);
-  h->jpair_active = false;
-}
+void enqueue_tm_head(vof2d_ctx* h, int par) { L<T>::momentum(h, true, par, L<T>::plan_for_tm(h)); }
 // The handle leaves the chained k_tm batches (a field is read or written from outside, a verb, a parameter): the
 // reference's u_star, v_star, rhs after the last step are in the other set of arrays -- copy them into the host's view.
 int settle_ahead(vof2d_ctx* h) {
-  if (!h->ahead) return VOF_OK;
-  h->ahead = false;
+  if (!h->state.ahead) return VOF_OK;
+  h->state.ahead = false;
   // exactly the cells the predictor writes (:206-233, :238-243) -- u* on i in [2, nx], v* on j in [2, ny], rhs on the
   // interior: everything else of the other set is whatever a verb left in mx, my, kappa
   auto copy = [&](int dst, int src, int i0, int j0) -> hipError_t {
@@ -403,19 +387,18 @@ int ensure_ok(vof2d_ctx* h) {
   do { if ((h)->d.dtype == VOF_F64) { expr_d; } else { expr_f; } } while (0)
 #define DISPATCH_B(h, expr_d, expr_f) ((h)->d.dtype == VOF_F64 ? (expr_d) : (expr_f))
 
-// true if the next vof_step runs the fused full-domain schedule (k_momentum, 2 x k_jacobi_tb,
-// k_transport) that leaves the ghost cells virtual
-bool step_leaves_ghosts_virtual(const vof2d_ctx* h) {
-  return h->g.wall_lo && h->g.wall_hi && h->fuse_transport &&
-         h->virtual_ghosts && !h->f_ghosts_dirty && !h->uv_ghosts_dirty;
+// what plan_step (runtime/state.h) asks of the handle; its `virt` is true if the next step runs the fused full-domain
+// schedule (k_momentum, 2 x k_jacobi_tb, k_transport) that leaves the ghost cells virtual
+inline StepCaps step_caps(const vof2d_ctx* h, bool graphs) {
+  return {h->g.wall_lo && h->g.wall_hi, h->fuse_transport != 0, h->virtual_ghosts != 0, graphs};
 }
 // Every entry point that reads or writes fields other than through the fused step calls this
 // first: if the last step skipped its set_BC launch, run it now (u, v, F with its twin, p).
 void settle_ghosts(vof2d_ctx* h) {
   (void)settle_ahead(h);
-  if (!h->ghosts_virtual) return;
+  if (!h->state.ghosts_virtual) return;
   DISPATCH_T(h, L<double>::set_bc<BC_ALL>(h), L<float>::set_bc<BC_ALL>(h));
-  h->ghosts_virtual = false;
+  h->state.ghosts_virtual = false;
 }
 
 int copy_rows_host(vof2d_ctx* h, int id, int g0, int g1, void* host, size_t nbytes, bool to_host) {

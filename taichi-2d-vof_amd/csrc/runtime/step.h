@@ -2,7 +2,7 @@
 // handle runs, the batches, and the three ways a step is run (inside a batch, from its own graph, eagerly)
 //
 // Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h, launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
 #pragma once
 #include "schedule.h"
 #include "multigrid.h"
@@ -133,7 +133,7 @@ void build_step_batches(vof2d_ctx* h, int variant) {
   }
 }
 
-// ---- the three ways vof_step runs a step (step_n picks)
+// ---- the three ways vof_step runs a step (step_loop and step_n pick)
 // 1. Inside a batch: as many of the `remaining` steps as the largest batch graph that fits holds, one graph launch.  An
 // even number of steps leaves the F / twin pair and the host's view of it where they were.  Parity and orientation flip
 // together from step to step, so two (parity, orientation) pairs are reachable; the batch graphs of both are captured the
@@ -165,16 +165,17 @@ int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
     if (variant) {
       // the k_tm batches chain: each ends with the next step's predictor in place (enqueue_steps_tm); only the first
       // after anything else needs its k_momentum launched in front
-      if (h->ahead) h->tm_chained += 1;
+      if (h->state.ahead) h->tm_chained += 1;
       else DISPATCH_T(h, enqueue_tm_head<double>(h, par), enqueue_tm_head<float>(h, par));
-      h->ahead = true;
-    } else h->ahead = false;
+      h->state.ahead = true;
+    } else h->state.ahead = false;
     if (hipGraphLaunch(GB[b][par][ori], h->stream) != hipSuccess) return fail(h, VOF_EHIP, "hipGraphLaunch of a step batch");
     if (time_it) {
       if (hipEventRecord(t.ev[2 * t.n + 1], h->stream) == hipSuccess) t.n += 1;
       else (void)hipGetLastError();   // (the batch ran: this timing is lost, the steps are not)
     }
-    if (variant) { h->tm_steps += K; if (h->jpair_captured) h->pair_launches += (int64_t)K * (h->d.jacobi_iters / 10); }
+    // (what jacobi_pair_ok looks at changes through vof_set_param only, which drops the graphs: it says what they were captured with)
+    if (variant) { h->tm_steps += K; if (DISPATCH_B(h, L<double>::jacobi_pair_ok(h), L<float>::jacobi_pair_ok(h))) h->pair_launches += (int64_t)K * (h->d.jacobi_iters / 10); }
     else if (h->halves_captured[b]) h->halves_steps += K;
     *ran = K;
     return VOF_OK;
@@ -184,6 +185,7 @@ int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
 // 2. From the step's own graph, captured on first use.  Graphs bake the field pointers in: one per (parity, which buffer
 // of the F / twin pair holds F).  The two-kernel transport swaps the pair twice per step, the fused one once.
 int run_step_graph(vof2d_ctx* h, bool virt) {
+  h->state.ahead = false;   // (this step forms its own predictor, into the host's view of u*, v*, rhs)
   hipGraphExec_t& exec = h->graphs.step[(int)(h->istep & 1)][ori_F(h)];
   int rc;
   if (!exec && (rc = capture_or_fail(h, /*upload=*/true, &exec, "the step graph", [&] {
@@ -197,40 +199,39 @@ int run_step_graph(vof2d_ctx* h, bool virt) {
 // 3. Eagerly, launch by launch: the first step after set_init_F / from_numpy / a single verb (lean = false: the schedule with
 // the reference's intermediate set_BC calls), the one step after u / v were written without a set_BC (stored ghost cells
 // must be read as they are, a captured step holds the kernels of the regular schedule), and every step of a handle
-// created with VOF_FLAG_NO_GRAPH.
-int run_step_eager(vof2d_ctx* h, bool lean, bool virt) {
-  DISPATCH_T(h, enqueue_step<double>(h, h->istep, lean, virt), enqueue_step<float>(h, h->istep, lean, virt));
+// created with VOF_FLAG_NO_GRAPH.  mg: the steps of vof_step_mg.
+int run_step_eager(vof2d_ctx* h, bool lean, bool virt, const StepMg* mg) {
+  h->state.ahead = false;   // (see run_step_graph)
+  DISPATCH_T(h, enqueue_step<double>(h, h->istep, lean, virt, mg), enqueue_step<float>(h, h->istep, lean, virt, mg));
   return ensure_ok(h);
 }
 
-// nsteps steps.  A step that starts with consistent F ghosts runs the lean schedule (full domains: k_momentum, 2 x
-// k_jacobi_tb, k_transport and no boundary launch -- virtual ghosts; strips: the two-kernel transport and one boundary
-// launch at the end).
-int step_n(vof2d_ctx* h, int64_t nsteps) {
-  const bool use_graph = !(h->d.flags & VOF_FLAG_NO_GRAPH);
+// nsteps steps of vof_step (mg == nullptr) or vof_step_mg: prologue and epilogue of a step from runtime/state.h.  A step that
+// starts with consistent F ghosts runs the lean schedule (full domains: k_momentum, 2 x k_jacobi_tb, k_transport and no boundary
+// launch -- virtual ghosts; strips: the two-kernel transport and one boundary launch at the end).  run_captured(plan, steps
+// left, &ran) is how a step of the handle's regular schedule runs: inside a batch graph that runs *ran steps, or (*ran left
+// 0) from the step's own graph.
+template <typename RunCaptured>
+int step_loop(vof2d_ctx* h, int64_t nsteps, bool use_graph, const StepMg* mg, RunCaptured&& run_captured) {
   for (int64_t s = 0; s < nsteps; ++s) {
     h->istep += 1;
-    const bool lean = !h->f_ghosts_dirty;
-    const bool virt = step_leaves_ghosts_virtual(h);
-    if (!virt) settle_ghosts(h);
-    const bool captured = use_graph && lean && !h->uv_ghosts_dirty;   // the handle's regular schedule: what the graphs hold
+    const StepPlan p = plan_step(h->state, step_caps(h, use_graph));
+    if (!p.virt) settle_ghosts(h);
     int rc, ran = 0;
-    if (captured && virt) {   // steady state of a full domain
-      if ((rc = run_step_batch(h, nsteps - s, &ran))) { h->istep -= 1; return rc; }
-      if (ran) {
-        h->istep += ran - 1;
-        s += ran - 1;
-        h->ghosts_virtual = true;
-        continue;
-      }
-    }
-    h->ahead = false;   // (this step forms its own predictor, into the host's view of u*, v*, rhs)
-    if ((rc = captured ? run_step_graph(h, virt) : run_step_eager(h, lean, virt))) return rc;
-    h->f_ghosts_dirty = false;
-    h->uv_ghosts_dirty = false;
-    h->ghosts_virtual = virt;
+    if ((rc = p.captured ? run_captured(p, nsteps - s, &ran) : run_step_eager(h, p.lean, p.virt, mg))) return rc;
+    if (ran) { h->istep += ran - 1; s += ran - 1; }
+    finish_step(h->state, p);   // (behind a batch: nothing was dirty, the ghost cells are virtual)
   }
   return VOF_OK;
+}
+int step_n(vof2d_ctx* h, int64_t nsteps) {
+  return step_loop(h, nsteps, !(h->d.flags & VOF_FLAG_NO_GRAPH), nullptr, [h](const StepPlan& p, int64_t remaining, int* ran) {
+    if (p.virt) {   // steady state of a full domain
+      if (const int rc = run_step_batch(h, remaining, ran)) { h->istep -= 1; return rc; }
+      if (*ran) return (int)VOF_OK;
+    }
+    return run_step_graph(h, p.virt);
+  });
 }
 
 // ---- vof_step_mg: the same three ways minus the batches, the step's sweeps replaced by `cycles` V-cycles (enqueue_step
@@ -238,6 +239,7 @@ int step_n(vof2d_ctx* h, int64_t nsteps) {
 // dropped when one of those changes (F and its twin apart: the slots are keyed by the orientation), and with every
 // other graph when a knob does (destroy_graphs).
 int run_step_mg_graph(vof2d_ctx* h, bool virt, const StepMg& mg) {
+  h->state.ahead = false;   // (see run_step_graph; settled in front of the loop: step_mg_n)
   GraphCache& G = h->graphs;
   void* key[NFIELDS];
   memcpy(key, h->fld, sizeof(key));
@@ -281,23 +283,9 @@ int step_mg_n(vof2d_ctx* h, int64_t nsteps, int cycles, int criterion, double* l
     // the handle back in the state every other entry point expects.
     (void)settle_ahead(h);
     const StepMg mg{cycles, criterion};
-    const bool use_graph = !(h->d.flags & VOF_FLAG_NO_GRAPH) && h->mg_graph;
-    for (int64_t s = 0; s < nsteps; ++s) {
-      h->istep += 1;
-      const bool lean = !h->f_ghosts_dirty;
-      const bool virt = step_leaves_ghosts_virtual(h);
-      if (!virt) settle_ghosts(h);
-      const bool captured = use_graph && lean && !h->uv_ghosts_dirty;
-      if (captured) rc = run_step_mg_graph(h, virt, mg);
-      else {
-        DISPATCH_T(h, enqueue_step<double>(h, h->istep, lean, virt, &mg), enqueue_step<float>(h, h->istep, lean, virt, &mg));
-        rc = ensure_ok(h);
-      }
-      if (rc) return rc;
-      h->f_ghosts_dirty = false;
-      h->uv_ghosts_dirty = false;
-      h->ghosts_virtual = virt;
-    }
+    if ((rc = step_loop(h, nsteps, !(h->d.flags & VOF_FLAG_NO_GRAPH) && h->mg_graph, &mg,
+                        [h, &mg](const StepPlan& p, int64_t, int*) { return run_step_mg_graph(h, p.virt, mg); })))
+      return rc;
     if (last_residual || worst_residual || worst_step) {
       HIPCHK(h, hipMemcpyAsync(rec, h->mg_rec, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -339,7 +327,7 @@ int profile_steps(vof2d_ctx* h, int64_t nsteps) {
     int batch = 0;
     // A handle whose batch graphs run the k_tm form is profiled in that form: the same launch sequence, eagerly, every
     // launch between its own event pair (k_momentum, K x k_jacobi_pair / 2 K x k_jacobi_tb, K - 1 x k_tm, k_transport).
-    const bool tm_form = batch_form(h, false) == 1 && !h->f_ghosts_dirty && !h->uv_ghosts_dirty && step_leaves_ghosts_virtual(h) && nsteps - done >= 2;
+    const bool tm_form = batch_form(h, false) == 1 && plan_step(h->state, step_caps(h, false)).virt && nsteps - done >= 2;
     if (tm_form) {
       // (1 + K x (Jacobi launches + 1) launches, each with its own event pair out of the pool)
       const int per_tm_step = 1 + (DISPATCH_B(h, L<double>::jacobi_pair_ok(h), L<float>::jacobi_pair_ok(h)) ? h->d.jacobi_iters / 10 : h->d.jacobi_iters / 5);
@@ -347,23 +335,20 @@ int profile_steps(vof2d_ctx* h, int64_t nsteps) {
       for (int b = vof2d_ctx::kStepBatches - 1; b >= 0; --b)
         if (nsteps - done >= batch_steps(h, 1, b) && 1 + batch_steps(h, 1, b) * per_tm_step <= vof2d_ctx::kMaxTimed && batch_steps(h, 1, b) > K) K = batch_steps(h, 1, b);
       if (1 + K * per_tm_step > vof2d_ctx::kMaxTimed) { h->timed = -1; return fail(h, VOF_ESTATE, "a k_tm batch of two steps has more launches than the profiling event pool"); }
-      if (!h->ahead) DISPATCH_T(h, enqueue_tm_head<double>(h, (int)((h->istep + 1) & 1)), enqueue_tm_head<float>(h, (int)((h->istep + 1) & 1)));
-      h->ahead = true;
+      if (!h->state.ahead) DISPATCH_T(h, enqueue_tm_head<double>(h, (int)((h->istep + 1) & 1)), enqueue_tm_head<float>(h, (int)((h->istep + 1) & 1)));
+      h->state.ahead = true;
       DISPATCH_T(h, enqueue_steps_tm<double>(h, h->istep + 1, K), enqueue_steps_tm<float>(h, h->istep + 1, K));
       h->istep += K;
-      h->ghosts_virtual = true;
+      h->state.ghosts_virtual = true;
       batch = K;
     }
     while (!tm_form && done + batch < nsteps && h->timed + per_step <= vof2d_ctx::kMaxTimed) {
       h->istep += 1;
-      h->ahead = false;
-      const bool lean = !h->f_ghosts_dirty;
-      const bool virt = step_leaves_ghosts_virtual(h);
-      if (!virt) settle_ghosts(h);
-      DISPATCH_T(h, enqueue_step<double>(h, h->istep, lean, virt), enqueue_step<float>(h, h->istep, lean, virt));
-      h->f_ghosts_dirty = false;
-      h->uv_ghosts_dirty = false;
-      h->ghosts_virtual = virt;
+      h->state.ahead = false;   // (cleared in front of settle_ghosts, unlike step_loop: no copy of a predictor formed ahead, no ensure_ok per step)
+      const StepPlan p = plan_step(h->state, step_caps(h, false));
+      if (!p.virt) settle_ghosts(h);
+      DISPATCH_T(h, enqueue_step<double>(h, h->istep, p.lean, p.virt), enqueue_step<float>(h, h->istep, p.lean, p.virt));
+      finish_step(h->state, p);
       ++batch;
     }
     const int launches = h->timed;

@@ -6,8 +6,9 @@
 // exists here: every verb is a kernel launch.
 //
 // This file holds the extern "C" entry points only: null and argument checks, the error messages, settle_ghosts, one
-// call into the runtime, the dirty flags.  The runtime behind them:
+// call into the runtime, what the call did to the handle's state (a call into runtime/state.h).  The runtime behind them:
 //   runtime/context.h    the handle (with its graph cache), constants
+//   runtime/state.h      plain C++: what the fields and ghost cells hold (FieldState), a field written from outside, the prologue and epilogue of a step, the phase order
 //   runtime/launches.h   chunk-length heuristics, one launch wrapper per kernel (tile counts from the geometry in vof2d_device.h)
 //   runtime/graphs.h     the keys of the graph cache, the one capture helper
 //   runtime/rows.h       plain C++: the owned rows of a strip, its edge bands, the rest; what a launch of one part gets
@@ -60,6 +61,18 @@ const Knob* find_knob(const char* name) {
     if (!strcmp(name, k.name)) return &k;
   return nullptr;
 }
+
+// ---- checks several entry points share (0: go on)
+int check_criterion(vof2d_ctx* h, int criterion) {
+  return criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL ? fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL") : VOF_OK;
+}
+int check_whole_domain(vof2d_ctx* h, const char* why_not_a_strip) {   // (the message names the entry point and the reason)
+  return h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1 ? fail(h, VOF_ESTATE, why_not_a_strip) : VOF_OK;
+}
+int check_no_phased_step(vof2d_ctx* h) {
+  return phased_step_in_progress(h->state) ? fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress") : VOF_OK;
+}
+bool full_domain(const vof2d_ctx* h) { return h->g.wall_lo && h->g.wall_hi; }
 
 }  // namespace
 
@@ -192,17 +205,14 @@ int vof_set_init_F(vof2d_handle h, int32_t ic) {
   if (ic < 1 || ic > 3) return fail(h, VOF_EINVAL, "ic must be 1, 2 or 3 (2dvof.py:13)");
   settle_ghosts(h);
   DISPATCH_T(h, L<double>::init_F(h, ic), L<float>::init_F(h, ic));
-  h->f_ghosts_dirty = true;
-  forget_batch_form(h);
+  if (field_written(h->state, fF, full_domain(h), false)) forget_batch_form(h);
   if (tm_by_rule(h)) (void)post_gas_count(h);   // (the batch-form rule looks at the new F: the count is taken now, asynchronously, and read by the first batched step)
   return ensure_ok(h);
 }
 int vof_set_BC(vof2d_handle h) {
   if (!h) return VOF_EINVAL;
   DISPATCH_T(h, (L<double>::set_bc<BC_ALL | BC_RHO>(h)), (L<float>::set_bc<BC_ALL | BC_RHO>(h)));
-  h->f_ghosts_dirty = false;
-  h->uv_ghosts_dirty = false;
-  h->ghosts_virtual = false;   // this launch is the one a fused step left out
+  bc_applied(h->state);   // this launch is the one a fused step left out
   return ensure_ok(h);
 }
 int vof_cal_nu_rho(vof2d_handle h) {
@@ -215,14 +225,14 @@ int vof_get_normal_young(vof2d_handle h) {
   if (!h) return VOF_EINVAL;
   settle_ghosts(h);
   DISPATCH_T(h, (L<double>::normals(h), L<double>::kappa(h)), (L<float>::normals(h), L<float>::kappa(h)));
-  h->alt_dirty = true;
+  verb_wrote_alt(h->state);
   return ensure_ok(h);
 }
 int vof_advect_upwind(vof2d_handle h) {
   if (!h) return VOF_EINVAL;
   settle_ghosts(h);
   DISPATCH_T(h, L<double>::predictor<true>(h), L<float>::predictor<true>(h));
-  h->alt_dirty = true;
+  verb_wrote_alt(h->state);
   return ensure_ok(h);
 }
 int vof_solve_p_jacobi(vof2d_handle h, int32_t n) {
@@ -238,14 +248,14 @@ int vof_update_uv(vof2d_handle h) {
   if (!h) return VOF_EINVAL;
   settle_ghosts(h);
   DISPATCH_T(h, L<double>::correct<true>(h), L<float>::correct<true>(h));
-  h->uv_ghosts_dirty = true;
+  verb_wrote_uv(h->state);
   return ensure_ok(h);
 }
 int vof_fct_x_sweep(vof2d_handle h) {
   if (!h) return VOF_EINVAL;
   settle_ghosts(h);
   DISPATCH_T(h, (sweep_x<double, false, false>(h)), (sweep_x<float, false, false>(h)));
-  h->f_ghosts_dirty = true;
+  verb_wrote_F(h->state);
   sweep_swapped(h);
   return ensure_ok(h);
 }
@@ -253,7 +263,7 @@ int vof_fct_y_sweep(vof2d_handle h) {
   if (!h) return VOF_EINVAL;
   settle_ghosts(h);
   DISPATCH_T(h, (sweep_y<double, false, false>(h)), (sweep_y<float, false, false>(h)));
-  h->f_ghosts_dirty = true;
+  verb_wrote_F(h->state);
   sweep_swapped(h);
   return ensure_ok(h);
 }
@@ -271,28 +281,27 @@ int vof_post_process_f(vof2d_handle h) {
   if (!h) return VOF_EINVAL;
   settle_ghosts(h);
   DISPATCH_T(h, L<double>::post(h), L<float>::post(h));
-  h->f_ghosts_dirty = true;
+  verb_wrote_F(h->state);
   return ensure_ok(h);
 }
 
 int vof_step(vof2d_handle h, int64_t nsteps) {
   if (!h) return VOF_EINVAL;
   if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (const int rc = check_no_phased_step(h)) return rc;
   return step_n(h, nsteps);   // (runtime/step.h: each step inside a batch graph, from its own graph, or eagerly)
 }
 int vof_step_phase(vof2d_handle h, int32_t phase) {
   if (!h) return VOF_EINVAL;
   if (phase < 0 || phase > 2) return fail(h, VOF_EINVAL, "phase must be 0, 1 or 2");
-  if (phase != h->next_phase) return fail(h, VOF_ESTATE, "vof_step_phase must be called in the order 0, 1, 2");
+  if (!phase_is_next(h->state, phase)) return fail(h, VOF_ESTATE, "vof_step_phase must be called in the order 0, 1, 2");
   if (phase == 0) {
     settle_ghosts(h);
     int rc = match_phase_graph_orientation(h);
     if (rc) return rc;
     h->istep += 1;
   }
-  h->next_phase = phase == 2 ? 0 : phase + 1;
-  if (phase == 2) h->f_ghosts_dirty = h->uv_ghosts_dirty = false;   // the phases carry every set_BC of the step
+  phase_taken(h->state, phase);
   return step_phase(h, phase);
 }
 int vof_get_istep(vof2d_handle h, int64_t* istep) {
@@ -336,7 +345,7 @@ int vof_solve_p(vof2d_handle h, double tol, int32_t max_iters, int32_t check_eve
                 int32_t* iters_done, double* residual) {
   if (!h || !iters_done || !residual) return VOF_EINVAL;
   if (max_iters < 1 || check_every < 1) return fail(h, VOF_EINVAL, "max_iters and check_every must be >= 1");
-  if (criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
+  if (const int rc = check_criterion(h, criterion)) return rc;
   int done = 0;
   double r = 0.0;
   bool first = true;
@@ -364,9 +373,8 @@ int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_
                    int32_t build_rhs, int32_t* iters_done, double* residual, double* drift) {
   if (!h || !iters_done || !residual || !drift) return VOF_EINVAL;
   if (max_iters < 1 || check_every < 1) return fail(h, VOF_EINVAL, "max_iters and check_every must be >= 1");
-  if (criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
-  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
-    return fail(h, VOF_ESTATE, "vof_solve_p_cg needs the whole domain in one handle (the dot products of a strip would need an all-reduce)");
+  if (const int rc = check_criterion(h, criterion)) return rc;
+  if (const int rc = check_whole_domain(h, "vof_solve_p_cg needs the whole domain in one handle (the dot products of a strip would need an all-reduce)")) return rc;
   settle_ghosts(h);
   int rc = cg_prepare(h);
   if (rc) return rc;
@@ -400,9 +408,8 @@ int vof_solve_p_mg(vof2d_handle h, double tol, int32_t max_cycles, int32_t check
                    int32_t build_rhs, int32_t* cycles_done, double* residual, double* drift) {
   if (!h || !cycles_done || !residual || !drift) return VOF_EINVAL;
   if (max_cycles < 1 || check_every < 1) return fail(h, VOF_EINVAL, "max_cycles and check_every must be >= 1");
-  if (criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
-  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
-    return fail(h, VOF_ESTATE, "vof_solve_p_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)");
+  if (const int rc = check_criterion(h, criterion)) return rc;
+  if (const int rc = check_whole_domain(h, "vof_solve_p_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)")) return rc;
   settle_ghosts(h);
   return mg_solve(h, tol, max_cycles, check_every, criterion, build_rhs, cycles_done, residual, drift);
 }
@@ -413,10 +420,9 @@ int vof_step_mg(vof2d_handle h, int64_t nsteps, int32_t cycles, int32_t criterio
   if (!h) return VOF_EINVAL;
   if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
   if (cycles < 1) return fail(h, VOF_EINVAL, "cycles must be >= 1");
-  if (criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
-  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
-    return fail(h, VOF_ESTATE, "vof_step_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)");
-  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (const int rc = check_criterion(h, criterion)) return rc;
+  if (const int rc = check_whole_domain(h, "vof_step_mg needs the whole domain in one handle (a strip's coarse levels and sums would span its neighbours)")) return rc;
+  if (const int rc = check_no_phased_step(h)) return rc;
   return step_mg_n(h, nsteps, cycles, criterion, last_residual, worst_residual, worst_step);
 }
 
@@ -436,12 +442,11 @@ int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycl
   if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
   if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
   if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
-  if (mg_cycles >= 1 && criterion != VOF_RESID_ABS && criterion != VOF_RESID_REL) return fail(h, VOF_EINVAL, "criterion must be VOF_RESID_ABS or VOF_RESID_REL");
+  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
   if (cap_rows < nsteps / every) return fail(h, VOF_EINVAL, "cap_rows is smaller than nsteps / every");
   if (!out && nsteps / every > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one row is due");
-  if (h->d.row_lo != 0 || h->d.row_hi != h->d.nx + 1)
-    return fail(h, VOF_ESTATE, "vof_step_diag needs the whole domain in one handle (a strip's steps need their exchanges: call vof_diagnostics between them)");
-  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (const int rc = check_whole_domain(h, "vof_step_diag needs the whole domain in one handle (a strip's steps need their exchanges: call vof_diagnostics between them)")) return rc;
+  if (const int rc = check_no_phased_step(h)) return rc;
   if (nsteps == 0) {
     if (rows_written) *rows_written = 0;
     return VOF_OK;
@@ -472,9 +477,7 @@ int vof_set_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, const
   if (id < 0) return fail(h, VOF_EINVAL, "unknown field name");
   int rc = copy_rows_host(h, id, g0, g1, const_cast<void*>(src), nbytes, false);
   if (rc == VOF_OK && id == fF) rc = copy_rows_host(h, fF2, g0, g1, const_cast<void*>(src), nbytes, false);
-  if (id == fF || id == fF2) { h->f_ghosts_dirty = true; forget_batch_form(h); }
-  if (id == fMX || id == fMY) h->alt_dirty = true;
-  if (id == fU || id == fV) h->uv_ghosts_dirty = true;
+  if (field_written(h->state, id, full_domain(h), false)) forget_batch_form(h);
   return rc;
 }
 int vof_get_field(vof2d_handle h, const char* name, void* dst, size_t nbytes) {
@@ -528,11 +531,7 @@ int vof_copy_rows(vof2d_handle dst, vof2d_handle src, const char* name, int32_t 
     HIPCHK(dst, hipEventRecord(dst->ev1, dst->stream));
     HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev1, 0));
   }
-  if (dst->g.wall_lo && dst->g.wall_hi) {  // a full domain: the rows' neighbours' ghost cells may no longer mirror them
-    if (id == fF) { dst->f_ghosts_dirty = true; forget_batch_form(dst); }
-    if (id == fMX || id == fMY) dst->alt_dirty = true;
-    if (id == fU || id == fV) dst->uv_ghosts_dirty = true;
-  }
+  if (field_written(dst->state, id, full_domain(dst), /*rows_only_inside=*/true)) forget_batch_form(dst);
   return VOF_OK;
 }
 
@@ -553,7 +552,7 @@ static int vis_scratch(vof2d_handle h, size_t bytes) {
 int vof_get_vis_field(vof2d_handle h, const char* which, void* dst, size_t nbytes) {
   if (!h || !which || !dst) return VOF_EINVAL;
   settle_ghosts(h);
-  if (!(h->g.wall_lo && h->g.wall_hi)) return fail(h, VOF_ESTATE, "display fields need a full-domain handle");
+  if (!full_domain(h)) return fail(h, VOF_ESTATE, "display fields need a full-domain handle");
   int mode = !strcmp(which, "vof") ? 0 : !strcmp(which, "u") ? 1 : !strcmp(which, "v") ? 2 : !strcmp(which, "vnorm") ? 3 : -1;
   if (mode < 0) return fail(h, VOF_EINVAL, "display field must be vof, u, v or vnorm");
   const size_t bytes = (size_t)4 * h->g.nx * h->g.ny * h->esz;
@@ -575,7 +574,7 @@ int vof_get_vis_field(vof2d_handle h, const char* which, void* dst, size_t nbyte
 int vof_interp_velocity(vof2d_handle h, void* dst, size_t nbytes) {
   if (!h || !dst) return VOF_EINVAL;
   settle_ghosts(h);
-  if (!(h->g.wall_lo && h->g.wall_hi)) return fail(h, VOF_ESTATE, "interp_velocity needs a full-domain handle");
+  if (!full_domain(h)) return fail(h, VOF_ESTATE, "interp_velocity needs a full-domain handle");
   const size_t bytes = (size_t)2 * (h->g.nx + 2) * (h->g.ny + 2) * h->esz;
   if (nbytes != bytes) return fail(h, VOF_EINVAL, "buffer must be (nx+2, ny+2, 2) of the field dtype");
   int rc = vis_scratch(h, bytes);
@@ -657,9 +656,7 @@ int vof_get_counter(vof2d_handle h, const char* name, int64_t* value) {
     unsigned long long v = 0;
     HIPCHK(h, hipMemcpyAsync(&v, h->d_tbmask + 2 * TB_BANDS * (TB_COLS / 64), sizeof(v), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->jpair_active = true;
-    const TbPlan tp = L<double>::tb_plan(h, (int)(h->istep & 1));
-    h->jpair_active = false;
+    const TbPlan tp = L<double>::tb_plan(h, (int)(h->istep & 1), PlanFor::kJacobiPair);
     *value = !strcmp(name, "dbg_plan_word") ? (int64_t)v : !strcmp(name, "dbg_plan_waves") ? tp.waves : !strcmp(name, "dbg_plan_R") ? tp.R : tp.ntt;
     return VOF_OK;
   }
@@ -711,7 +708,7 @@ int vof_timer_stop(vof2d_handle h, float* ms) {
 int vof_profile_steps(vof2d_handle h, int64_t nsteps) {
   if (!h) return VOF_EINVAL;
   if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (const int rc = check_no_phased_step(h)) return rc;
   return profile_steps(h, nsteps);
 }
 int vof_get_profile(vof2d_handle h, const char* kernel, double* avg_us, int64_t* launches) {
@@ -732,7 +729,7 @@ int vof_reset_profile(vof2d_handle h) {
 int vof_time_jacobi(vof2d_handle h, int32_t n, float* ms_per_sweep) {
   if (!h || !ms_per_sweep) return VOF_EINVAL;
   if (n < 2 || (n & 1)) return fail(h, VOF_EINVAL, "n must be even and >= 2");
-  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (const int rc = check_no_phased_step(h)) return rc;
   // one hipEvent pair on the handle's stream around n back-to-back sweeps of the current rhs
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   DISPATCH_T(h, jacobi_n<double>(h, n, false), jacobi_n<float>(h, n, false));
@@ -824,9 +821,9 @@ int vof_comm_exchange(vof2d_handle h, uint32_t field_mask) {
 
 int vof_step_tm_piece(vof2d_handle h, int32_t piece) {
   if (!h || piece < 0 || piece > 2) return VOF_EINVAL;
-  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (const int rc = check_no_phased_step(h)) return rc;
   if (!mode5_ok(h)) return fail(h, VOF_ESTATE, "the pair kernels need the fused transport and five-sweep Jacobi launches");
-  if (h->f_ghosts_dirty || h->uv_ghosts_dirty) return fail(h, VOF_ESTATE, "the first step after set_init_F / set_field runs through vof_step");
+  if (!clean_ghosts(h->state)) return fail(h, VOF_ESTATE, "the first step after set_init_F / set_field runs through vof_step");
   (void)settle_ahead(h);   // (a full domain that ran chained k_tm batches: its u*, v*, rhs are the last step's from here on)
   if (piece == 0) {
     DISPATCH_T(h, tm5_head<double>(h), tm5_head<float>(h));
@@ -843,13 +840,13 @@ int vof_step_tm_piece(vof2d_handle h, int32_t piece) {
     swap_F(h);
     if (!h->virtual_ghosts) DISPATCH_T(h, L<double>::set_bc<BC_ALL>(h), L<float>::set_bc<BC_ALL>(h));
   }
-  h->ghosts_virtual = h->virtual_ghosts != 0;
+  finish_step(h->state, strip_step_plan(h, true));   // (nothing was dirty: refused above)
   return ensure_ok(h);
 }
 int vof_step_exchange(vof2d_handle h, int64_t nsteps, int32_t overlap) {
   if (!h || nsteps < 0 || overlap < 0 || overlap > 5 || overlap == 2) return VOF_EINVAL;   // (2 was retired: never worth it)
   if (!h->comm) return fail(h, VOF_ESTATE, "vof_comm_init has not been called");
-  if (h->next_phase != 0) return fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress");
+  if (const int rc = check_no_phased_step(h)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   (void)settle_ahead(h);   // (see vof_step_tm_piece)
   return overlap == 5 ? step_exchange_mode5(h, nsteps) : step_exchange(h, nsteps, overlap);
