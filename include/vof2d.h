@@ -275,6 +275,52 @@ int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycl
 #define VOF_IFACE_SUM_ISTEP 3
 #define VOF_IFACE_SUM_N 4
 int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary /* VOF_IFACE_SUM_N */);
+/* Extension: how many pieces the liquid (or the gas) is in, and what each piece is doing: connected-component labelling and per-blob
+ * sums on the device instead of copying F, u, v to the host.  Cells: the handle's owned interior cells, i in [max(own_lo, 1), min(own_hi, nx)],
+ * j in [1, ny]; ghost cells are never members; every operand is converted to double first (one code path for both dtypes).
+ *   member      VOF_BLOB_LIQUID: F >= threshold; VOF_BLOB_GAS: F < threshold; a NaN F is a member of neither
+ *   a blob      a maximal set of members connected through shared faces (4-connectivity: diagonal neighbours are not connected).  Its
+ *               FIRST CELL is its smallest cell in ascending (i, j) order, i first; blobs are listed in ascending order of their first cell
+ *   a row       VOF_BLOB_N doubles (unused slots read 0): I0, J0 the first cell (global indices); CELLS; IMIN, IMAX, JMIN, JMAX the extent
+ *               (all integers, exact as doubles); SUM_W, SUM_WI, SUM_WJ = sum of w, w i, w j with w = Fc (liquid) or 1 - Fc (gas),
+ *               Fc = fmin(fmax(F, 0), 1), i and j the global integer indices -- the volume is SUM_W dx dy, the centroid
+ *               xc = (SUM_WI / SUM_W - 0.5) dx, yc = (SUM_WJ / SUM_W - 0.5) dy; SUM_WU, SUM_WV = sum of w uc, w vc with the cell-centre
+ *               velocities uc = (u[i,j] + u[i+1,j]) / 2, vc = (v[i,j] + v[i,j+1]) / 2 of interp_velocity (2dvof.py:492), the expressions of
+ *               vof_diagnostics -- the blob's velocity is SUM_WU / SUM_W.  A NaN in u or v reaches the sums of the blob that holds it only
+ *   summary     SUM_BLOBS the blobs that exist (may exceed cap_rows), SUM_MEMBER_CELLS, SUM_MAX_CELLS the size of the largest blob,
+ *               SUM_ISTEP the handle's istep; it always describes ALL blobs, so rows = NULL with cap_rows = 0 sizes a buffer
+ *   labels      optional (NULL skips them): a dense (owned interior rows, ny) array of int32, the 0-based index of the cell's blob in the
+ *               full list (also of blobs beyond cap_rows), -1 for a non-member; labels_bytes must match exactly
+ * At most cap_rows rows are written and nothing behind min(BLOBS, cap_rows) rows is touched.  The same state and call give the same bytes,
+ * on any run and any handle: the integers come from 32-bit integer atomics (independent of arrival order), the five sums are formed in
+ * double in the fixed order csrc/kernels/blobs.h states, which depends on the geometry and the blob's own extent alone; no floating-point
+ * atomics.  No field, istep, counter or cached graph changes, and a vof_step / vof_step_mg / vof_step_diag that follows gives the bits it
+ * would have given without the call.  Works on strip handles: the value is that of the strip's own rows as if the strip's edges were
+ * walls (row own_hi + 1 of u is a stored halo row); a driver joins the strips' lists (vof2d/blobs.py, combine).  A phase other than the
+ * two, a threshold NaN or outside (0, 1), cap_rows < 0, rows == NULL with cap_rows > 0, summary == NULL, a wrong labels_bytes, more than
+ * 2^31 - 1 cells: VOF_EINVAL, the handle untouched.  Synchronises and copies out. */
+#define VOF_BLOB_LIQUID 0
+#define VOF_BLOB_GAS 1
+#define VOF_BLOB_I0 0     /* the first cell, global indices as doubles */
+#define VOF_BLOB_J0 1
+#define VOF_BLOB_CELLS 2
+#define VOF_BLOB_IMIN 3
+#define VOF_BLOB_IMAX 4
+#define VOF_BLOB_JMIN 5
+#define VOF_BLOB_JMAX 6
+#define VOF_BLOB_SUM_W 7
+#define VOF_BLOB_SUM_WI 8
+#define VOF_BLOB_SUM_WJ 9
+#define VOF_BLOB_SUM_WU 10
+#define VOF_BLOB_SUM_WV 11
+#define VOF_BLOB_N 16
+#define VOF_BLOB_SUM_BLOBS 0
+#define VOF_BLOB_SUM_MEMBER_CELLS 1
+#define VOF_BLOB_SUM_MAX_CELLS 2
+#define VOF_BLOB_SUM_ISTEP 3
+#define VOF_BLOB_SUM_N 4
+int vof_blobs(vof2d_handle h, int32_t phase, double threshold, double* rows, int64_t cap_rows,
+              int32_t* labels, size_t labels_bytes, double* summary /* VOF_BLOB_SUM_N */);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

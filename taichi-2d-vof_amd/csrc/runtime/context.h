@@ -229,6 +229,18 @@ struct vof2d_ctx {
   double* iface_part = nullptr;
   double* iface_rows = nullptr;      // iface_cap rows of VOF_IFACE_N doubles
   int64_t iface_cap = 0;
+  // vof_blobs (runtime/blobs.h).  One allocation fixed by the geometry: parent, then labels, of every owned cell; the blob index of
+  // every root; the root count of every (row, column tile), turned into offsets in place; 8 doubles (the summary, the total of a scan).
+  // Grown on demand: the integer records of the blobs, the wave offsets and the rows of the blobs asked for, the partials of their sums
+  int* blob_lab = nullptr;
+  int* blob_idx = nullptr;
+  int* blob_cnt = nullptr;
+  double* blob_sum = nullptr;
+  int* blob_rec = nullptr;           // blob_rec_cap records of kBlobRec ints
+  int* blob_off = nullptr;           // blob_off_cap ints
+  double* blob_rows = nullptr;       // blob_rows_cap rows of VOF_BLOB_N doubles
+  double* blob_part = nullptr;       // blob_part_cap partials of kBlobSums doubles
+  int64_t blob_rec_cap = 0, blob_off_cap = 0, blob_rows_cap = 0, blob_part_cap = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

@@ -17,6 +17,7 @@
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
 //   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
 //   runtime/interface.h  the buffers, launches and copies of vof_interface
+//   runtime/blobs.h      the buffers, launches and copies of vof_blobs
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -28,6 +29,7 @@
 #include "runtime/step.h"
 #include "runtime/diag_reduce.h"
 #include "runtime/interface.h"
+#include "runtime/blobs.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -194,6 +196,7 @@ int vof_destroy(vof2d_handle h) {
   mg_release(h);
   diag_release(h);
   iface_release(h);
+  blobs_release(h);
   if (h->arena) (void)hipFree(h->arena);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -461,6 +464,17 @@ int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, do
   if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
   if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_interface keeps 32-bit offsets: at most 2^31 - 1 cells");
   return iface_run(h, eps, rows, cap_rows, summary);
+}
+
+// ---- droplets and bubbles, labelled and measured (kernels/blobs.h, runtime/blobs.h)
+int vof_blobs(vof2d_handle h, int32_t phase, double threshold, double* rows, int64_t cap_rows, int32_t* labels, size_t labels_bytes, double* summary) {
+  if (!h || !summary) return VOF_EINVAL;
+  if (phase != VOF_BLOB_LIQUID && phase != VOF_BLOB_GAS) return fail(h, VOF_EINVAL, "phase must be VOF_BLOB_LIQUID or VOF_BLOB_GAS");
+  if (!(threshold > 0.0 && threshold < 1.0)) return fail(h, VOF_EINVAL, "threshold must lie in (0, 1)");
+  if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
+  if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_blobs keeps 32-bit keys: at most 2^31 - 1 cells");
+  if (labels && labels_bytes != (size_t)blob_cells(h) * sizeof(int32_t)) return fail(h, VOF_EINVAL, "labels_bytes is not (owned interior rows) x ny x 4");
+  return blobs_run(h, phase, threshold, rows, cap_rows, labels, summary);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

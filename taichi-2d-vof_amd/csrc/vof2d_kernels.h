@@ -22,6 +22,7 @@
 //   mg.h         k_mg_smooth, k_mg_restrict, k_mg_prolong, k_mg_coarse_block, k_mg_step_record  (extension: geometric multigrid on the same equation)
 //   diag.h       k_diag, k_diag_finish   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
 //   interface.h  k_iface, k_iface_scan   (extension: the interface as PLIC segments, counted, scanned and emitted in (i, j) order)
+//   blobs.h      k_blob_init, k_blob_merge, k_blob_flatten, k_blob_number, k_blob_label, k_blob_stats, k_blob_summary, k_blob_plan, k_blob_sums, k_blob_rows   (extension: droplets and bubbles labelled by union-find, numbered by first cell, measured in a fixed order)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
@@ -37,3 +38,4 @@
 #include "kernels/mg.h"
 #include "kernels/diag.h"
 #include "kernels/interface.h"
+#include "kernels/blobs.h"

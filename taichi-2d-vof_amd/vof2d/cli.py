@@ -71,6 +71,12 @@ def build_parser():
                      help='every N steps write data/interface_NNNNNN.npy -- the interface as one PLIC segment per mixed cell, '
                           'rows of i, j, x0, y0, x1, y1, nx, ny extracted on the device (vof_interface) -- and append istep, '
                           'segments, degenerate, length to data/interface.csv; with -s the VOF frame draws the segments')
+    ext.add_argument('--blobs-every', type=int, default=None, metavar='N',
+                     help='every N steps append one line per blob to data/blobs.csv -- istep, blob, cells, volume, xc, yc, uc, vc, '
+                          'imin, imax, jmin, jmax of every connected piece of the phase, labelled and measured on the device (vof_blobs)')
+    ext.add_argument('--blobs-phase', choices=('liquid', 'gas'), default='liquid',
+                     help='the phase whose pieces --blobs-every lists: liquid (F >= T, droplets) or gas (F < T, bubbles)')
+    ext.add_argument('--blobs-threshold', type=float, default=0.5, metavar='T', help='the F that separates the phases for --blobs-every, in (0, 1)')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
 
@@ -83,6 +89,10 @@ def parse_args(argv=None):
         parser.error("--diag-every needs N >= 1")
     if args.interface_every is not None and args.interface_every < 1:
         parser.error("--interface-every needs N >= 1")
+    if args.blobs_every is not None and args.blobs_every < 1:
+        parser.error("--blobs-every needs N >= 1")
+    if not 0.0 < args.blobs_threshold < 1.0:
+        parser.error("--blobs-threshold needs 0 < T < 1")
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -229,6 +239,9 @@ class _Single:
     def interface(self):
         return self.eng.interface()
 
+    def blobs(self):
+        return self.eng.blobs(self.args.blobs_phase, self.args.blobs_threshold)
+
     def take_diag(self):
         rows, self.diag_rows = self.diag_rows, []
         return rows
@@ -298,6 +311,9 @@ class _Strips:
 
     def interface(self):
         return self.s.interface()                    # (collective: rank 0 holds the domain's list, the others None)
+
+    def blobs(self):
+        return self.s.blobs(self.args.blobs_phase, self.args.blobs_threshold)   # (collective, likewise)
 
     def take_diag(self):
         rows, self.diag_rows = self.diag_rows, []
@@ -405,12 +421,23 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                 f.write(','.join([str(k), repr(k * dt)] + [repr(float(last[c])) for c in diag.DERIVED]) + '\n')
         return last
 
+    # ... and so are the blobs (vof_blobs)
+    blobs_every = getattr(args, "blobs_every", None) or 0
+    blobs_path = 'data/blobs.csv'
+    if blobs_every and lead:
+        from . import blobs as blobs_mod
+        if not (args.resume and os.path.exists(blobs_path) and os.path.getsize(blobs_path) > 0):
+            with open(blobs_path, 'w') as f:
+                f.write(blobs_mod.CSV_HEADER + '\n')
+
     def next_stop(i):
         n = nstep - i % nstep
         if stop_at_diag:
             n = min(n, diag_every - i % diag_every)
         if iface_every:
             n = min(n, iface_every - i % iface_every)
+        if blobs_every:
+            n = min(n, blobs_every - i % blobs_every)
         if args.save_every:
             n = min(n, args.save_every - i % args.save_every)
         if args.steps:
@@ -435,6 +462,11 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                     np.save('data/interface_%06d.npy' % istep, seg)
                     with open(iface_path, 'a') as f:
                         f.write('%d,%d,%d,%r\n' % (istep, summ["SEGMENTS"], summ["DEGENERATE"], float(summ["LENGTH"])))
+            if blobs_every and istep % blobs_every == 0:
+                found = drv.blobs()
+                if lead:
+                    with open(blobs_path, 'a') as f:
+                        f.writelines(line + '\n' for line in blobs_mod.csv_lines(found[0], istep, eng.get_param("dx"), eng.get_param("dy")))
             if args.save_every and istep % args.save_every == 0:
                 fields = {f: drv.full(f) for f in STATE}
                 warn = drv.courant()

@@ -224,6 +224,30 @@ class Engine:
         self._iface_cap = cap
         return rows[:n].copy(), interface.summary_of(list(summ))
 
+    def blobs(self, phase="liquid", threshold=0.5, labels=False):
+        """vof_blobs: the connected pieces of the liquid (F >= threshold) or of the gas (F < threshold) on the owned interior
+        rows, labelled and measured on the device; returns (rows, summary[, labels]): an (n, VOF_BLOB_N) float64 array in
+        ascending order of the blobs' first cells (the slots: vof2d/blobs.py), the summary as a dict keyed by blobs.SUMMARY
+        and, if asked for, the (owned interior rows, ny) int32 array of blob indices (-1: not a member).  One call with the
+        capacity the last call needed (plus a margin); a second one if the list has outgrown it."""
+        from . import blobs
+        ptr = C.POINTER(C.c_double)
+        summ = (C.c_double * _abi.VOF_BLOB_SUM_N)()
+        nrows = max(min(self.own_hi, self.nx) - max(self.own_lo, 1) + 1, 0)
+        lab = np.empty((nrows, self.ny), dtype=np.int32) if labels else None
+        cap = getattr(self, "_blobs_cap", 16)
+        while True:
+            rows = np.empty((cap, _abi.VOF_BLOB_N), dtype=np.float64)
+            self._ck(self.api.blobs(self._h, blobs.PHASES[phase], float(threshold), rows.ctypes.data_as(ptr) if cap else None, cap,
+                                    lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None, lab.nbytes if labels else 0, summ), "blobs")
+            n = int(summ[_abi.VOF_BLOB_SUM_BLOBS])
+            if n <= cap:
+                break
+            cap = n + n // 8 + 16
+        self._blobs_cap = cap
+        out = (rows[:n].copy(), blobs.summary_of(list(summ)))
+        return out + (lab,) if labels else out
+
     def jacobi_sweeps_norms(self, n, build_rhs=True):
         """(max|p_new - p|, max|p_new|) of the last of n sweeps over the owned rows."""
         upd, pm = C.c_double(), C.c_double()

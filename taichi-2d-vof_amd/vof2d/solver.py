@@ -139,6 +139,10 @@ class VOF2D:
         """The interface as PLIC segments, extracted on the device (vof_interface): (rows, summary), vof2d/interface.py."""
         return self.eng.interface(eps)
 
+    def blobs(self, phase="liquid", threshold=0.5, labels=False):
+        """Droplets or bubbles labelled and measured on the device (vof_blobs): (rows, summary[, labels]), vof2d/blobs.py."""
+        return self.eng.blobs(phase, threshold, labels)
+
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)

@@ -485,6 +485,19 @@ class StripSolver:
         parts = self.comm.gather_object(mine)
         return interface.combine(parts) if self.rank == 0 else None
 
+    def blobs(self, phase="liquid", threshold=0.5, labels=False):
+        """vof_blobs of the whole domain on rank 0 (None elsewhere): every strip labels and measures its own rows as if its
+        edges were walls, rank 0 gathers (rows, summary, labels) in rank order and joins the blobs that meet across an edge
+        (blobs.combine).  world == 1: the single-domain value."""
+        from . import blobs
+        if self.world == 1:
+            return self.eng.blobs(phase, threshold, labels)
+        parts = self.comm.gather_object(self.eng.blobs(phase, threshold, True))
+        if self.rank != 0:
+            return None
+        out = blobs.combine(parts, self.ny)
+        return out if labels else out[:2]
+
     def sync(self):
         self.eng.sync()
 
