@@ -1,0 +1,77 @@
+// runtime/buffers.h -- DevBuf, the one owner of a device allocation of the handle beside the field arena, and the
+// handle's list of them
+//
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip); context.h includes it in front of the handle.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../../include/vof2d.h"
+#include "carve.h"
+
+struct vof2d_ctx;
+namespace {   // what DevBuf needs of the handle; defined behind it (runtime/context.h)
+int fail(vof2d_ctx* h, int code, const char* msg);
+hipStream_t stream_of(const vof2d_ctx* h);
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;   // the capacity
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  template <typename T> T* as(size_t byte_offset = 0) const { return reinterpret_cast<T*>(static_cast<char*>(p) + byte_offset); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  // Room for `want` bytes.  Nothing to do if it is there; otherwise the old contents are given up -- behind a wait for the
+  // handle's stream: launches that read them may still be queued (hipFree waits anyway) -- and `zero` clears the new ones on
+  // that stream.  VOF_ENOMEM with the message `what` and an empty buffer if there is no memory.
+  int reserve(vof2d_ctx* h, size_t want, const char* what, bool zero = false) {
+    if (bytes >= want) return VOF_OK;
+    hipStream_t const stream = stream_of(h);
+    if (p) (void)hipStreamSynchronize(stream);
+    release();
+    if (hipMalloc(&p, want) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return fail(h, VOF_ENOMEM, what);
+    }
+    bytes = want;
+    if (zero && hipMemsetAsync(p, 0, want, stream) != hipSuccess) {
+      release();
+      return fail(h, VOF_EHIP, "hipMemsetAsync of a new work buffer failed");
+    }
+    return VOF_OK;
+  }
+};
+
+// Every work buffer of a handle: allocated by the first call that needs it (the first two: vof_create), kept until
+// vof_destroy.  Nothing but DevBufs, so that they are released as one flat range: one added here is released too.
+struct WorkBufs {
+  DevBuf courant;      // device counters: [0] courant, [1] max|p_new - p| bits, [2] max|p_new| bits (residual solve), [3] exact-zero cells of F
+  DevBuf tbmask;       // work plan of k_jacobi_tb (TbPlan): 2 x TB_BANDS mask words, then the plan (1 + waves entries)
+  DevBuf cg_fields;    // vof_solve_p_cg (runtime/multigrid.h, CgCarve): r, two direction arrays (ping-pong), q
+  DevBuf cg_part;      // ... one partial per block (kCgPart doubles), then the CG_NSCAL device scalars
+  DevBuf mg_arena;     // vof_solve_p_mg (MgCarve): the levels below the grid, the work arrays and scalars of the coarsest-level solve
+  DevBuf mg_rec;       // vof_step_mg: the residual record (kernels/mg.h, MGR_*)
+  DevBuf diag_part;    // vof_diagnostics / vof_step_diag (runtime/diag_reduce.h): one partial per block of k_diag
+  DevBuf diag_rows;    // ... the rows recorded on the device, VOF_DIAG_N doubles each, grown on demand
+  DevBuf iface_work;   // vof_interface (runtime/interface.h, IfaceCarve): the segment counts, turned into offsets in place; the partials; the summary
+  DevBuf iface_rows;   // ... the segments, VOF_IFACE_N doubles each, grown on demand
+  DevBuf blob_work;    // vof_blobs (runtime/blobs.h, BlobCarve): what the geometry fixes
+  DevBuf blob_rec;     // ... grown on demand: the integer records of the blobs (kBlobRec ints each),
+  DevBuf blob_off;     // the wave offsets and
+  DevBuf blob_rows;    // the rows (VOF_BLOB_N doubles each) of the blobs asked for,
+  DevBuf blob_part;    // the partials of their sums (kBlobSums doubles each)
+  DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
+  DevBuf red;          // device scalar of vof_comm_allreduce_max
+
+  DevBuf* begin() { return &courant; }
+  DevBuf* end() { return begin() + sizeof(WorkBufs) / sizeof(DevBuf); }
+  void release() { for (DevBuf* b = begin(); b != end(); ++b) b->release(); }
+};
+static_assert(sizeof(WorkBufs) % sizeof(DevBuf) == 0, "WorkBufs is walked as one array");
+
+}  // namespace

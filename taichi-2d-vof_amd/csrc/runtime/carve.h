@@ -1,0 +1,66 @@
+// runtime/carve.h -- one allocation cut into consecutive, aligned ranges; the arenas of the verbs cut that way
+//
+// Plain C++ (no HIP): runtime/buffers.h includes it, the CPU tests compile it on its own.  All figures are bytes.
+#pragma once
+#include <stddef.h>
+
+#include <array>
+#include <vector>
+
+namespace vof {
+
+struct Carve {
+  size_t total = 0;
+  size_t take(size_t bytes, size_t align = 1) {   // the offset of the range
+    const size_t at = (total + align - 1) / align * align;
+    total = at + bytes;
+    return at;
+  }
+  size_t ints(size_t n) { return take(n * sizeof(int)); }
+  size_t doubles(size_t n) { return take(n * sizeof(double), sizeof(double)); }
+};
+
+// vof_solve_p_cg, two allocations: r, two direction arrays (ping-pong), q in the fields' layout; one partial per block, then the scalars
+struct CgCarve { size_t fld[4], fields_total, sc, part_total; };
+inline CgCarve carve_cg(size_t field_bytes, size_t part_doubles, size_t scalars) {
+  CgCarve c;
+  Carve fields, part;
+  for (size_t& f : c.fld) f = fields.take(field_bytes);
+  part.doubles(part_doubles);
+  c.sc = part.doubles(scalars);
+  c.fields_total = fields.total; c.part_total = part.total;
+  return c;
+}
+
+// vof_solve_p_mg: e (two), f of every level >= 1; r, two directions, q of the coarsest-level solve, sized for level 1; its scalars.
+// level_bytes[l] is one array of level l (entry 0, the grid, has none here); at least two levels.
+struct MgCarve { std::vector<std::array<size_t, 3>> level; size_t cgw[4], sc, total; };
+inline MgCarve carve_mg(const std::vector<size_t>& level_bytes, size_t scalars) {
+  MgCarve c{std::vector<std::array<size_t, 3>>(level_bytes.size()), {}, 0, 0};
+  Carve a;
+  for (size_t l = 1; l < level_bytes.size(); ++l)
+    for (size_t& at : c.level[l]) at = a.take(level_bytes[l]);
+  for (size_t& w : c.cgw) w = a.take(level_bytes[1]);
+  c.sc = a.doubles(scalars);
+  c.total = a.total;
+  return c;
+}
+
+// vof_interface: the count of every (row, column tile) and one spare int; the block partials and the summary
+struct IfaceCarve { size_t cnt, part, total; };
+inline IfaceCarve carve_iface(size_t entries, size_t doubles) {
+  Carve a;
+  const size_t cnt = a.ints(entries + 1), part = a.doubles(doubles);
+  return {cnt, part, a.total};
+}
+
+// vof_blobs: parent, then label, of every cell; the blob index of every root; the root count of every (row, column tile),
+// two ints of k_blob_stats and one spare; 8 doubles (the summary, the total of a scan)
+struct BlobCarve { size_t lab, idx, cnt, sum, total; };
+inline BlobCarve carve_blobs(size_t cells, size_t entries) {
+  Carve a;
+  const size_t lab = a.ints(cells), idx = a.ints(cells), cnt = a.ints(entries + 3), sum = a.doubles(8);
+  return {lab, idx, cnt, sum, a.total};
+}
+
+}  // namespace vof

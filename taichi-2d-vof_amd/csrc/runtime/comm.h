@@ -1,7 +1,6 @@
 // runtime/comm.h -- strips over RCCL: run-time binding (dlopen), the halo send/recv groups, the step with its exchanges
 //
-// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
 #include "step.h"
 
@@ -66,7 +65,6 @@ void comm_teardown(vof2d_ctx* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->cstream) (void)hipStreamSynchronize(h->cstream);
   h->graphs.clear_exchange();  // captured send/recv nodes hold the communicator: they go first
-  if (h->d_red) { (void)hipFree(h->d_red); h->d_red = nullptr; }
   if (h->comm && rccl()) (void)rccl()->CommDestroy(h->comm);
   h->comm = nullptr;
   if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);

@@ -1,8 +1,6 @@
 // runtime/context.h -- field ids, constants folded like the reference does, the handle (vof2d_ctx), error helpers
 //
-// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h (and diag.h in the diagnostic
-// build).  Everything here has internal linkage.
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
 #include <vector>
 
@@ -21,6 +19,7 @@
 #include "../../../include/vof2d.h"
 #include "../vof2d_kernels.h"
 #include "state.h"
+#include "buffers.h"
 
 using namespace vof;
 
@@ -196,59 +195,39 @@ struct vof2d_ctx {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int device = 0;
-  unsigned long long* d_courant = nullptr;  // device counters: [0] courant, [1] max|p_new - p| bits, [2] max|p_new| bits (residual solve)
+  WorkBufs buf;   // every device allocation but the arena (runtime/buffers.h); the typed pointers below are views into them
+  unsigned long long* d_courant = nullptr;  // buf.courant
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int64_t istep = 0;
   // conjugate-gradient pressure solve (vof_solve_p_cg): work arrays in the fields' layout, allocated by the first call
-  char* cg_arena = nullptr;     // r, two direction arrays (ping-pong), q
-  void* cg_fld[4] = {nullptr, nullptr, nullptr, nullptr};
+  void* cg_fld[4] = {nullptr, nullptr, nullptr, nullptr};   // r, two direction arrays (ping-pong), q
   double* cg_part = nullptr;    // one partial per block (kCgPart doubles), then the CG_NSCAL device scalars
   double* cg_sc = nullptr;
   int cg_s = 1;                 // which of cg_fld[1..2] holds the current direction
   // multigrid pressure solve (vof_solve_p_mg, runtime/multigrid.h): the levels below the grid, allocated by the first call
   std::vector<MgLevel> mg_lv;   // as deep as the rule allows; knob "mg_levels" caps how many a cycle visits
-  char* mg_arena = nullptr;     // e (two), f of every level >= 1; r, two directions, q of the coarsest-level solve; its scalars
-  void* mg_cgw[4] = {nullptr, nullptr, nullptr, nullptr};
+  void* mg_cgw[4] = {nullptr, nullptr, nullptr, nullptr};   // r, two directions, q of the coarsest-level solve; its scalars
   double* mg_sc = nullptr;
   int mg_nu = 2;                // knob "mg_nu": sweeps before and after the coarser levels
   int mg_levels = -1;           // knob "mg_levels": cap on the depth of a cycle (-1: none)
   int mg_graph = 1;             // knob "mg_graph": 0 launches every kernel of a cycle itself instead of replaying the captured cycle
   void* mg_key[3] = {nullptr, nullptr, nullptr};   // p, pt, rhs the cached cycle was captured with
   int mg_coarse_block = 0;      // knob "mg_coarse_block": the coarsest-level solve as one launch of one workgroup (k_mg_coarse_block) where the level is small enough
-  // vof_step_mg (runtime/step.h): the residual record on the device (kernels/mg.h, MGR_*), and what the step graphs were captured for
-  double* mg_rec = nullptr;
+  // vof_step_mg (runtime/step.h): what the step graphs were captured for
   void* step_mg_key[NFIELDS] = {};   // the field views (F and its twin apart: the graphs are keyed by the orientation)
   int step_mg_cycles = 0, step_mg_crit = 0;
-  // vof_diagnostics / vof_step_diag (runtime/diag_reduce.h): one partial per block of k_diag, and the rows recorded on the device
-  double* diag_part = nullptr;
-  double* diag_rows = nullptr;       // diag_cap rows of VOF_DIAG_N doubles, grown on demand
-  int64_t diag_cap = 0;
-  // vof_interface (runtime/interface.h): the segment count of every (row, column tile), turned into offsets in place; behind it, in
-  // the same allocation, one partial per block of k_iface and the summary; the segments, grown on demand
-  int* iface_cnt = nullptr;
-  double* iface_part = nullptr;
-  double* iface_rows = nullptr;      // iface_cap rows of VOF_IFACE_N doubles
-  int64_t iface_cap = 0;
-  // vof_blobs (runtime/blobs.h).  One allocation fixed by the geometry: parent, then labels, of every owned cell; the blob index of
-  // every root; the root count of every (row, column tile), turned into offsets in place; 8 doubles (the summary, the total of a scan).
-  // Grown on demand: the integer records of the blobs, the wave offsets and the rows of the blobs asked for, the partials of their sums
-  int* blob_lab = nullptr;
+  double* iface_part = nullptr;   // vof_interface (runtime/interface.h): the block partials, then the summary, behind the counts in buf.iface_work
+  // vof_blobs (runtime/blobs.h): the blob index of every root, the root counts, the 8 doubles behind the labels in buf.blob_work
   int* blob_idx = nullptr;
   int* blob_cnt = nullptr;
   double* blob_sum = nullptr;
-  int* blob_rec = nullptr;           // blob_rec_cap records of kBlobRec ints
-  int* blob_off = nullptr;           // blob_off_cap ints
-  double* blob_rows = nullptr;       // blob_rows_cap rows of VOF_BLOB_N doubles
-  double* blob_part = nullptr;       // blob_part_cap partials of kBlobSums doubles
-  int64_t blob_rec_cap = 0, blob_off_cap = 0, blob_rows_cap = 0, blob_part_cap = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)
   int mom_rows = 0;     // rows per wave chunk of k_momentum (0 = heuristic)
   int tb_general = 0;   // force the general (dx != dy) fused Jacobi kernel (tests: both forms on square cells)
   int tb_adapt = 1;     // fused steps: shorter chunks on the tile columns the tiny-value front is crossing (k_jacobi_tb)
-  unsigned long long* d_tbmask = nullptr;  // work plan of k_jacobi_tb (TbPlan): 2 x TB_BANDS mask words, then the plan (1 + waves entries)
-  long tbplan_cap = 0;                     // waves the plan area holds
+  unsigned long long* d_tbmask = nullptr;  // buf.tbmask
   int fctx_rows = 0;    // rows per wave chunk of k_fct_x (0 = heuristic, at most 16)
   int fctx_corr_rows = 0;  // ... of its update_uv-carrying form (0 = same rule)
   int fuse_transport = 1;  // vof_step on a full domain: update_uv and both FCT sweeps in one kernel (k_transport)
@@ -299,8 +278,6 @@ struct vof2d_ctx {
   std::vector<hipEvent_t> hev;
   bool batching = true;         // false after a failed capture of a batch: one graph launch per step from then on (build_step_batches)
   FieldState state;             // what the fields and ghost cells hold, the phase order (runtime/state.h)
-  void* vis = nullptr;      // scratch for the display fields (vof_get_vis_field / vof_interp_velocity)
-  size_t vis_bytes = 0;
   // built-in in-situ profiler (vof_profile_steps): every launch carries a start/stop event pair
   static constexpr int kMaxTimed = 96;
   hipEvent_t tev[2 * kMaxTimed] = {};
@@ -319,7 +296,6 @@ struct vof2d_ctx {
   int xchg_graph = 1;                // 0 after a failed capture (or VOF2D_XCHG_GRAPH=0): eager launches
   int64_t xchg_steps = 0;            // steps run by vof_step_exchange (the first one is always eager)
   int64_t xchg_graph_steps = 0;      // ... of which replayed from a captured graph
-  double* d_red = nullptr;           // device scalar of vof_comm_allreduce_max
   int comm_rank = 0, comm_world = 1;
   int peer_lo = -1, peer_hi = -1;  // ranks owning the rows below own_lo / above own_hi (-1: wall)
   char err[512];
@@ -340,6 +316,14 @@ namespace {
 int fail(vof2d_ctx* h, int code, const char* msg) {
   if (h) snprintf(h->err, sizeof(h->err), "%s", msg);
   return code;
+}
+hipStream_t stream_of(const vof2d_ctx* h) { return h->stream; }
+
+// `bytes` from the device to the host behind everything enqueued on the handle's stream, and the wait for them
+int read_back(vof2d_ctx* h, void* dst, const void* src, size_t bytes) {
+  HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return VOF_OK;
 }
 
 int field_id(const char* name) {

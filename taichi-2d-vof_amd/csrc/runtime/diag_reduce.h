@@ -1,8 +1,7 @@
 // runtime/diag_reduce.h -- vof_diagnostics and vof_step_diag: the handle's buffers, the launch of k_diag + k_diag_finish, the stepping loop that records rows
 //
-// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h (with state.h), launches.h, graphs.h, schedule.h, multigrid.h, step.h, diag_reduce.h, comm.h, selftest.h.  Everything here has
-// internal linkage.  (runtime/diag.h is something else: the vof_debug_* entry points of the diagnostic build.)
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
+// (runtime/diag.h is something else: the vof_debug_* entry points of the diagnostic build.)
 #pragma once
 #include "step.h"
 
@@ -10,52 +9,22 @@ namespace {
 
 static_assert(DG_N == VOF_DIAG_N && DG_CELLS == VOF_DIAG_CELLS && DG_MAX_F == VOF_DIAG_MAX_F, "kernels/diag.h and include/vof2d.h name the same slots");
 
-// The cells a handle reports: its owned interior rows, inside what it can compute (row own_hi + 1 of u is read: a strip
-// stores it as a halo row, a full domain as the wall's ghost row)
-inline void diag_rows_of(const vof2d_ctx* h, int& lo, int& hi) {
-  lo = h->d.own_lo > h->g.ilo ? h->d.own_lo : h->g.ilo;
-  hi = h->d.own_hi < h->g.ihi ? h->d.own_hi : h->g.ihi;
+// The cells a handle reports (ReportedRows, runtime/rows.h) and the geometry a launch on them gets: cg_tile cuts [g.ilo, g.ihi] into chunks
+struct Reported : ReportedRows { Geom g; };
+inline Reported reported(const vof2d_ctx* h) {
+  Reported r{reported_rows(h->d.row_lo, h->d.row_hi, h->d.own_lo, h->d.own_hi, h->d.nx, h->g.ny, h->g.ntj), h->g};
+  r.g.ilo = r.range.first; r.g.ihi = r.range.last;
+  return r;
 }
 // rows per wave chunk: the cells-per-wave rule (every chunk re-reads one row of u; few, long chunks keep the partials few)
 inline int diag_chunk(const vof2d_ctx* h) { return chunk_rows(h, h->g.ntj, 2, 16); }
-inline unsigned diag_blocks(const vof2d_ctx* h) {
-  int lo, hi;
-  diag_rows_of(h, lo, hi);
-  return hi < lo ? 0u : blocks_rows(hi - lo + 1, h->g.ntj, diag_chunk(h));
-}
 
 // The partials buffer (once) and room for `rows` rows of diagnostics on the device (grown on demand: the old rows are
 // given up, nobody reads them after the call that recorded them).  Called before anything of the call is enqueued.
 int diag_prepare(vof2d_ctx* h, int64_t rows) {
-  if (!h->diag_part) {
-    const size_t n = (size_t)diag_blocks(h) * kDiagPart + 1;
-    if (hipMalloc(reinterpret_cast<void**>(&h->diag_part), n * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      h->diag_part = nullptr;
-      return fail(h, VOF_ENOMEM, "vof_diagnostics: no memory for the reduction buffer");
-    }
-  }
-  if (rows < 1) rows = 1;
-  if (h->diag_cap >= rows) return VOF_OK;
-  if (h->diag_rows) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(h->diag_rows);
-    h->diag_rows = nullptr;
-    h->diag_cap = 0;
-  }
-  if (hipMalloc(reinterpret_cast<void**>(&h->diag_rows), (size_t)rows * DG_N * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    h->diag_rows = nullptr;
-    return fail(h, VOF_ENOMEM, "vof_step_diag: no memory for the rows");
-  }
-  h->diag_cap = rows;
-  return VOF_OK;
-}
-void diag_release(vof2d_ctx* h) {
-  if (h->diag_part) (void)hipFree(h->diag_part);
-  if (h->diag_rows) (void)hipFree(h->diag_rows);
-  h->diag_part = h->diag_rows = nullptr;
-  h->diag_cap = 0;
+  const size_t part = (size_t)reported(h).blocks(diag_chunk(h)) * kDiagPart + 1;
+  if (const int rc = h->buf.diag_part.reserve(h, part * sizeof(double), "vof_diagnostics: no memory for the reduction buffer")) return rc;
+  return h->buf.diag_rows.reserve(h, (size_t)(rows < 1 ? 1 : rows) * DG_N * sizeof(double), "vof_step_diag: no memory for the rows");
 }
 
 // One row of diagnostics of the fields as vof_get_field would return them now, into slot `slot` of the device rows:
@@ -64,16 +33,13 @@ void diag_release(vof2d_ctx* h) {
 template <typename T>
 void diag_launch(vof2d_ctx* h, int64_t slot) {
   constexpr int V = VecWidth<T>::V;
-  int lo, hi;
-  diag_rows_of(h, lo, hi);
-  const unsigned nb = diag_blocks(h);
-  Geom g = h->g;
-  g.ilo = lo; g.ihi = hi;   // (cg_tile cuts [g.ilo, g.ihi] into chunks)
+  const Reported rep = reported(h);
+  const unsigned nb = rep.blocks(diag_chunk(h));
+  double* const part = h->buf.diag_part.as<double>();
   if (nb)
-    launch(h, kOther, k_diag<T, V>, dim3(nb), 0, g, (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fU), (const T*)F_<T>(h, fV), diag_chunk(h),
-           h->cd.dxi, h->cd.dyi, h->cd.rho_g, h->cd.rho_l, h->diag_part);
-  const double cells = hi < lo ? 0.0 : (double)(hi - lo + 1) * (double)h->g.ny;
-  launch(h, kOther, k_diag_finish, dim3(1), 0, (const double*)h->diag_part, (int)nb, h->diag_rows + slot * DG_N, (double)h->istep, cells);
+    launch(h, kOther, k_diag<T, V>, dim3(nb), 0, rep.g, (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fU), (const T*)F_<T>(h, fV), diag_chunk(h),
+           h->cd.dxi, h->cd.dyi, h->cd.rho_g, h->cd.rho_l, part);
+  launch(h, kOther, k_diag_finish, dim3(1), 0, (const double*)part, (int)nb, h->buf.diag_rows.as<double>() + slot * DG_N, (double)h->istep, (double)rep.cells());
 }
 int diag_enqueue(vof2d_ctx* h, int64_t slot) {
   settle_ghosts(h);
@@ -93,10 +59,7 @@ int step_diag_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int cri
     if ((rc = diag_enqueue(h, r))) return rc;
   }
   if (nsteps % every && (rc = steps(nsteps % every))) return rc;
-  if (rows > 0) {
-    HIPCHK(h, hipMemcpyAsync(out, h->diag_rows, (size_t)rows * DG_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+  if (rows > 0 && (rc = read_back(h, out, h->buf.diag_rows.p, (size_t)rows * DG_N * sizeof(double)))) return rc;
   if (rows_written) *rows_written = rows;
   return VOF_OK;
 }

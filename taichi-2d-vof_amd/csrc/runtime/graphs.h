@@ -1,7 +1,6 @@
 // runtime/graphs.h -- the keys of the graph cache (GraphCache, context.h) and the one way a graph is captured
 //
-// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
 #include "launches.h"
 

@@ -1,7 +1,7 @@
-// runtime/multigrid.h -- the hierarchy of vof_solve_p_mg, one V-cycle (enqueued, or captured once and replayed), the driver loop
+// runtime/multigrid.h -- the work arrays of vof_solve_p_cg, the hierarchy of vof_solve_p_mg, one V-cycle (enqueued, or captured once and
+// replayed), the driver loop of both solves
 //
-// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h (with state.h), launches.h, graphs.h, schedule.h, multigrid.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
 #include "schedule.h"
 
@@ -10,26 +10,16 @@ namespace {
 // The work arrays, reduction buffer and device scalars of vof_solve_p_cg, allocated by the first call of either solver:
 // the checks of vof_solve_p_mg run the same residual kernel into the same scalars.
 int cg_prepare(vof2d_ctx* h) {
-  if (h->cg_arena) return VOF_OK;
-  const size_t fbytes = h->field_elems * h->esz;
+  if (h->buf.cg_part.p) return VOF_OK;
   const size_t nblocks = blocks_rows(interior_rows(h), h->g.ntj, 1);   // (the most blocks a launch can have: one-row chunks, knob "rows_per_wave")
-  const size_t pbytes = (nblocks * kCgPart + CG_NSCAL) * sizeof(double);
-  if (hipMalloc(reinterpret_cast<void**>(&h->cg_arena), 4 * fbytes) != hipSuccess) {
-    (void)hipGetLastError();
-    h->cg_arena = nullptr;
-    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the work arrays");
-  }
-  if (hipMalloc(reinterpret_cast<void**>(&h->cg_part), pbytes) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipFree(h->cg_arena);
-    h->cg_arena = nullptr; h->cg_part = nullptr;
-    return fail(h, VOF_ENOMEM, "vof_solve_p_cg: no memory for the reduction buffer");
-  }
-  for (int k = 0; k < 4; ++k) h->cg_fld[k] = h->cg_arena + (size_t)k * fbytes;
-  h->cg_sc = h->cg_part + nblocks * kCgPart;
-  // cells outside the interior are never written again: they stay 0 (kernels/cg.h, k_cg_apply)
-  HIPCHK(h, hipMemsetAsync(h->cg_arena, 0, 4 * fbytes, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->cg_part, 0, pbytes, h->stream));
+  const CgCarve c = carve_cg(h->field_elems * h->esz, nblocks * kCgPart, CG_NSCAL);
+  // zeroed: cells outside the interior are never written again, they stay 0 (kernels/cg.h, k_cg_apply)
+  int rc = h->buf.cg_fields.reserve(h, c.fields_total, "vof_solve_p_cg: no memory for the work arrays", true);
+  if (rc) return rc;
+  if ((rc = h->buf.cg_part.reserve(h, c.part_total, "vof_solve_p_cg: no memory for the reduction buffer", true))) return rc;
+  for (int k = 0; k < 4; ++k) h->cg_fld[k] = h->buf.cg_fields.as<char>(c.fld[k]);
+  h->cg_part = h->buf.cg_part.as<double>();
+  h->cg_sc = h->buf.cg_part.as<double>(c.sc);
   return VOF_OK;
 }
 
@@ -59,7 +49,7 @@ int mg_prepare(vof2d_ctx* h) {
   l0.g = h->g; l0.scale = 1.0; l0.bytes = h->field_elems * h->esz;
   lv.push_back(l0);
   const size_t align = 128 / h->esz;
-  size_t total = 0;
+  std::vector<size_t> bytes{l0.bytes};
   for (;;) {
     const MgLevel& f = lv.back();
     if (f.g.nx % 2 || f.g.ny % 2 || f.g.nx / 2 < 4 || f.g.ny / 2 < 4) break;
@@ -67,35 +57,22 @@ int mg_prepare(vof2d_ctx* h) {
     c.g = mg_level_geom(h, f.g.nx / 2, f.g.ny / 2);
     c.scale = f.scale * 0.25;
     c.bytes = ((size_t)(c.g.nx + 2) * (size_t)c.g.pitch + align) * h->esz;
-    total += 3 * c.bytes;
+    bytes.push_back(c.bytes);
     lv.push_back(c);
   }
   if (lv.size() > 1) {
-    total += 4 * lv[1].bytes + CG_NSCAL * sizeof(double);
-    if (hipMalloc(reinterpret_cast<void**>(&h->mg_arena), total) != hipSuccess) {
-      (void)hipGetLastError();
-      h->mg_arena = nullptr;
-      return fail(h, VOF_ENOMEM, "vof_solve_p_mg: no memory for the coarser levels");
-    }
-    // cells outside a level's interior are never written: they stay 0
-    HIPCHK(h, hipMemsetAsync(h->mg_arena, 0, total, h->stream));
-    char* at = h->mg_arena;
+    const MgCarve c = carve_mg(bytes, CG_NSCAL);
+    DevBuf& arena = h->buf.mg_arena;
+    // zeroed: cells outside a level's interior are never written, they stay 0
+    if (const int rc = arena.reserve(h, c.total, "vof_solve_p_mg: no memory for the coarser levels", true)) return rc;
     for (size_t l = 1; l < lv.size(); ++l) {
-      lv[l].e[0] = at; lv[l].e[1] = at + lv[l].bytes; lv[l].f = at + 2 * lv[l].bytes;
-      at += 3 * lv[l].bytes;
+      lv[l].e[0] = arena.as<char>(c.level[l][0]); lv[l].e[1] = arena.as<char>(c.level[l][1]); lv[l].f = arena.as<char>(c.level[l][2]);
     }
-    for (int k = 0; k < 4; ++k) { h->mg_cgw[k] = at; at += lv[1].bytes; }
-    h->mg_sc = reinterpret_cast<double*>(at);
+    for (int k = 0; k < 4; ++k) h->mg_cgw[k] = arena.as<char>(c.cgw[k]);
+    h->mg_sc = arena.as<double>(c.sc);
   }
   h->mg_lv.swap(lv);
   return VOF_OK;
-}
-void mg_release(vof2d_ctx* h) {
-  if (h->mg_arena) (void)hipFree(h->mg_arena);
-  if (h->mg_rec) (void)hipFree(h->mg_rec);
-  h->mg_arena = nullptr;
-  h->mg_rec = nullptr;
-  h->mg_lv.clear();
 }
 
 inline int mg_depth(const vof2d_ctx* h) {
@@ -151,7 +128,7 @@ void mg_enqueue_cycle(vof2d_ctx* h) {
 // vof_solve_p_mg(tol = -1, max_cycles = check_every = cycles, build_rhs = 1) runs behind the rhs the step's k_momentum
 // has formed -- the clean direction arrays (the part of them the coarsest level reads; the block kernel reads none), the
 // drift constant, the cycles, the residual -- minus the residual in front (nobody would read it) and every host wait,
-// plus the record.  The caller has run cg_prepare and mg_prepare and owns h->mg_rec.
+// plus the record.  The caller has run cg_prepare and mg_prepare and holds the record (buf.mg_rec).
 template <typename T>
 void mg_enqueue_step_solve(vof2d_ctx* h, int cycles, int criterion) {
   if (!mg_block_in_effect(h)) {
@@ -162,7 +139,7 @@ void mg_enqueue_step_solve(vof2d_ctx* h, int cycles, int criterion) {
   L<T>::cg_drift(h, L<T>::cg_sum_ap(h));
   for (int k = 0; k < cycles; ++k) mg_enqueue_cycle<T>(h);
   L<T>::cg_residual(h, 1);
-  launch_block(h, kOther, k_mg_step_record, dim3(1), 64u, 0, (const double*)h->cg_sc, h->mg_rec, criterion);
+  launch_block(h, kOther, k_mg_step_record, dim3(1), 64u, 0, (const double*)h->cg_sc, h->buf.mg_rec.as<double>(), criterion);
 }
 
 // n cycles: replays of the one captured cycle (a cycle at 1024^2 is some hundred small launches), or the launches themselves
@@ -183,6 +160,51 @@ int mg_cycles(vof2d_ctx* h, int n) {
   return VOF_OK;
 }
 
+// The driver loop of vof_solve_p_cg and vof_solve_p_mg, behind their prologues (the first residual is enqueued): read the
+// scalars; stop at the tolerance, at a non-finite field, at the cap (where `stop_ends`: at a direction with nothing to
+// divide by, CG_STOP, too: reported as it is); advance(n) enqueues n more iterations or cycles; the residual again
+// (restart: the argument of cg_residual).
+template <typename Advance>
+int solve_loop(vof2d_ctx* h, double tol, int max_iters, int check_every, int criterion, bool stop_ends, int restart, Advance advance,
+               int32_t* iters_done, double* residual, double* drift) {
+  int done = 0, rc;
+  double r = 0.0, sc[CG_NSCAL];
+  for (;;) {
+    if ((rc = ensure_ok(h)) || (rc = read_back(h, sc, h->cg_sc, sizeof(sc)))) return rc;
+    r = vof_residual_value(sc[CG_MAXZ], sc[CG_MAXP], criterion);
+    if (r <= tol || !(r < HUGE_VAL)) break;   // converged, or a non-finite field
+    if (done >= max_iters || (stop_ends && sc[CG_STOP] != 0.0)) break;
+    const int n = check_every < max_iters - done ? check_every : max_iters - done;
+    if ((rc = advance(n))) return rc;
+    done += n;
+    DISPATCH_T(h, L<double>::cg_residual(h, restart), L<float>::cg_residual(h, restart));
+  }
+  *iters_done = done;
+  *residual = r;
+  *drift = sc[CG_C];
+  return VOF_OK;
+}
+// what both solves start with, behind their clean direction arrays: the drift constant and the first residual
+void solve_prologue(vof2d_ctx* h) {
+  const double sum_ap = DISPATCH_B(h, L<double>::cg_sum_ap(h), L<float>::cg_sum_ap(h));
+  DISPATCH_T(h, (L<double>::cg_drift(h, sum_ap), L<double>::cg_residual(h, 1)), (L<float>::cg_drift(h, sum_ap), L<float>::cg_residual(h, 1)));
+}
+
+// The driver of vof_solve_p_cg (arguments checked by the entry point)
+int cg_solve(vof2d_ctx* h, double tol, int max_iters, int check_every, int criterion, int build_rhs, int32_t* iters_done,
+             double* residual, double* drift) {
+  if (const int rc = cg_prepare(h)) return rc;
+  if (build_rhs) DISPATCH_T(h, L<double>::rhs<false>(h), L<float>::rhs<false>(h));
+  // a new solve starts from the steepest-descent direction: beta = 0 and a clean direction array
+  HIPCHK(h, hipMemsetAsync(h->cg_fld[1], 0, 2 * h->field_elems * h->esz, h->stream));
+  solve_prologue(h);
+  auto advance = [h](int n) {
+    for (int k = 0; k < n; ++k) DISPATCH_T(h, L<double>::cg_iteration(h), L<float>::cg_iteration(h));
+    return (int)VOF_OK;
+  };
+  return solve_loop(h, tol, max_iters, check_every, criterion, true, 0, advance, iters_done, residual, drift);
+}
+
 // The driver of vof_solve_p_mg (arguments checked by the entry point): c, then check / cycles / check ... as vof_solve_p_cg
 int mg_solve(vof2d_ctx* h, double tol, int max_cycles, int check_every, int criterion, int build_rhs, int32_t* cycles_done,
              double* residual, double* drift) {
@@ -193,26 +215,8 @@ int mg_solve(vof2d_ctx* h, double tol, int max_cycles, int check_every, int crit
   // the coarsest-level solve starts every time from beta = 0 times the old direction: that array must be finite
   if (mg_depth(h) == 1) HIPCHK(h, hipMemsetAsync(h->cg_fld[1], 0, 2 * h->field_elems * h->esz, h->stream));
   else HIPCHK(h, hipMemsetAsync(h->mg_cgw[1], 0, 2 * h->mg_lv[1].bytes, h->stream));
-  const double sum_ap = DISPATCH_B(h, L<double>::cg_sum_ap(h), L<float>::cg_sum_ap(h));
-  DISPATCH_T(h, (L<double>::cg_drift(h, sum_ap), L<double>::cg_residual(h, 1)), (L<float>::cg_drift(h, sum_ap), L<float>::cg_residual(h, 1)));
-  int done = 0;
-  double r = 0.0, sc[CG_NSCAL];
-  for (;;) {
-    if ((rc = ensure_ok(h))) return rc;
-    HIPCHK(h, hipMemcpyAsync(sc, h->cg_sc, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    r = vof_residual_value(sc[CG_MAXZ], sc[CG_MAXP], criterion);
-    if (r <= tol || !(r < HUGE_VAL)) break;   // converged, or a non-finite field
-    if (done >= max_cycles) break;
-    const int n = check_every < max_cycles - done ? check_every : max_cycles - done;
-    if ((rc = mg_cycles(h, n))) return rc;
-    done += n;
-    DISPATCH_T(h, L<double>::cg_residual(h, 1), L<float>::cg_residual(h, 1));
-  }
-  *cycles_done = done;
-  *residual = r;
-  *drift = sc[CG_C];
-  return VOF_OK;
+  solve_prologue(h);
+  return solve_loop(h, tol, max_cycles, check_every, criterion, false, 1, [h](int n) { return mg_cycles(h, n); }, cycles_done, residual, drift);
 }
 
 }  // namespace

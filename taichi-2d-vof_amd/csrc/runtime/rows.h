@@ -3,6 +3,8 @@
 //
 // Plain C++ (no HIP): the host runtime includes it through schedule.h, the CPU tests compile it on its own.
 #pragma once
+#include <stdint.h>
+
 #include "../../../include/vof2d.h"
 
 namespace vof {
@@ -36,6 +38,20 @@ inline StripRows strip_rows(int row_lo, int row_hi, int own_lo, int own_hi, int 
   if (edge_hi) s.band_hi = {in_hi + 1, s.owned.last};
   s.rest = {in_lo, in_hi};
   return s;
+}
+
+// The cells a handle reports (vof_diagnostics, vof_interface, vof_blobs): its owned rows inside what it can compute (row
+// own_hi + 1 of u is read: a strip stores it as a halo row, a full domain as the wall's ghost row), ny columns in ntj tiles
+struct ReportedRows {
+  RowRange range;
+  int ny, ntj;
+  int rows() const { return range.rows(); }
+  int64_t cells() const { return (int64_t)rows() * ny; }
+  int64_t entries() const { return (int64_t)rows() * ntj; }   // one per (row, column tile)
+  unsigned blocks(int R) const { return (unsigned)(((long)((rows() + R - 1) / R) * ntj + 3) / 4); }   // chunks of R rows, four waves a block
+};
+inline ReportedRows reported_rows(int row_lo, int row_hi, int own_lo, int own_hi, int nx, int ny, int ntj) {
+  return {strip_rows(row_lo, row_hi, own_lo, own_hi, nx, 0).owned, ny, ntj};   // (the owned rows do not depend on the halo width)
 }
 
 // The kernels that end a step on a strip run on all owned rows at once, or on the bands first (the exchange waits for

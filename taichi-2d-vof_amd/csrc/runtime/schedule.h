@@ -1,7 +1,6 @@
 // runtime/schedule.h -- the per-step launch schedule (2dvof.py:506-528): sweeps, phases, the fused full-domain step, ghost-cell bookkeeping, graph housekeeping
 //
-// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
 #include "graphs.h"
 #include "rows.h"

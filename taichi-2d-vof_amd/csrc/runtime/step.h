@@ -1,8 +1,7 @@
 // runtime/step.h -- the scheduler behind vof_step, vof_step_phase and vof_profile_steps: which form of the batch graphs a
 // handle runs, the batches, and the three ways a step is run (inside a batch, from its own graph, eagerly)
 //
-// Part of the host-side runtime of libvof2d_hip.so; included (once, in this order) by vof2d_api.hip:
-// context.h (with state.h), launches.h, graphs.h, schedule.h, step.h, comm.h, selftest.h.  Everything here has internal linkage.
+// Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
 #include "schedule.h"
 #include "multigrid.h"
@@ -272,12 +271,8 @@ int step_mg_n(vof2d_ctx* h, int64_t nsteps, int cycles, int criterion, double* l
     int rc = cg_prepare(h);
     if (rc) return rc;
     if ((rc = mg_prepare(h))) return rc;
-    if (!h->mg_rec && hipMalloc(reinterpret_cast<void**>(&h->mg_rec), sizeof(rec)) != hipSuccess) {
-      (void)hipGetLastError();
-      h->mg_rec = nullptr;
-      return fail(h, VOF_ENOMEM, "vof_step_mg: no memory for the residual record");
-    }
-    HIPCHK(h, hipMemsetAsync(h->mg_rec, 0, sizeof(rec), h->stream));
+    if ((rc = h->buf.mg_rec.reserve(h, sizeof(rec), "vof_step_mg: no memory for the residual record"))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->buf.mg_rec.p, 0, sizeof(rec), h->stream));
     // A k_tm batch of vof_step may have left the next step's predictor formed ahead: it is formed again (k_momentum is the
     // first launch of every step here, and writes the same bits from the same u, v, F), so all that is to do is to hand
     // the handle back in the state every other entry point expects.
@@ -286,10 +281,7 @@ int step_mg_n(vof2d_ctx* h, int64_t nsteps, int cycles, int criterion, double* l
     if ((rc = step_loop(h, nsteps, !(h->d.flags & VOF_FLAG_NO_GRAPH) && h->mg_graph, &mg,
                         [h, &mg](const StepPlan& p, int64_t, int*) { return run_step_mg_graph(h, p.virt, mg); })))
       return rc;
-    if (last_residual || worst_residual || worst_step) {
-      HIPCHK(h, hipMemcpyAsync(rec, h->mg_rec, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    if ((last_residual || worst_residual || worst_step) && (rc = read_back(h, rec, h->buf.mg_rec.p, sizeof(rec)))) return rc;
   }
   if (last_residual) *last_residual = rec[MGR_LAST];
   if (worst_residual) *worst_residual = rec[MGR_WORST];

@@ -7,13 +7,16 @@
 //
 // This file holds the extern "C" entry points only: null and argument checks, the error messages, settle_ghosts, one
 // call into the runtime, what the call did to the handle's state (a call into runtime/state.h).  The runtime behind them:
-//   runtime/context.h    the handle (with its graph cache), constants
+// They are included once, in the order of the #include lines below (each names the one before it; the diagnostic build adds
+// runtime/diag.h at the end):
+//   runtime/context.h    the handle (with its graph cache), constants, read_back
+//   runtime/buffers.h    DevBuf, the owner of a device allocation, and the handle's list of them; with runtime/carve.h, plain C++: the arenas cut into ranges
 //   runtime/state.h      plain C++: what the fields and ghost cells hold (FieldState), a field written from outside, the prologue and epilogue of a step, the phase order
 //   runtime/launches.h   chunk-length heuristics, one launch wrapper per kernel (tile counts from the geometry in vof2d_device.h)
 //   runtime/graphs.h     the keys of the graph cache, the one capture helper
-//   runtime/rows.h       plain C++: the owned rows of a strip, its edge bands, the rest; what a launch of one part gets
+//   runtime/rows.h       plain C++: the owned rows of a strip, its edge bands, the rest; what a launch of one part gets; the cells a handle reports
 //   runtime/schedule.h   the per-step schedule, ghost-cell bookkeeping, dropping graphs
-//   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop
+//   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop of both
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
 //   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
 //   runtime/interface.h  the buffers, launches and copies of vof_interface
@@ -148,11 +151,11 @@ int vof_create(const vof2d_desc* d, void* stream, vof2d_handle* out) {
     h->f_home = h->fld[fF];
     h->us_home = h->fld[fUS];
     h->p_home = h->fld[fP];
-    if (hipMalloc(reinterpret_cast<void**>(&h->d_courant), 4 * sizeof(unsigned long long)) != hipSuccess) { rc = VOF_ENOMEM; break; }
-    if (hipMemsetAsync(h->d_courant, 0, 4 * sizeof(unsigned long long), h->stream) != hipSuccess) { rc = VOF_EHIP; break; }
-    const size_t tbmask_bytes = (2 * TB_BANDS * (TB_COLS / 64) + 1 + kTbPlanWaves) * sizeof(unsigned long long);   // the mask words, then the plan (context.h)
-    if (hipMalloc(reinterpret_cast<void**>(&h->d_tbmask), tbmask_bytes) != hipSuccess) { rc = VOF_ENOMEM; break; }
-    if (hipMemsetAsync(h->d_tbmask, 0, tbmask_bytes, h->stream) != hipSuccess) { rc = VOF_EHIP; break; }
+    if ((rc = h->buf.courant.reserve(h, 4 * sizeof(unsigned long long), "vof_create: no memory for the counters", true))) break;
+    const size_t tbmask_bytes = (2 * TB_BANDS * (TB_COLS / 64) + 1 + kTbPlanWaves) * sizeof(unsigned long long);   // the mask words, then the plan
+    if ((rc = h->buf.tbmask.reserve(h, tbmask_bytes, "vof_create: no memory for the work plan", true))) break;
+    h->d_courant = h->buf.courant.as<unsigned long long>();
+    h->d_tbmask = h->buf.tbmask.as<unsigned long long>();
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { rc = VOF_EHIP; break; }
     if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = VOF_EHIP; break; }
   } while (0);
@@ -179,7 +182,6 @@ int vof_destroy(vof2d_handle h) {
   if (h->ev_gas) (void)hipEventDestroy(h->ev_gas);
   if (h->h_gas) (void)hipHostFree(h->h_gas);
   comm_teardown(h);
-  if (h->vis) (void)hipFree(h->vis);
 #ifdef VOF_SHORTCUT_STATS
   {
     unsigned long long a[16] = {};
@@ -189,14 +191,7 @@ int vof_destroy(vof2d_handle h) {
               a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11]);
   }
 #endif
-  if (h->d_courant) (void)hipFree(h->d_courant);
-  if (h->d_tbmask) (void)hipFree(h->d_tbmask);
-  if (h->cg_arena) (void)hipFree(h->cg_arena);
-  if (h->cg_part) (void)hipFree(h->cg_part);
-  mg_release(h);
-  diag_release(h);
-  iface_release(h);
-  blobs_release(h);
+  h->buf.release();   // every work buffer (runtime/buffers.h)
   if (h->arena) (void)hipFree(h->arena);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -332,8 +327,7 @@ int vof_jacobi_sweeps_norms(vof2d_handle h, int32_t n, int32_t build_rhs, double
   int rc = ensure_ok(h);
   if (rc) return rc;
   unsigned long long bits[2] = {0, 0};
-  HIPCHK(h, hipMemcpyAsync(bits, h->d_courant + 1, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if ((rc = read_back(h, bits, h->d_courant + 1, sizeof(bits)))) return rc;
   memcpy(max_update, &bits[0], sizeof(double));
   memcpy(max_p, &bits[1], sizeof(double));
   return VOF_OK;
@@ -371,7 +365,7 @@ int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t 
   return vof_solve_p(h, tol, max_iters, check_every, VOF_RESID_ABS, iters_done, residual);
 }
 
-// ---- conjugate-gradient pressure solve (kernels/cg.h; cg_prepare: runtime/multigrid.h)
+// ---- conjugate-gradient pressure solve (kernels/cg.h, runtime/multigrid.h)
 int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every, int32_t criterion,
                    int32_t build_rhs, int32_t* iters_done, double* residual, double* drift) {
   if (!h || !iters_done || !residual || !drift) return VOF_EINVAL;
@@ -379,31 +373,7 @@ int vof_solve_p_cg(vof2d_handle h, double tol, int32_t max_iters, int32_t check_
   if (const int rc = check_criterion(h, criterion)) return rc;
   if (const int rc = check_whole_domain(h, "vof_solve_p_cg needs the whole domain in one handle (the dot products of a strip would need an all-reduce)")) return rc;
   settle_ghosts(h);
-  int rc = cg_prepare(h);
-  if (rc) return rc;
-  if (build_rhs) DISPATCH_T(h, L<double>::rhs<false>(h), L<float>::rhs<false>(h));
-  // a new solve starts from the steepest-descent direction: beta = 0 and a clean direction array
-  HIPCHK(h, hipMemsetAsync(h->cg_fld[1], 0, 2 * h->field_elems * h->esz, h->stream));
-  const double sum_ap = DISPATCH_B(h, L<double>::cg_sum_ap(h), L<float>::cg_sum_ap(h));
-  DISPATCH_T(h, (L<double>::cg_drift(h, sum_ap), L<double>::cg_residual(h, 1)), (L<float>::cg_drift(h, sum_ap), L<float>::cg_residual(h, 1)));
-  int done = 0;
-  double r = 0.0, sc[CG_NSCAL];
-  for (;;) {
-    if ((rc = ensure_ok(h))) return rc;
-    HIPCHK(h, hipMemcpyAsync(sc, h->cg_sc, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    r = vof_residual_value(sc[CG_MAXZ], sc[CG_MAXP], criterion);
-    if (r <= tol || !(r < HUGE_VAL)) break;   // converged, or a non-finite field
-    if (done >= max_iters || sc[CG_STOP] != 0.0) break;   // the cap, or a direction with nothing to divide by: reported as it is
-    const int n = check_every < max_iters - done ? check_every : max_iters - done;
-    for (int k = 0; k < n; ++k) DISPATCH_T(h, L<double>::cg_iteration(h), L<float>::cg_iteration(h));
-    done += n;
-    DISPATCH_T(h, L<double>::cg_residual(h, 0), L<float>::cg_residual(h, 0));
-  }
-  *iters_done = done;
-  *residual = r;
-  *drift = sc[CG_C];
-  return VOF_OK;
+  return cg_solve(h, tol, max_iters, check_every, criterion, build_rhs, iters_done, residual, drift);
 }
 
 // ---- geometric multigrid on the same equation (kernels/mg.h, runtime/multigrid.h)
@@ -435,9 +405,7 @@ int vof_diagnostics(vof2d_handle h, double* out) {
   int rc = diag_prepare(h, 1);
   if (rc) return rc;
   if ((rc = diag_enqueue(h, 0))) return rc;
-  HIPCHK(h, hipMemcpyAsync(out, h->diag_rows, VOF_DIAG_N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return VOF_OK;
+  return read_back(h, out, h->buf.diag_rows.p, VOF_DIAG_N * sizeof(double));
 }
 int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
                   int64_t* rows_written) {
@@ -473,7 +441,7 @@ int vof_blobs(vof2d_handle h, int32_t phase, double threshold, double* rows, int
   if (!(threshold > 0.0 && threshold < 1.0)) return fail(h, VOF_EINVAL, "threshold must lie in (0, 1)");
   if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
   if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_blobs keeps 32-bit keys: at most 2^31 - 1 cells");
-  if (labels && labels_bytes != (size_t)blob_cells(h) * sizeof(int32_t)) return fail(h, VOF_EINVAL, "labels_bytes is not (owned interior rows) x ny x 4");
+  if (labels && labels_bytes != (size_t)reported(h).cells() * sizeof(int32_t)) return fail(h, VOF_EINVAL, "labels_bytes is not (owned interior rows) x ny x 4");
   return blobs_run(h, phase, threshold, rows, cap_rows, labels, summary);
 }
 
@@ -551,18 +519,7 @@ int vof_copy_rows(vof2d_handle dst, vof2d_handle src, const char* name, int32_t 
 
 // 2dvof.py:458-492 -- display fields.  The image / vector field is produced on the device into a
 // scratch buffer allocated on first use and copied to the caller's dense host array.
-static int vis_scratch(vof2d_handle h, size_t bytes) {
-  if (h->vis_bytes >= bytes) return VOF_OK;
-  if (h->vis) (void)hipFree(h->vis);
-  h->vis = nullptr;
-  h->vis_bytes = 0;
-  if (hipMalloc(&h->vis, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(h, VOF_ENOMEM, "hipMalloc of the visualisation buffer failed");
-  }
-  h->vis_bytes = bytes;
-  return VOF_OK;
-}
+constexpr const char* kVisNoMem = "hipMalloc of the visualisation buffer failed";
 int vof_get_vis_field(vof2d_handle h, const char* which, void* dst, size_t nbytes) {
   if (!h || !which || !dst) return VOF_EINVAL;
   settle_ghosts(h);
@@ -571,18 +528,17 @@ int vof_get_vis_field(vof2d_handle h, const char* which, void* dst, size_t nbyte
   if (mode < 0) return fail(h, VOF_EINVAL, "display field must be vof, u, v or vnorm");
   const size_t bytes = (size_t)4 * h->g.nx * h->g.ny * h->esz;
   if (nbytes != bytes) return fail(h, VOF_EINVAL, "buffer must be (2*nx, 2*ny) of the field dtype");
-  int rc = vis_scratch(h, bytes);
+  int rc = h->buf.vis.reserve(h, bytes, kVisNoMem);
   if (rc) return rc;
   dim3 grid((2 * h->g.ny + 255) / 256, 2 * h->g.nx);
   const double umax = h->d.Lx / 0.2, vmax = h->d.Ly / 0.2;  // :468, :476, :484
   if (h->d.dtype == VOF_F64)
     launch(h, kOther, k_vis_field<double>, grid, 0, h->g, (const double*)F_<double>(h, fF), (const double*)F_<double>(h, fU),
-           (const double*)F_<double>(h, fV), (double*)h->vis, mode, umax, vmax);
+           (const double*)F_<double>(h, fV), h->buf.vis.as<double>(), mode, umax, vmax);
   else
     launch(h, kOther, k_vis_field<float>, grid, 0, h->g, (const float*)F_<float>(h, fF), (const float*)F_<float>(h, fU),
-           (const float*)F_<float>(h, fV), (float*)h->vis, mode, (float)umax, (float)vmax);
-  HIPCHK(h, hipMemcpyAsync(dst, h->vis, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+           (const float*)F_<float>(h, fV), h->buf.vis.as<float>(), mode, (float)umax, (float)vmax);
+  if ((rc = read_back(h, dst, h->buf.vis.p, bytes))) return rc;
   return ensure_ok(h);
 }
 int vof_interp_velocity(vof2d_handle h, void* dst, size_t nbytes) {
@@ -591,17 +547,16 @@ int vof_interp_velocity(vof2d_handle h, void* dst, size_t nbytes) {
   if (!full_domain(h)) return fail(h, VOF_ESTATE, "interp_velocity needs a full-domain handle");
   const size_t bytes = (size_t)2 * (h->g.nx + 2) * (h->g.ny + 2) * h->esz;
   if (nbytes != bytes) return fail(h, VOF_EINVAL, "buffer must be (nx+2, ny+2, 2) of the field dtype");
-  int rc = vis_scratch(h, bytes);
+  int rc = h->buf.vis.reserve(h, bytes, kVisNoMem);
   if (rc) return rc;
   dim3 grid((h->g.ny + 2 + 255) / 256, h->g.nx + 2);
   if (h->d.dtype == VOF_F64)
     launch(h, kOther, k_interp_velocity<double>, grid, 0, h->g, (const double*)F_<double>(h, fU),
-           (const double*)F_<double>(h, fV), (double*)h->vis);
+           (const double*)F_<double>(h, fV), h->buf.vis.as<double>());
   else
     launch(h, kOther, k_interp_velocity<float>, grid, 0, h->g, (const float*)F_<float>(h, fU),
-           (const float*)F_<float>(h, fV), (float*)h->vis);
-  HIPCHK(h, hipMemcpyAsync(dst, h->vis, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+           (const float*)F_<float>(h, fV), h->buf.vis.as<float>());
+  if ((rc = read_back(h, dst, h->buf.vis.p, bytes))) return rc;
   return ensure_ok(h);
 }
 
@@ -653,23 +608,20 @@ int vof_get_counter(vof2d_handle h, const char* name, int64_t* value) {
   if (!h || !name || !value) return VOF_EINVAL;
   if (!strcmp(name, "courant_violations")) {
     unsigned long long v = 0;
-    HIPCHK(h, hipMemcpyAsync(&v, h->d_courant, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (const int rc = read_back(h, &v, h->d_courant, sizeof(v))) return rc;
     *value = (int64_t)v;
     return VOF_OK;
   }
   if (!strcmp(name, "tb_plan_active")) {   // 1 if the last fused step's k_jacobi_tb launches ran the equal-cost work plan (tb_make_plan)
     unsigned long long v = 0;
-    HIPCHK(h, hipMemcpyAsync(&v, h->d_tbmask + 2 * TB_BANDS * (TB_COLS / 64), sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (const int rc = read_back(h, &v, h->d_tbmask + 2 * TB_BANDS * (TB_COLS / 64), sizeof(v))) return rc;
     *value = v ? 1 : 0;   // (plan[0] of an active plan carries its geometry: plan_key)
     return VOF_OK;
   }
 #ifdef VOF_WAVE_TIMES
   if (!strncmp(name, "dbg_plan_", 9)) {   // diagnostic build: the plan word in memory and the geometry a k_jacobi_pair launch would expect
     unsigned long long v = 0;
-    HIPCHK(h, hipMemcpyAsync(&v, h->d_tbmask + 2 * TB_BANDS * (TB_COLS / 64), sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (const int rc = read_back(h, &v, h->d_tbmask + 2 * TB_BANDS * (TB_COLS / 64), sizeof(v))) return rc;
     const TbPlan tp = L<double>::tb_plan(h, (int)(h->istep & 1), PlanFor::kJacobiPair);
     *value = !strcmp(name, "dbg_plan_word") ? (int64_t)v : !strcmp(name, "dbg_plan_waves") ? tp.waves : !strcmp(name, "dbg_plan_R") ? tp.R : tp.ntt;
     return VOF_OK;
@@ -802,13 +754,12 @@ int vof_comm_allreduce_max(vof2d_handle h, double* value) {
   if (!h->comm) return fail(h, VOF_ESTATE, "vof_comm_init has not been called");
   Rccl* r = rccl();
   HIPCHK(h, hipSetDevice(h->device));
-  if (!h->d_red) HIPCHK(h, hipMalloc(&h->d_red, sizeof(double)));
+  if (const int rc = h->buf.red.reserve(h, sizeof(double), "vof_comm_allreduce_max: no memory for the scalar")) return rc;
+  double* const red = h->buf.red.as<double>();
   // on the compute stream: ordered after everything enqueued so far, so it doubles as a barrier
-  HIPCHK(h, hipMemcpyAsync(h->d_red, value, sizeof(double), hipMemcpyHostToDevice, h->stream));
-  NCCLCHK(h, r->AllReduce(h->d_red, h->d_red, 1, /*ncclFloat64*/ 8, /*ncclMax*/ 2, h->comm, h->stream));
-  HIPCHK(h, hipMemcpyAsync(value, h->d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return VOF_OK;
+  HIPCHK(h, hipMemcpyAsync(red, value, sizeof(double), hipMemcpyHostToDevice, h->stream));
+  NCCLCHK(h, r->AllReduce(red, red, 1, /*ncclFloat64*/ 8, /*ncclMax*/ 2, h->comm, h->stream));
+  return read_back(h, value, red, sizeof(double));
 }
 int vof_comm_info(vof2d_handle h, int32_t* rccl_version, int32_t* graph_capture) {
   if (!h) return VOF_EINVAL;

@@ -28,6 +28,10 @@ def dtype_code(dtype):
     return {np.dtype(np.float64): _abi.VOF_F64, np.dtype(np.float32): _abi.VOF_F32}[np.dtype(dtype)]
 
 
+def criterion_code(criterion):
+    return {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+
+
 def make_desc(api, nx, ny, dtype="f64", coord_cast="f32", rows=None, own=None, jacobi_iters=10,
               device=-1, flags=0, **consts):
     """vof_desc_default + overrides.  rows=(row_lo,row_hi), own=(own_lo,own_hi)."""
@@ -152,7 +156,7 @@ class Engine:
         """vof_solve_p: sweeps until the residual (\"abs\": max|p_new - p|; \"rel\": that over
         max(max|p_new|, tiny)) is <= tol; returns (sweeps done, residual).  Same defaults as
         StripSolver.solve_p and vof_solve_p_residual (absolute criterion, a check every 10 sweeps)."""
-        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        crit = criterion_code(criterion)
         it, res = C.c_int32(), C.c_double()
         self._ck(self.api.solve_p(self._h, float(tol), int(max_iters), int(check_every), crit,
                                   C.byref(it), C.byref(res)), "solve_p")
@@ -162,7 +166,7 @@ class Engine:
         """vof_solve_p_cg: conjugate gradients on the pressure equation until max|z| (\"abs\"; \"rel\": over
         max(max|p|, tiny)) is <= tol, z = what one more Jacobi sweep would change beyond the drift constant;
         returns (iterations done, residual, drift)."""
-        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        crit = criterion_code(criterion)
         it, res, drift = C.c_int32(), C.c_double(), C.c_double()
         self._ck(self.api.solve_p_cg(self._h, float(tol), int(max_iters), int(check_every), crit,
                                      1 if build_rhs else 0, C.byref(it), C.byref(res), C.byref(drift)), "solve_p_cg")
@@ -171,7 +175,7 @@ class Engine:
     def solve_p_mg(self, tol, max_cycles, check_every=1, criterion="abs", build_rhs=True):
         """vof_solve_p_mg: V-cycles of geometric multigrid on the equation of solve_p_cg, same residual and stopping
         rule; returns (cycles done, residual, drift).  Knobs (set_param): mg_nu, mg_levels."""
-        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        crit = criterion_code(criterion)
         it, res, drift = C.c_int32(), C.c_double(), C.c_double()
         self._ck(self.api.solve_p_mg(self._h, float(tol), int(max_cycles), int(check_every), crit,
                                      1 if build_rhs else 0, C.byref(it), C.byref(res), C.byref(drift)), "solve_p_mg")
@@ -181,7 +185,7 @@ class Engine:
         """vof_step_mg: nsteps time steps whose pressure solve is `cycles` V-cycles of solve_p_mg's cycle, warm-started
         from p; returns (residual of the last step, worst residual of the call, the istep it belongs to).  One read-back,
         at the end.  Knobs (set_param): mg_nu, mg_levels, mg_graph, mg_coarse_block."""
-        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        crit = criterion_code(criterion)
         last, worst, at = C.c_double(), C.c_double(), C.c_int64()
         self._ck(self.api.step_mg(self._h, int(nsteps), int(cycles), crit, C.byref(last), C.byref(worst), C.byref(at)), "step_mg")
         return last.value, worst.value, at.value
@@ -197,7 +201,7 @@ class Engine:
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """vof_step_diag: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), a row of diagnostics recorded on
         the device behind every `every` of them, one read-back at the end; returns the (rows, VOF_DIAG_N) float64 array."""
-        crit = {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
+        crit = criterion_code(criterion)
         rows = max(int(nsteps), 0) // int(every) if int(every) >= 1 else 0
         out = np.zeros((rows, _abi.VOF_DIAG_N), dtype=np.float64)
         done = C.c_int64()
@@ -211,18 +215,10 @@ class Engine:
         slots: vof2d/interface.py) and the summary as a dict keyed by interface.SUMMARY.  One call with the capacity the
         last call needed (plus a margin); a second one if the list has outgrown it."""
         from . import interface
-        ptr = C.POINTER(C.c_double)
         summ = (C.c_double * _abi.VOF_IFACE_SUM_N)()
-        cap = getattr(self, "_iface_cap", 0)
-        while True:
-            rows = np.empty((cap, _abi.VOF_IFACE_N), dtype=np.float64)
-            self._ck(self.api.interface(self._h, float(eps), rows.ctypes.data_as(ptr) if cap else None, cap, summ), "interface")
-            n = int(summ[_abi.VOF_IFACE_SUM_SEGMENTS])
-            if n <= cap:
-                break
-            cap = n + n // 8 + 16
-        self._iface_cap = cap
-        return rows[:n].copy(), interface.summary_of(list(summ))
+        rows = self._sized_rows("_iface_cap", 0, _abi.VOF_IFACE_N, summ, _abi.VOF_IFACE_SUM_SEGMENTS, "interface",
+                                lambda ptr, cap: self.api.interface(self._h, float(eps), ptr, cap, summ))
+        return rows, interface.summary_of(list(summ))
 
     def blobs(self, phase="liquid", threshold=0.5, labels=False):
         """vof_blobs: the connected pieces of the liquid (F >= threshold) or of the gas (F < threshold) on the owned interior
@@ -231,22 +227,29 @@ class Engine:
         and, if asked for, the (owned interior rows, ny) int32 array of blob indices (-1: not a member).  One call with the
         capacity the last call needed (plus a margin); a second one if the list has outgrown it."""
         from . import blobs
-        ptr = C.POINTER(C.c_double)
         summ = (C.c_double * _abi.VOF_BLOB_SUM_N)()
         nrows = max(min(self.own_hi, self.nx) - max(self.own_lo, 1) + 1, 0)
         lab = np.empty((nrows, self.ny), dtype=np.int32) if labels else None
-        cap = getattr(self, "_blobs_cap", 16)
+        rows = self._sized_rows("_blobs_cap", 16, _abi.VOF_BLOB_N, summ, _abi.VOF_BLOB_SUM_BLOBS, "blobs",
+                                lambda ptr, cap: self.api.blobs(self._h, blobs.PHASES[phase], float(threshold), ptr, cap,
+                                                                lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None,
+                                                                lab.nbytes if labels else 0, summ))
+        out = (rows, blobs.summary_of(list(summ)))
+        return out + (lab,) if labels else out
+
+    def _sized_rows(self, cap_attr, first_cap, width, summ, count_slot, what, call):
+        """The rows of a verb that fills at most `cap` of them and reports in summ[count_slot] how many there are:
+        call(rows pointer, cap) with the capacity the last call needed (plus a margin), once more if the list has outgrown it."""
+        cap = getattr(self, cap_attr, first_cap)
         while True:
-            rows = np.empty((cap, _abi.VOF_BLOB_N), dtype=np.float64)
-            self._ck(self.api.blobs(self._h, blobs.PHASES[phase], float(threshold), rows.ctypes.data_as(ptr) if cap else None, cap,
-                                    lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None, lab.nbytes if labels else 0, summ), "blobs")
-            n = int(summ[_abi.VOF_BLOB_SUM_BLOBS])
+            rows = np.empty((cap, width), dtype=np.float64)
+            self._ck(call(rows.ctypes.data_as(C.POINTER(C.c_double)) if cap else None, cap), what)
+            n = int(summ[count_slot])
             if n <= cap:
                 break
             cap = n + n // 8 + 16
-        self._blobs_cap = cap
-        out = (rows[:n].copy(), blobs.summary_of(list(summ)))
-        return out + (lab,) if labels else out
+        setattr(self, cap_attr, cap)
+        return rows[:n].copy()
 
     def jacobi_sweeps_norms(self, n, build_rhs=True):
         """(max|p_new - p|, max|p_new|) of the last of n sweeps over the owned rows."""
