@@ -28,6 +28,7 @@
 #pragma once
 #include "momentum.h"
 #include "transport.h"
+#include "tm_segments.h"
 
 namespace vof {
 
@@ -277,9 +278,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void k
                                             const T* __restrict__ us, const T* __restrict__ vs, const T* __restrict__ p,
                                             T* __restrict__ Uo, T* __restrict__ Vo, T* __restrict__ us_out,
                                             T* __restrict__ vs_out, T* __restrict__ rhs,
-                                            unsigned long long* __restrict__ courant, int R, TbPlan tp, int first, int last,
-                                            int first2 = 1, int last2 = 0) {
-  // rows [first, last] and -- the two edge bands of a strip in one launch -- [first2, last2] (last2 < first2: none), each cut in chunks of R
+                                            unsigned long long* __restrict__ courant, TbPlan tp, TmSegments rows) {
+  // rows: up to four row ranges, each cut in chunks of its own length and handed out in order (tm_segments.h) -- the body and the
+  // shorter chunks of a full domain's tail, or the two edge bands of a strip in one launch
   constexpr int W = TmGeom<V>::W, HF = TmGeom<V>::H, STRIDE = TmGeom<V>::STRIDE;
   static_assert(HF >= 4 + 3 && HF % V == 0, "momentum's inputs must lie inside the transport march's valid columns");
   static_assert(sizeof(TbPlanShared) <= sizeof(TmRing<double, 2>) / 2, "the planner block borrows the ring's LDS");
@@ -303,14 +304,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void k
   const int lane = threadIdx.x & 63;
   const int tj = pair % ntf, ch = pair / ntf;
   const int c0 = 1 - HF + tj * STRIDE;
-  int ma = first + ch * R, lim = last;
-  if (ma > last) {         // (block-uniform)
-    const int n1 = last >= first ? (last - first + R) / R : 0;
-    ma = first2 + (ch - n1) * R;
-    lim = last2;
-    if (last2 < first2 || ma > last2) return;   // both waves leave
-  }
-  const int mb = ma + R - 1 < lim ? ma + R - 1 : lim;
+  int ma = 1, mb = 0;
+  if (!tm_chunk_rows_of(rows, ch, ma, mb)) return;   // (block-uniform) both waves leave
   // interior pair, stated as what the IN marches fold to constants: every row the pair loads, forms or tests (ma - 8 .. mb + 7: the
   // x pipeline's "row strictly inside [ilo, ihi]" tests reach ma - 7 and mb + 6) lies inside the computable rows [ilo, ihi] -- on a
   // full domain [1, nx], on a strip also inside the stored rows, whose addresses the interior marches do not clamp --, every row it

@@ -270,7 +270,11 @@ struct vof2d_ctx {
   int64_t pair_launches = 0; // k_jacobi_pair launches replayed (counter "pair_launches")
   TuneState tune;
   int64_t tm_steps = 0;      // steps replayed from k_tm batch graphs (counter "tm_steps")
-  int tm_rows = 0;          // rows per pair chunk of k_tm (0 = 32)
+  int tm_rows = 0;          // rows per pair chunk of k_tm (0 = the heuristic, L::tm_body_rows)
+  // shorter chunks for the rows k_tm hands out last (L::tm_chunk_rows): -1 by the rule, -2 the rule whatever the body's chunk length, 0 never, 1 as tm_tail_at / tm_tail_rows say
+  int tm_taper = -1;
+  int tm_tail_at[3] = {0, 0, 0}, tm_tail_rows[3] = {0, 0, 0};   // first row and chunk length of tail segment 1..3 (0: none)
+  int tm_segments_last = 0;  // row segments of the last k_tm launch enqueued (counter "tm_segments")
   int halves = -1;   // -1: where it pays (halves_eligible), 0: never, 1: wherever the schedule allows
   std::vector<hipStream_t> chain_streams;   // streams of the chains below the first
   bool halves_captured[kStepBatches] = {};   // the batch graphs of size step_batch[b] the handle holds were captured in this form

@@ -349,7 +349,7 @@ struct L {
   // k_transport of this step + k_momentum of the next in one launch (k_tm): reads fld[fF], fld[fUS], fld[fVS], fld[fP];
   // writes fld[fF2], rhs, u*' / v*' into fld[fMX] / fld[fMY] (the caller alternates the pairs and swaps F), u and v
   // only with STORE_UV; adapt_par: parity of the NEXT step (its planner block rides here as it does in k_momentum)
-  static int tm_chunk_rows(const vof2d_ctx* h, long rows, int ntf, long cap) {
+  static int tm_body_rows(const vof2d_ctx* h, long rows, int ntf, long cap) {
     if (h->tm_rows > 0) return h->tm_rows;
     long k = (rows * ntf + cap * 25) / (cap * 50);
     if (k < 2) k = 2;
@@ -358,8 +358,53 @@ struct L {
     const long R = (rows + chunks - 1) / chunks;
     return (int)(R < 16 ? 16 : (R > 96 ? 96 : R));
   }
-  // rows [first, last] and, in the same launch, [first2, last2]; store_uv: the last k_tm of a batch; rhs_id: the array the
-  // next step's rhs goes to (fRHS, or fKAPPA where the caller alternates the two: enqueue_steps_tm)
+  // The rows [first, last] of one launch as segments (kernels/tm_segments.h): the body in chunks of tm_body_rows and, behind it, up to
+  // three tail segments of shorter chunks.  The hardware hands the pairs out in index order, so the chunks of the last rows are the
+  // ones that start last, and a launch ended with whole 52-row gas chunks (87 us each) at falling occupancy: Sum durations / (span x
+  // slots) = 0.735.  Shorter chunks there fill the slots the body's pairs leave (0.82-0.85) at the price of their 14 lead-in steps.
+  // Knob tm_taper: 0 one segment (no tail); 1 the tail as the knobs tm_tail_at1..3 (first row of tail segment 1..3; 0: none) and
+  // tm_tail_rows1..3 (its chunk length) say, on any launch that takes its chunk length from here -- a segment whose first row is the
+  // next one's is empty --; -1 (the default) by the rule; -2 the rule's cut without its condition on the body's chunk length.
+  // THE RULE (kTmTaper): on a full domain whose launch runs more than one residency round with the heuristic's chunk length R >= 28,
+  // the last rows go in chunks of R / 2, R / 4 and R / 6 (at least 8) rows, as many chunk rows of each as make 30 %, 40 % and 20 % of
+  // the resident pairs (4096^2: rows 3500-3811 in 26-row chunks, 3812-4032 in 13s, 4033-4096 in 8s; 2923 -> 3885 pairs).  Swept with
+  // tools/probes/tm_taper_ab.py, every run a process of its own, the candidates alternating (profiles/tm_taper_sweep.txt), ms/step
+  // over steps 61-460, medians, off -> rule: 4096^2 dam-break 0.431 -> 0.400 (shares 30/40/0 0.405, 30/60/0 0.402, 30/60/30 0.404,
+  // 30/40/45 0.405, 20/40/0 0.409; a box earlier 15/30/0 0.396, 30/40/80 0.396, R / 4 alone 0.409 against 0.390-0.391), 4096^2 bubble
+  // 0.597 -> 0.543 (30/60/30 0.535, 30/40/0 0.548); with shares 30/40/0 and 30/40/45, between which the rule lies: 3072^2 (R = 29)
+  // 0.271 -> 0.258 / 0.263, 5120^2 0.607 -> 0.586 / 0.589, 6144^2 0.861 -> 0.844 / 0.844,
+  // 8192^2 (7.8 rounds: the tail is a small part) 1.45 -> 1.45.  2048^2 (R = 16: every tail chunk would be 8 rows, and the lead-in
+  // steps cost more than the tail gives) 0.1586 -> 0.1605: hence R >= 28, the shortest body measured to gain.  Strips, one-round
+  // launches and forced chunk lengths (tm_rows) keep one segment.
+  struct TmTaperRule { int div[3]; int share[3]; int floor_rows; int min_body_rows; };   // tail segment j: chunks of R / div[j] rows (>= floor_rows), share[j] % of the resident pairs
+  static constexpr TmTaperRule kTmTaper{{2, 4, 6}, {30, 40, 20}, 8, 28};
+  static TmSegments tm_chunk_rows(const vof2d_ctx* h, int first, int last, int ntf, long cap) {
+    const int R = tm_body_rows(h, last - first + 1, ntf, cap);
+    int at[3] = {last + 1, last + 1, last + 1}, len[3] = {1, 1, 1};
+    if (h->tm_taper > 0) {
+      int lo = first;
+      bool more = true;
+      for (int j = 0; j < 3; ++j) {
+        more = more && h->tm_tail_at[j] > 0;
+        if (more) at[j] = h->tm_tail_at[j] < lo ? lo : (h->tm_tail_at[j] > last + 1 ? last + 1 : h->tm_tail_at[j]);
+        len[j] = h->tm_tail_rows[j] > 0 ? h->tm_tail_rows[j] : 1;
+        lo = at[j];
+      }
+    } else if (h->tm_taper < 0 && h->tm_rows <= 0 && h->g.wall_lo && h->g.wall_hi && first == h->g.ilo && last == h->g.ihi &&
+               (long)tm_seg_chunks(first, last, R) * ntf > cap && (R >= kTmTaper.min_body_rows || h->tm_taper == -2)) {
+      int lo = last + 1;
+      for (int j = 2; j >= 0; --j) {
+        len[j] = R / kTmTaper.div[j] > kTmTaper.floor_rows ? R / kTmTaper.div[j] : kTmTaper.floor_rows;
+        lo -= (int)((kTmTaper.share[j] * cap + 50L * ntf) / (100L * ntf)) * len[j];   // (chunk rows of the segment) * (their length)
+        at[j] = lo;
+      }
+      if (at[0] < first + R) return tm_segments(tm_seg(first, last, R));
+    }
+    return tm_segments(tm_seg(first, at[0] - 1, R), tm_seg(at[0], at[1] - 1, len[0]), tm_seg(at[1], at[2] - 1, len[1]), tm_seg(at[2], last, len[2]));
+  }
+  // rows [first, last] and, in the same launch, [first2, last2] (a strip's two edge bands: two segments of rows_forced-row chunks);
+  // store_uv: the last k_tm of a batch; rhs_id: the array the next step's rhs goes to (fRHS, or fKAPPA where the caller alternates
+  // the two: enqueue_steps_tm)
   static void tm(vof2d_ctx* h, bool y_first, bool store_uv, int adapt_par, PlanFor plan_for, int rhs_id, int first = 1, int last = 0, int rows_forced = 0, int first2 = 1, int last2 = 0) {
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
     const int ntf = TmGeom<V>::tiles(h->g.ny);
@@ -370,11 +415,13 @@ struct L {
     // (2.5 rounds) 261 / 281 (inside / behind the front), 48 252 / 282, 52 253 / 280, 54 256 / 277, 56 257 / 284,
     // 100 376 / 381 (tools/probes/pair_bound.py --rows)
     dispatch([&](auto YF, auto UV, auto BS) {
-      const int R = rows_forced > 0 ? rows_forced : tm_chunk_rows(h, last - first + 1, ntf, resident(h, k_tm<T, V, YF(), UV(), true>, 128));
-      const unsigned pairs = (unsigned)((((last - first + R) / R) + (last2 >= first2 ? (last2 - first2 + R) / R : 0)) * ntf) + (tp.masks ? 1u : 0u);
+      const TmSegments rows = rows_forced > 0 ? tm_segments(tm_seg(first, last, rows_forced), tm_seg(first2, last2, rows_forced))
+                                              : tm_chunk_rows(h, first, last, ntf, resident(h, k_tm<T, V, YF(), UV(), true>, 128));
+      const unsigned pairs = (unsigned)(tm_chunks(rows) * ntf) + (tp.masks ? 1u : 0u);
+      h->tm_segments_last = tm_used_segments(rows);
       launch_block(h, UV() ? kTMUV : kTM, k_tm<T, V, YF(), UV(), BS()>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
                    (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
-                   F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, rhs_id), h->d_courant, R, tp, first, last, first2, last2);
+                   F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, rhs_id), h->d_courant, tp, rows);
     }, y_first, store_uv, buffer_stores_ok(h) && (h->buf_stores & 4));
   }
   // ---- conjugate gradients (kernels/cg.h)

@@ -54,7 +54,10 @@ const Knob kKnobs[] = {
   KNOB("fctx_corr_rows", fctx_corr_rows, false), KNOB("band_rows", band_rows, false), KNOB("rows_per_wave", rows_override, false),
   KNOB("fuse_transport", fuse_transport, false), KNOB("virtual_ghosts", virtual_ghosts, false), KNOB("buffer_stores", buf_stores, false),
   KNOB("overlap_halves", halves, false), KNOB("batch_steps", step_batch[0], false), KNOB("fuse_tm", fuse_tm, false),
-  KNOB("tm_rows", tm_rows, false), KNOB("jacobi_pair", jpair, false), KNOB("jacobi_pair_rows", jpair_rows, false),
+  KNOB("tm_rows", tm_rows, false), KNOB("tm_taper", tm_taper, true),
+  KNOB("tm_tail_at1", tm_tail_at[0], false), KNOB("tm_tail_at2", tm_tail_at[1], false), KNOB("tm_tail_at3", tm_tail_at[2], false),
+  KNOB("tm_tail_rows1", tm_tail_rows[0], false), KNOB("tm_tail_rows2", tm_tail_rows[1], false), KNOB("tm_tail_rows3", tm_tail_rows[2], false),
+  KNOB("jacobi_pair", jpair, false), KNOB("jacobi_pair_rows", jpair_rows, false),
   KNOB("pair_slow10", pair_slow10, false), KNOB("solve_pairs", solve_pairs, false),
   KNOB("tb_slow10", tb_slow10, false), KNOB("tune_period", tune.period, false),
   KNOB("mg_nu", mg_nu, true), KNOB("mg_levels", mg_levels, true), KNOB("mg_graph", mg_graph, true),
@@ -629,6 +632,10 @@ int vof_get_counter(vof2d_handle h, const char* name, int64_t* value) {
 #endif
   if (!strcmp(name, "pair_launches")) {   // k_jacobi_pair launches replayed from batch graphs
     *value = h->pair_launches;
+    return VOF_OK;
+  }
+  if (!strcmp(name, "tm_segments")) {   // row segments of the last k_tm launch enqueued (1: no tail; kernels/tm_segments.h)
+    *value = h->tm_segments_last;
     return VOF_OK;
   }
   if (!strcmp(name, "tm_chained_batches")) {   // k_tm batches that found the predictor of their first step in place
