@@ -321,6 +321,67 @@ int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, do
 #define VOF_BLOB_SUM_N 4
 int vof_blobs(vof2d_handle h, int32_t phase, double threshold, double* rows, int64_t cap_rows,
               int32_t* labels, size_t labels_bytes, double* summary /* VOF_BLOB_SUM_N */);
+/* Extension: where a fluid element goes.  Passive tracer particles owned by the handle, moved with the flow on the device instead of
+ * copying u, v to the host every step.  All tracer arithmetic is in double, whatever the handle's dtype: every field operand is
+ * converted to double on load (one code path).  dx, dy, dxi, dyi, Lx, Ly, dt are the Python-double values vof_get_param returns.
+ *   positions   physical, x in [0, Lx], y in [0, Ly]; cell i covers [(i - 1) dx, i dx] (the convention of vof_interface)
+ *   the fields  u[i,j] sits at ((i - 1) dx, (j - 0.5) dy), v[i,j] at ((i - 0.5) dx, (j - 1) dy), F[i,j] at ((i - 0.5) dx, (j - 0.5) dy);
+ *               ghost cells count, with the values vof_get_field would return at that moment (ghost cells a fused step left virtual
+ *               are settled first)
+ *   a sample    bilinear, of a field f at (x, y): s = x * dxi + ox, t = y * dyi + oy with (ox, oy) = (0, 0.5) for u, (0.5, 0) for v,
+ *               (0.5, 0.5) for F; ib = floor(s) + (ox == 0 ? 1 : 0) clamped to [1, nx] for u and to [0, nx] for v and F,
+ *               a = s - (ib - (ox == 0 ? 1 : 0)); likewise jb from t, clamped to [1, ny] for v and to [0, ny] for u and F, and b; then, in
+ *               exactly this order, lo = f[ib,jb] + a * (f[ib+1,jb] - f[ib,jb]), hi = f[ib,jb+1] + a * (f[ib+1,jb+1] - f[ib,jb+1]),
+ *               value = lo + b * (hi - lo).  With these clamps every load lies inside the stored (nx + 2, ny + 2) array for any position
+ *               of the closed domain, walls and corners included
+ *   an advance  by a time h, on the frozen velocity field, by the explicit midpoint rule: k1 = (u, v)(x, y); xm = x + (0.5 * h) * k1.u,
+ *               ym likewise; if xm or ym is not finite the tracer is lost, otherwise both are clamped; k2 = (u, v)(xm, ym);
+ *               x' = x + h * k2.u, y' likewise; if either is not finite the tracer is lost, otherwise both are clamped.  The clamp is
+ *               c < 0 ? 0 : (c > L ? L : c) (it keeps a NaN)
+ *   lost        a lost tracer gets x = y = NaN and is never moved or sampled again; its U, V, F read NaN.  Nothing is skipped
+ *               silently: lost tracers are counted
+ *   a row       VOF_TRACER_N doubles: X, Y and U, V, F sampled at the tracer's current position; unused slots read 0.  Rows come in
+ *               the order the tracers were given: a tracer's index is its identity for the life of the set
+ *   summary     VOF_TRACER_SUM_N doubles: COUNT, LOST, IN_LIQUID (the number with sampled F >= 0.5), ISTEP, TIME (the sum of all h
+ *               advanced since the set was given, accumulated on the host in call order); unused slots read 0
+ * The expression order is stated in csrc/kernels/tracers.h.  The counts come from 32-bit integer atomics, no floating-point atomics: the
+ * same state and calls give the same bytes.
+ *   vof_tracers_set      replaces the handle's set and zeroes TIME; n = 0 clears it.  The positions are checked on the host: one that is
+ *                        not finite or lies outside the closed domain returns VOF_EINVAL and the old set stays; so do n < 0,
+ *                        n > 2^31 - 1 and xy == NULL with n > 0
+ *   vof_tracers_advance  one advance of every tracer by `time` on the current u, v.  Enqueues only.  A non-finite time: VOF_EINVAL;
+ *                        an empty set: VOF_OK, nothing is launched
+ *   vof_tracers_get      samples U, V, F, forms the summary, synchronises and copies out.  At most cap_rows rows are written and nothing
+ *                        behind min(COUNT, cap_rows) rows is touched; the summary always describes ALL tracers, so rows = NULL with
+ *                        cap_rows = 0 reads the counts alone
+ *   vof_step_tracers     for r = 0 .. nsteps / every - 1: `every` steps -- exactly vof_step(h, every) if mg_cycles == 0, exactly
+ *                        vof_step_mg(h, every, mg_cycles, criterion, NULL, NULL, NULL) if mg_cycles >= 1 --, then one advance by
+ *                        (double)every * dt, then, if snap_every >= 1 and (r + 1) % snap_every == 0, a snapshot of all rows recorded on
+ *                        the device (COUNT x VOF_TRACER_N doubles).  A remainder of nsteps % every steps is stepped without an advance
+ *                        (TIME shows the lag).  Nothing waits for the device before the end of the call; then one copy writes the
+ *                        snapshots to snaps and *snaps_written (may be NULL) is set.  snap_every = 0 records nothing and snaps may be
+ *                        NULL.  every < 1, nsteps < 0, snap_every < 0, cap_snaps below the snapshots due, snaps == NULL with one due,
+ *                        mg_cycles < 0, a bad criterion with mg_cycles >= 1: VOF_EINVAL, the handle and the tracers untouched
+ * Whole-domain handles only (a strip returns VOF_ESTATE and is left untouched); VOF_ESTATE too while a phased step is in progress.  No
+ * field, istep, counter or cached graph changes because of tracers: a vof_step / vof_step_mg / vof_step_diag that follows gives the bits it
+ * would have given without them.  vof_set_init_F and vof_set_field leave the set alone; vof_destroy releases it. */
+#define VOF_TRACER_X 0
+#define VOF_TRACER_Y 1
+#define VOF_TRACER_U 2
+#define VOF_TRACER_V 3
+#define VOF_TRACER_F 4
+#define VOF_TRACER_N 8
+#define VOF_TRACER_SUM_COUNT 0
+#define VOF_TRACER_SUM_LOST 1
+#define VOF_TRACER_SUM_IN_LIQUID 2
+#define VOF_TRACER_SUM_ISTEP 3
+#define VOF_TRACER_SUM_TIME 4
+#define VOF_TRACER_SUM_N 8
+int vof_tracers_set(vof2d_handle h, const double* xy /* n x 2 */, int64_t n);
+int vof_tracers_advance(vof2d_handle h, double time);
+int vof_tracers_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summary /* VOF_TRACER_SUM_N */);
+int vof_step_tracers(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
+                     int64_t snap_every, double* snaps, int64_t cap_snaps, int64_t* snaps_written);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

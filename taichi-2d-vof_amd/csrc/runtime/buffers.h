@@ -65,6 +65,10 @@ struct WorkBufs {
   DevBuf blob_off;     // the wave offsets and
   DevBuf blob_rows;    // the rows (VOF_BLOB_N doubles each) of the blobs asked for,
   DevBuf blob_part;    // the partials of their sums (kBlobSums doubles each)
+  DevBuf tracer_pos;   // vof_tracers_* (runtime/tracers.h): the positions, n x 2 doubles -- state, not scratch: replaced by vof_tracers_set alone, whatever the three below do
+  DevBuf tracer_rows;  // ... the rows of vof_tracers_get (VOF_TRACER_N doubles each), grown on demand
+  DevBuf tracer_snaps; // ... the snapshots vof_step_tracers records, grown on demand
+  DevBuf tracer_cnt;   // ... the integer counters (TRC_N words), then the summary (VOF_TRACER_SUM_N doubles)
   DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
   DevBuf red;          // device scalar of vof_comm_allreduce_max
 

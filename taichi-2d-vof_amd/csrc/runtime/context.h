@@ -221,6 +221,9 @@ struct vof2d_ctx {
   int* blob_idx = nullptr;
   int* blob_cnt = nullptr;
   double* blob_sum = nullptr;
+  // vof_tracers_* (runtime/tracers.h): the tracers of buf.tracer_pos, and the time they have been advanced by since vof_tracers_set
+  int64_t tracer_n = 0;
+  double tracer_time = 0.0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

@@ -21,6 +21,7 @@
 //   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
 //   runtime/interface.h  the buffers, launches and copies of vof_interface
 //   runtime/blobs.h      the buffers, launches and copies of vof_blobs
+//   runtime/tracers.h    the buffers, launches and copies of vof_tracers_*, the loop of vof_step_tracers
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -33,6 +34,7 @@
 #include "runtime/diag_reduce.h"
 #include "runtime/interface.h"
 #include "runtime/blobs.h"
+#include "runtime/tracers.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -446,6 +448,52 @@ int vof_blobs(vof2d_handle h, int32_t phase, double threshold, double* rows, int
   if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_blobs keeps 32-bit keys: at most 2^31 - 1 cells");
   if (labels && labels_bytes != (size_t)reported(h).cells() * sizeof(int32_t)) return fail(h, VOF_EINVAL, "labels_bytes is not (owned interior rows) x ny x 4");
   return blobs_run(h, phase, threshold, rows, cap_rows, labels, summary);
+}
+
+// ---- passive tracers moved with the flow (kernels/tracers.h, runtime/tracers.h)
+namespace {
+int check_tracers_allowed(vof2d_ctx* h) {
+  if (const int rc = check_whole_domain(h, "the vof_tracers_* verbs and vof_step_tracers need the whole domain in one handle (a tracer would leave a strip's rows)")) return rc;
+  return check_no_phased_step(h);
+}
+}  // namespace
+int vof_tracers_set(vof2d_handle h, const double* xy, int64_t n) {
+  if (!h) return VOF_EINVAL;
+  if (n < 0 || n > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "n must lie in [0, 2^31 - 1]");
+  if (!xy && n > 0) return fail(h, VOF_EINVAL, "xy is NULL with n > 0");
+  if (const int rc = check_tracers_allowed(h)) return rc;
+  if (!tracer_positions_ok(h, xy, n)) return fail(h, VOF_EINVAL, "a position is not finite or lies outside [0, Lx] x [0, Ly]");
+  return tracers_set(h, xy, n);
+}
+int vof_tracers_advance(vof2d_handle h, double time) {
+  if (!h) return VOF_EINVAL;
+  if (!std::isfinite(time)) return fail(h, VOF_EINVAL, "time must be finite");
+  if (const int rc = check_tracers_allowed(h)) return rc;
+  return tracers_advance(h, time);
+}
+int vof_tracers_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summary) {
+  if (!h || !summary) return VOF_EINVAL;
+  if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
+  if (const int rc = check_tracers_allowed(h)) return rc;
+  return tracers_get(h, rows, cap_rows, summary);
+}
+int vof_step_tracers(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, int64_t snap_every, double* snaps,
+                     int64_t cap_snaps, int64_t* snaps_written) {
+  if (!h) return VOF_EINVAL;
+  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (snap_every < 0) return fail(h, VOF_EINVAL, "snap_every must be >= 0 (0: no snapshots)");
+  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
+  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  const int64_t due = tracer_snaps_due(nsteps, every, snap_every);
+  if (cap_snaps < due) return fail(h, VOF_EINVAL, "cap_snaps is smaller than the snapshots due, (nsteps / every) / snap_every");
+  if (!snaps && due > 0) return fail(h, VOF_EINVAL, "snaps is NULL and at least one snapshot is due");
+  if (const int rc = check_tracers_allowed(h)) return rc;
+  if (nsteps == 0) {
+    if (snaps_written) *snaps_written = 0;
+    return VOF_OK;
+  }
+  return step_tracers_n(h, nsteps, every, mg_cycles, criterion, snap_every, snaps, snaps_written);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

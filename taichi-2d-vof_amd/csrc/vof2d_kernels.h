@@ -23,6 +23,7 @@
 //   diag.h       k_diag, k_diag_finish   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
 //   interface.h  k_iface, k_iface_scan   (extension: the interface as PLIC segments, counted, scanned and emitted in (i, j) order)
 //   blobs.h      k_blob_init, k_blob_merge, k_blob_flatten, k_blob_number, k_blob_label, k_blob_stats, k_blob_summary, k_blob_plan, k_blob_sums, k_blob_rows   (extension: droplets and bubbles labelled by union-find, numbered by first cell, measured in a fixed order)
+//   tracers.h    k_tracer_advance, k_tracer_sample, k_tracer_finish   (extension: passive particles, one per lane: bilinear gather on the staggered grid, midpoint rule, walls)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
@@ -39,3 +40,4 @@
 #include "kernels/diag.h"
 #include "kernels/interface.h"
 #include "kernels/blobs.h"
+#include "kernels/tracers.h"

@@ -25,6 +25,11 @@ VOF_BLOB_LIQUID, VOF_BLOB_GAS = 0, 1
  VOF_BLOB_SUM_WJ, VOF_BLOB_SUM_WU, VOF_BLOB_SUM_WV) = range(12)
 VOF_BLOB_N = 16
 VOF_BLOB_SUM_BLOBS, VOF_BLOB_SUM_MEMBER_CELLS, VOF_BLOB_SUM_MAX_CELLS, VOF_BLOB_SUM_ISTEP, VOF_BLOB_SUM_N = range(5)
+# vof_tracers_*: the slots of a tracer's row and of the summary (vof2d/tracers.py)
+VOF_TRACER_X, VOF_TRACER_Y, VOF_TRACER_U, VOF_TRACER_V, VOF_TRACER_F = range(5)
+VOF_TRACER_N = 8
+VOF_TRACER_SUM_COUNT, VOF_TRACER_SUM_LOST, VOF_TRACER_SUM_IN_LIQUID, VOF_TRACER_SUM_ISTEP, VOF_TRACER_SUM_TIME = range(5)
+VOF_TRACER_SUM_N = 8
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -91,6 +96,10 @@ SIGNATURES = {
     "step_diag": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
     "interface": (C.c_int, [H, _dbl, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
     "blobs": (C.c_int, [H, _i32, _dbl, C.POINTER(_dbl), _i64, C.POINTER(_i32), C.c_size_t, C.POINTER(_dbl)]),
+    "tracers_set": (C.c_int, [H, C.POINTER(_dbl), _i64]),
+    "tracers_advance": (C.c_int, [H, _dbl]),
+    "tracers_get": (C.c_int, [H, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
+    "step_tracers": (C.c_int, [H, _i64, _i64, _i32, _i32, _i64, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
     "get_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "set_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "get_rows": (C.c_int, [H, _str, _i32, _i32, C.c_void_p, C.c_size_t]),
@@ -127,7 +136,8 @@ SIGNATURES = {
 # entry points that only the GPU library implements (timing / profiling on a HIP stream)
 GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_profile", "reset_profile",
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
-            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "blobs")
+            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "blobs",
+            "tracers_set", "tracers_advance", "tracers_get", "step_tracers")
 
 
 class Api:

@@ -77,6 +77,15 @@ def build_parser():
     ext.add_argument('--blobs-phase', choices=('liquid', 'gas'), default='liquid',
                      help='the phase whose pieces --blobs-every lists: liquid (F >= T, droplets) or gas (F < T, bubbles)')
     ext.add_argument('--blobs-threshold', type=float, default=0.5, metavar='T', help='the F that separates the phases for --blobs-every, in (0, 1)')
+    ext.add_argument('--tracers', type=int, default=0, metavar='N',
+                     help='about N passive tracer particles on a regular lattice, moved with the flow on the device (vof_step_tracers); one GPU')
+    ext.add_argument('--tracers-phase', choices=('liquid', 'gas', 'all'), default='liquid',
+                     help='which lattice points become tracers: those that start in the liquid (F >= 0.5, default), in the gas, or all')
+    ext.add_argument('--tracers-every', type=int, default=1, metavar='K',
+                     help='advance the tracers by K dt every K steps (default 1: every step)')
+    ext.add_argument('--tracers-save-every', type=int, default=None, metavar='M',
+                     help='every M steps write data/tracers_NNNNNN.npy -- rows of x, y, u, v, F per tracer, in the order they were seeded '
+                          '(vof_tracers_get) -- and append istep, time, count, lost, in_liquid to data/tracers.csv')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
 
@@ -93,6 +102,16 @@ def parse_args(argv=None):
         parser.error("--blobs-every needs N >= 1")
     if not 0.0 < args.blobs_threshold < 1.0:
         parser.error("--blobs-threshold needs 0 < T < 1")
+    if args.tracers < 0:
+        parser.error("--tracers needs N >= 0")
+    if args.tracers_every < 1:
+        parser.error("--tracers-every needs K >= 1")
+    if args.tracers_save_every is not None and args.tracers_save_every < 1:
+        parser.error("--tracers-save-every needs M >= 1")
+    if args.tracers_save_every is not None and not args.tracers:
+        parser.error("--tracers-save-every writes the tracers of --tracers N: pass that too")
+    if args.tracers and args.gpus > 1:
+        parser.error("--tracers runs on one GPU (a tracer would leave a strip's rows): drop --gpus")
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -180,9 +199,44 @@ class _Single:
         self.diag_rows = []
         if getattr(args, "mg_cycles", 0) > 0 and args.mg_coarse == "block":
             self.eng.set_param("mg_coarse_block", 1)
+        # --tracers: advanced by K dt every K steps; `tr_pending` steps have been taken since the last advance (a stop of the
+        # main loop may fall between two); TIME and the lost tracers of the run a checkpoint came from are carried beside the handle's
+        self.tr_every = args.tracers_every if getattr(args, "tracers", 0) else 0
+        self.tr_pending = 0
+        self.tr_time0 = 0.0
+        self.tr_lost0 = 0
 
     def init(self, ic):
         self.sim.set_init_F(ic)
+
+    def seed_tracers(self):
+        from . import tracers
+        return len(tracers.seed(self.eng, self.args.tracers, self.args.tracers_phase))
+
+    def tracer_rows(self):
+        """(rows, summary) with TIME and the counts continued over a resume."""
+        rows, summ = self.eng.tracers()
+        summ = dict(summ, TIME=self.tr_time0 + summ["TIME"], COUNT=summ["COUNT"] + self.tr_lost0, LOST=summ["LOST"] + self.tr_lost0)
+        return rows, summ
+
+    def save_tracers(self, path, istep):
+        rows, summ = self.tracer_rows()
+        tmp = path + ".tmp.npz"
+        np.savez(tmp, xy=rows[:, :2], time=np.float64(summ["TIME"]), istep=np.int64(istep), pending=np.int64(self.tr_pending), lost=np.int64(summ["LOST"]))
+        os.replace(tmp, path)
+
+    def load_tracers(self, path, istep):
+        """The tracers of a checkpoint, if `path` holds those of step `istep`: the positions that are not lost (a lost tracer stays
+        counted), TIME, the steps owed to the next advance.  False: there is nothing to restore, seed anew."""
+        if not os.path.exists(path):
+            return False
+        z = np.load(path, allow_pickle=False)
+        if int(z["istep"]) != istep:
+            return False
+        xy = z["xy"]
+        self.eng.tracers_set(xy[~np.isnan(xy[:, 0])])
+        self.tr_time0, self.tr_lost0, self.tr_pending = float(z["time"]), int(z["lost"]), int(z["pending"]) % self.tr_every
+        return True
 
     def load(self, fields, istep, courant=0):
         for f in STATE:
@@ -191,6 +245,28 @@ class _Single:
         self.base_courant = courant                  # (the device counter restarts at zero)
 
     def advance(self, n):
+        """n steps; with --tracers the tracers are advanced by K dt behind every K-th step counted from where they were seeded,
+        wherever the main loop stops in between."""
+        K = self.tr_every
+        if not K:
+            return self._advance(n)
+        a = self.args
+        fused = not (a.jacobi_tol > 0.0 or self.diag_in_advance or getattr(a, "mg_cycles", 0) > 0 or a.verbs)
+        dt = self.eng.get_param("dt")
+        while n > 0:
+            if self.tr_pending == 0 and n >= K and fused:
+                m = n // K * K
+                self.eng.step_tracers(m, K)          # (groups of K steps and an advance each, enqueued in one call)
+            else:
+                m = min(n, K - self.tr_pending)
+                self._advance(m)
+                self.tr_pending += m
+                if self.tr_pending == K:
+                    self.eng.tracers_advance(float(K) * dt)
+                    self.tr_pending = 0
+            n -= m
+
+    def _advance(self, n):
         a, sim = self.args, self.sim
         if a.jacobi_tol > 0.0:
             for _ in range(n):   # main loop :513-528 with the residual-terminated solve (extension)
@@ -392,6 +468,21 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         if lead:
             say(f'>>> Resumed from {args.resume} at step {istep}.')
 
+    # passive tracers (vof_tracers_*): seeded from the initial F, or restored beside the checkpoint
+    tracers_on = bool(getattr(args, "tracers", 0)) and world == 1
+    tr_save = (getattr(args, "tracers_save_every", None) or 0) if tracers_on else 0
+    tr_path = 'data/tracers.csv'
+    if tracers_on:
+        from . import tracers as tracers_mod
+        state = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'tracers_state.npz') if args.resume else None
+        if state and drv.load_tracers(state, istep):
+            say(f'>>> Tracers restored from {state}.')
+        else:
+            say(f'>>> {drv.seed_tracers()} tracers seeded ({args.tracers_phase}).')
+        if tr_save and not (args.resume and os.path.exists(tr_path) and os.path.getsize(tr_path) > 0):
+            with open(tr_path, 'w') as f:
+                f.write(tracers_mod.CSV_HEADER + '\n')
+
     diag_every = drv.diag_every
     stop_at_diag = bool(diag_every) and not drv.diag_in_advance
     diag_last = None
@@ -440,6 +531,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             n = min(n, blobs_every - i % blobs_every)
         if args.save_every:
             n = min(n, args.save_every - i % args.save_every)
+        if tr_save:
+            n = min(n, tr_save - i % tr_save)
         if args.steps:
             n = min(n, args.steps - i)
         return n
@@ -467,11 +560,18 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                 if lead:
                     with open(blobs_path, 'a') as f:
                         f.writelines(line + '\n' for line in blobs_mod.csv_lines(found[0], istep, eng.get_param("dx"), eng.get_param("dy")))
+            if tr_save and istep % tr_save == 0:
+                rows, summ = drv.tracer_rows()
+                np.save('data/tracers_%06d.npy' % istep, rows)
+                with open(tr_path, 'a') as f:
+                    f.write(tracers_mod.csv_line(dict(summ, ISTEP=istep)) + '\n')
             if args.save_every and istep % args.save_every == 0:
                 fields = {f: drv.full(f) for f in STATE}
                 warn = drv.courant()
                 if lead:
                     save_state('data/%08d.npz' % istep, fields, istep, nx, ny, args.dtype, args.ic, warn, numerics)
+                if tracers_on:
+                    drv.save_tracers('data/tracers_state.npz', istep)   # (beside the checkpoint, whose format stays as it is)
             if (istep % nstep) == 0:  # Output data every <nstep> steps            (:530)
                 warn = drv.courant()
                 extra = drv.report()

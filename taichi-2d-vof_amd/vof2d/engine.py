@@ -237,6 +237,43 @@ class Engine:
         out = (rows, blobs.summary_of(list(summ)))
         return out + (lab,) if labels else out
 
+    def tracers_set(self, xy):
+        """vof_tracers_set: replaces the handle's tracers by the (n, 2) positions xy (physical x, y inside the closed domain) and
+        zeroes TIME; an empty array clears the set."""
+        a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        self._ck(self.api.tracers_set(self._h, a.ctypes.data_as(C.POINTER(C.c_double)) if len(a) else None, len(a)), "tracers_set")
+
+    def tracers_advance(self, time):
+        """vof_tracers_advance: one midpoint-rule advance of every tracer by `time` on the current u, v (enqueues only)."""
+        self._ck(self.api.tracers_advance(self._h, float(time)), "tracers_advance")
+
+    def tracers(self, rows=True):
+        """vof_tracers_get: (rows, summary): the (COUNT, VOF_TRACER_N) float64 array of X, Y, U, V, F in the order the tracers were
+        given (the slots: vof2d/tracers.py) and the summary as a dict keyed by tracers.SUMMARY.  rows=False reads the summary
+        alone and returns (None, summary)."""
+        from . import tracers
+        summ = (C.c_double * _abi.VOF_TRACER_SUM_N)()
+        if not rows:
+            self._ck(self.api.tracers_get(self._h, None, 0, summ), "tracers_get")
+            return None, tracers.summary_of(list(summ))
+        out = self._sized_rows("_tracers_cap", 0, _abi.VOF_TRACER_N, summ, _abi.VOF_TRACER_SUM_COUNT, "tracers_get",
+                               lambda ptr, cap: self.api.tracers_get(self._h, ptr, cap, summ))
+        return out, tracers.summary_of(list(summ))
+
+    def step_tracers(self, nsteps, every=1, mg_cycles=0, criterion="rel", snap_every=0):
+        """vof_step_tracers: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), the tracers advanced by every * dt
+        behind every `every` of them, a snapshot of all rows recorded on the device behind every snap_every-th advance
+        (0: none), one read-back at the end; returns the (snapshots, COUNT, VOF_TRACER_N) float64 array."""
+        crit = criterion_code(criterion)
+        nsteps, every, snap_every = int(nsteps), int(every), int(snap_every)
+        due = (max(nsteps, 0) // every) // snap_every if every >= 1 and snap_every >= 1 else 0
+        count = int(self.tracers(rows=False)[1]["COUNT"]) if due else 0
+        out = np.zeros((due, count, _abi.VOF_TRACER_N), dtype=np.float64)
+        done = C.c_int64()
+        self._ck(self.api.step_tracers(self._h, nsteps, every, int(mg_cycles), crit, snap_every,
+                                       out.ctypes.data_as(C.POINTER(C.c_double)) if due else None, due, C.byref(done)), "step_tracers")
+        return out[:done.value]
+
     def _sized_rows(self, cap_attr, first_cap, width, summ, count_slot, what, call):
         """The rows of a verb that fills at most `cap` of them and reports in summ[count_slot] how many there are:
         call(rows pointer, cap) with the capacity the last call needed (plus a margin), once more if the list has outgrown it."""

@@ -143,6 +143,22 @@ class VOF2D:
         """Droplets or bubbles labelled and measured on the device (vof_blobs): (rows, summary[, labels]), vof2d/blobs.py."""
         return self.eng.blobs(phase, threshold, labels)
 
+    def tracers_set(self, xy):
+        """Give the handle a set of passive tracers at the (n, 2) physical positions xy (vof_tracers_set; vof2d/tracers.py: lattice, seed)."""
+        self.eng.tracers_set(xy)
+
+    def tracers_advance(self, time):
+        """Move every tracer by `time` with the current u, v (vof_tracers_advance)."""
+        self.eng.tracers_advance(time)
+
+    def tracers(self, rows=True):
+        """The tracers' rows X, Y, U, V, F and the summary (vof_tracers_get): (rows, summary), vof2d/tracers.py."""
+        return self.eng.tracers(rows)
+
+    def step_tracers(self, nsteps, every=1, mg_cycles=0, criterion="rel", snap_every=0):
+        """nsteps steps with the tracers advanced every `every` of them and snapshots recorded on the device (vof_step_tracers)."""
+        return self.eng.step_tracers(nsteps, every, mg_cycles, criterion, snap_every)
+
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)
