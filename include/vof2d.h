@@ -382,6 +382,80 @@ int vof_tracers_advance(vof2d_handle h, double time);
 int vof_tracers_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summary /* VOF_TRACER_SUM_N */);
 int vof_step_tracers(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
                      int64_t snap_every, double* snaps, int64_t cap_snaps, int64_t* snaps_written);
+/* Extension: the free-surface profile.  Both marginals of F, the top of the liquid over every row and the front on the floor, from one
+ * pass over F on the device instead of copying F to the host.  Cells: the handle's owned interior cells, i in [max(own_lo, 1),
+ * min(own_hi, nx)] -- `rows` of them, r = i - the first --, j in [1, ny]; every F is converted to double on load (one code path for both
+ * dtypes); the values are those vof_get_field would return at that moment.
+ *   depth_i[r]    the sum over j = 1 .. ny of (double)F[i,j]: times dy the liquid depth over the floor at x_i = (i - 0.5) dx (gravity is along
+ *                 j: gy = -5, gx = 0 in the reference).  The raw F, not a clamp of it: a NaN is not hidden, it reaches depth_i of its own
+ *                 row, depth_j of its own column and SUM, and nothing else
+ *   depth_j[j-1]  the sum over the owned i, ascending, of (double)F[i,j]: times dx the liquid width at height y_j = (j - 0.5) dy.  On a
+ *                 strip it is the strip's partial
+ *   top[r]        the largest j in [1, ny] with F[i,j] >= 0.5, or 0 if there is none (a NaN is not a member); int32, exact.  It includes
+ *                 spray and overturning: that is what "run-up" means
+ *   summary       VOF_DEPTH_SUM_N doubles (unused slots read 0): ROWS, ISTEP; FRONT_LO and FRONT_HI, the smallest and the largest owned i
+ *                 with F[i,1] >= 0.5 (global indices; both 0 if there is none); TOP_J the maximum of top; SUM, depth_i added in ascending
+ *                 i, one row after the other -- times dx dy the liquid volume
+ * The order of every sum is stated in csrc/kernels/depths.h and depends on the geometry alone; the integers come from 32-bit integer
+ * atomics; no floating-point atomics: the same state gives the same bytes.  Each output may be NULL (its cap only has to be >= 0 then) and
+ * is skipped; the summary always describes everything.  A non-NULL output needs cap_i >= rows, cap_j >= ny, cap_top >= rows respectively,
+ * and nothing behind rows, ny, rows elements is touched.  summary == NULL, a non-NULL output whose cap is too small, a negative cap,
+ * more than 2^31 - 1 cells: VOF_EINVAL, the handle untouched.  Works on strip handles: a driver concatenates depth_i and top in rank
+ * order, adds the depth_j partials in rank order and takes min / max of the fronts (vof2d/gauges.py, combine).  No field, istep, counter
+ * or cached graph changes, and a vof_step / vof_step_mg / vof_step_diag / vof_step_tracers that follows gives the bits it would have
+ * given without the call.  Synchronises and copies out. */
+#define VOF_DEPTH_SUM_ROWS 0
+#define VOF_DEPTH_SUM_ISTEP 1
+#define VOF_DEPTH_SUM_FRONT_LO 2  /* global row indices as doubles; 0: no liquid on the floor */
+#define VOF_DEPTH_SUM_FRONT_HI 3
+#define VOF_DEPTH_SUM_TOP_J 4
+#define VOF_DEPTH_SUM_SUM 5
+#define VOF_DEPTH_SUM_N 8
+int vof_depths(vof2d_handle h, double* depth_i, int64_t cap_i, double* depth_j, int64_t cap_j,
+               int32_t* top, int64_t cap_top, double* summary /* VOF_DEPTH_SUM_N */);
+/* Extension: fixed sensors and their time series.  A gauge is a fixed physical position in the closed domain [0, Lx] x [0, Ly], owned by
+ * the handle; what it reads is recorded on the device instead of copying F, u, v, p to the host for every sample.
+ *   a row       VOF_GAUGE_N doubles: X, Y; U, V, F the bilinear samples of the tracers (the sample of vof_tracers_*, the same offsets and
+ *               clamps); P, p sampled with F's offsets (0.5, 0.5) and clamps; DEPTH = depth_i[ig] * dy with ig = floor(X * dxi) + 1 clamped
+ *               to [1, nx], the depth_i bits those of vof_depths on the same state and dy the double of vof_get_param; TOP = (double)top[ig].
+ *               Rows come in the order the gauges were given
+ *   P           carries the arbitrary constant of the pure-Neumann pressure solve and the drift of the ten sweeps: take differences
+ *               against a gauge placed in the gas
+ *   summary     VOF_GAUGE_SUM_N doubles (unused slots read 0): COUNT, ISTEP, RECORDS (the records vof_step_gauges has taken since the set
+ *               was given)
+ *   vof_gauges_set   replaces the handle's set and zeroes RECORDS; n = 0 clears it.  The positions are checked on the host exactly as
+ *                    vof_tracers_set checks them, with the same errors; the old set stays on an error
+ *   vof_gauges_get   settles the ghost cells, runs the vof_depths pass if any gauge exists, samples, synchronises and copies out.  At most
+ *                    cap_rows rows are written and nothing behind min(COUNT, cap_rows) rows is touched
+ *   vof_step_gauges  for r = 0 .. nsteps / every - 1: `every` steps -- exactly vof_step(h, every) if mg_cycles == 0, exactly
+ *                    vof_step_mg(h, every, mg_cycles, criterion, NULL, NULL, NULL) if mg_cycles >= 1 --, then record r of COUNT x
+ *                    VOF_GAUGE_N doubles, written on the device into a buffer the handle owns (grown before anything is enqueued): bit
+ *                    for bit what vof_gauges_get yields behind the same steps.  A remainder of nsteps % every steps is stepped and gets
+ *                    no record.  Nothing waits for the device before the end of the call; then one copy writes `out` and
+ *                    *records_written (may be NULL) is set.  The argument errors are those of vof_step_diag (every < 1, nsteps < 0,
+ *                    cap_records < nsteps / every, out == NULL with a record due, mg_cycles < 0, a bad criterion with mg_cycles >= 1);
+ *                    an empty set with a record due is VOF_EINVAL too; the handle is untouched
+ * Whole-domain handles only (a strip returns VOF_ESTATE and is left untouched; vof_depths works on strips); VOF_ESTATE too while a phased
+ * step is in progress.  No field, istep, counter or cached graph changes because of gauges: every readable field, istep and
+ * courant_violations end where a single vof_step(nsteps) leaves them.  vof_set_init_F and vof_set_field leave the set alone; vof_destroy
+ * releases it. */
+#define VOF_GAUGE_X 0
+#define VOF_GAUGE_Y 1
+#define VOF_GAUGE_U 2
+#define VOF_GAUGE_V 3
+#define VOF_GAUGE_F 4
+#define VOF_GAUGE_P 5
+#define VOF_GAUGE_DEPTH 6
+#define VOF_GAUGE_TOP 7
+#define VOF_GAUGE_N 8
+#define VOF_GAUGE_SUM_COUNT 0
+#define VOF_GAUGE_SUM_ISTEP 1
+#define VOF_GAUGE_SUM_RECORDS 2
+#define VOF_GAUGE_SUM_N 8
+int vof_gauges_set(vof2d_handle h, const double* xy /* n x 2 */, int64_t n);
+int vof_gauges_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summary /* VOF_GAUGE_SUM_N */);
+int vof_step_gauges(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
+                    double* out, int64_t cap_records, int64_t* records_written);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

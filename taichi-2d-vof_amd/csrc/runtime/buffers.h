@@ -69,6 +69,10 @@ struct WorkBufs {
   DevBuf tracer_rows;  // ... the rows of vof_tracers_get (VOF_TRACER_N doubles each), grown on demand
   DevBuf tracer_snaps; // ... the snapshots vof_step_tracers records, grown on demand
   DevBuf tracer_cnt;   // ... the integer counters (TRC_N words), then the summary (VOF_TRACER_SUM_N doubles)
+  DevBuf depths_work;  // vof_depths (runtime/depths.h, DepthsCarve): the partials, depth_i, depth_j, the summary, top and the fronts' words
+  DevBuf gauge_pos;    // vof_gauges_* (runtime/depths.h): the positions, n x 2 doubles -- state, not scratch: replaced by vof_gauges_set alone
+  DevBuf gauge_rows;   // ... the rows of vof_gauges_get (VOF_GAUGE_N doubles each), grown on demand
+  DevBuf gauge_recs;   // ... the records vof_step_gauges takes, grown on demand
   DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
   DevBuf red;          // device scalar of vof_comm_allreduce_max
 

@@ -63,4 +63,18 @@ inline BlobCarve carve_blobs(size_t cells, size_t entries) {
   return {lab, idx, cnt, sum, a.total};
 }
 
+// vof_depths: the partials per (row, tile) and per (chunk, column); depth_i, depth_j and the summary; top of every row and the two
+// integer words of the fronts behind it (zeroed as one range)
+struct DepthsCarve { size_t rowpart, colpart, depth_i, depth_j, sum, top, top_bytes, total; };
+inline DepthsCarve carve_depths(size_t rows, size_t ny, size_t row_partials, size_t col_partials) {
+  Carve a;
+  DepthsCarve c;
+  c.rowpart = a.doubles(row_partials); c.colpart = a.doubles(col_partials);
+  c.depth_i = a.doubles(rows); c.depth_j = a.doubles(ny); c.sum = a.doubles(8);
+  c.top_bytes = (rows + 2) * sizeof(int);
+  c.top = a.ints(rows + 2);
+  c.total = a.total;
+  return c;
+}
+
 }  // namespace vof

@@ -224,6 +224,11 @@ struct vof2d_ctx {
   // vof_tracers_* (runtime/tracers.h): the tracers of buf.tracer_pos, and the time they have been advanced by since vof_tracers_set
   int64_t tracer_n = 0;
   double tracer_time = 0.0;
+  // vof_gauges_* (runtime/depths.h): the gauges of buf.gauge_pos, and the records vof_step_gauges has taken since vof_gauges_set
+  int64_t gauge_n = 0;
+  int64_t gauge_records = 0;
+  char* h_depths = nullptr;       // pinned host copy of the results of a vof_depths pass (one copy out, then memcpy to the caller's arrays)
+  size_t h_depths_bytes = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

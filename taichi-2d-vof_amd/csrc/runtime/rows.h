@@ -54,6 +54,35 @@ inline ReportedRows reported_rows(int row_lo, int row_hi, int own_lo, int own_hi
   return {strip_rows(row_lo, row_hi, own_lo, own_hi, nx, 0).owned, ny, ntj};   // (the owned rows do not depend on the halo width)
 }
 
+// The cells-per-wave rule of the chunk lengths (chunk_rows of runtime/launches.h, plain: ~4096 waves, a power of two between rmin
+// and rmax) on `rows` rows of `ntiles` tiles
+inline int cells_per_wave_rows(long rows, int ntiles, int rmin, int rmax) {
+  long R = rows * ntiles / 4096;
+  if (R < rmin) R = rmin;
+  if (R > rmax) R = rmax;
+  long P = 1;
+  while (P * 2 <= R) P *= 2;
+  return (int)(P < rmin ? rmin : P);
+}
+
+// vof_depths (kernels/depths.h): the chunk length -- the rule above with 2 and 32 on the rows the handle can compute,
+// max(1, row_lo + 1) .. min(nx, row_hi - 1), whatever it owns of them -- and what a launch on the reported rows leaves
+// behind: one partial per (row, tile) and per (chunk, column)
+inline int depths_chunk_rows(int row_lo, int row_hi, int nx, int ntj) {
+  const int ilo = row_lo + 1 > 1 ? row_lo + 1 : 1, ihi = row_hi - 1 < nx ? row_hi - 1 : nx;
+  return cells_per_wave_rows(ihi - ilo + 1, ntj, 2, 32);
+}
+struct DepthsGeom {
+  int R, chunks;
+  int64_t row_partials, col_partials;
+  unsigned blocks;                   // of k_depths: four waves a block (0: nothing to launch)
+  unsigned row_blocks, col_blocks;   // of k_depths_fold: 256 rows, 256 columns a block
+};
+inline DepthsGeom depths_geom(const ReportedRows& rep, int R) {
+  const int chunks = (rep.rows() + R - 1) / R;
+  return {R, chunks, rep.entries(), (int64_t)chunks * rep.ny, rep.blocks(R), (unsigned)((rep.rows() + 255) / 256), (unsigned)((rep.ny + 255) / 256)};
+}
+
 // The kernels that end a step on a strip run on all owned rows at once, or on the bands first (the exchange waits for
 // them alone) and on the rest beside the exchange.
 enum StripPart { kAllOwned = 0, kEdgeBands = 1, kRest = 2 };

@@ -22,6 +22,7 @@
 //   runtime/interface.h  the buffers, launches and copies of vof_interface
 //   runtime/blobs.h      the buffers, launches and copies of vof_blobs
 //   runtime/tracers.h    the buffers, launches and copies of vof_tracers_*, the loop of vof_step_tracers
+//   runtime/depths.h     the buffers, launches and copies of vof_depths and vof_gauges_*, the loop of vof_step_gauges
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -35,6 +36,7 @@
 #include "runtime/interface.h"
 #include "runtime/blobs.h"
 #include "runtime/tracers.h"
+#include "runtime/depths.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -186,6 +188,7 @@ int vof_destroy(vof2d_handle h) {
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_gas) (void)hipEventDestroy(h->ev_gas);
   if (h->h_gas) (void)hipHostFree(h->h_gas);
+  if (h->h_depths) (void)hipHostFree(h->h_depths);
   comm_teardown(h);
 #ifdef VOF_SHORTCUT_STATS
   {
@@ -494,6 +497,54 @@ int vof_step_tracers(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_c
     return VOF_OK;
   }
   return step_tracers_n(h, nsteps, every, mg_cycles, criterion, snap_every, snaps, snaps_written);
+}
+
+// ---- both marginals of F, the top of the liquid, the front; fixed sensors (kernels/depths.h, runtime/depths.h)
+int vof_depths(vof2d_handle h, double* depth_i, int64_t cap_i, double* depth_j, int64_t cap_j, int32_t* top, int64_t cap_top, double* summary) {
+  if (!h || !summary) return VOF_EINVAL;
+  if (cap_i < 0 || cap_j < 0 || cap_top < 0) return fail(h, VOF_EINVAL, "a cap is negative");
+  if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_depths keeps 32-bit offsets: at most 2^31 - 1 cells");
+  const int64_t rows = reported(h).rows();
+  if ((depth_i && cap_i < rows) || (top && cap_top < rows)) return fail(h, VOF_EINVAL, "cap_i or cap_top is smaller than the owned interior rows");
+  if (depth_j && cap_j < h->d.ny) return fail(h, VOF_EINVAL, "cap_j is smaller than ny");
+  return depths_run(h, depth_i, depth_j, top, summary);
+}
+namespace {
+int check_gauges_allowed(vof2d_ctx* h) {
+  if (const int rc = check_whole_domain(h, "the vof_gauges_* verbs and vof_step_gauges need the whole domain in one handle (a gauge may lie outside a strip's rows: call vof_depths on the strips)")) return rc;
+  return check_no_phased_step(h);
+}
+}  // namespace
+int vof_gauges_set(vof2d_handle h, const double* xy, int64_t n) {
+  if (!h) return VOF_EINVAL;
+  if (n < 0 || n > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "n must lie in [0, 2^31 - 1]");
+  if (!xy && n > 0) return fail(h, VOF_EINVAL, "xy is NULL with n > 0");
+  if (const int rc = check_gauges_allowed(h)) return rc;
+  if (!tracer_positions_ok(h, xy, n)) return fail(h, VOF_EINVAL, "a position is not finite or lies outside [0, Lx] x [0, Ly]");
+  return gauges_set(h, xy, n);
+}
+int vof_gauges_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summary) {
+  if (!h || !summary) return VOF_EINVAL;
+  if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
+  if (const int rc = check_gauges_allowed(h)) return rc;
+  return gauges_get(h, rows, cap_rows, summary);
+}
+int vof_step_gauges(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_records,
+                    int64_t* records_written) {
+  if (!h) return VOF_EINVAL;
+  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
+  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (cap_records < nsteps / every) return fail(h, VOF_EINVAL, "cap_records is smaller than nsteps / every");
+  if (!out && nsteps / every > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one record is due");
+  if (const int rc = check_gauges_allowed(h)) return rc;
+  if (h->gauge_n == 0 && nsteps / every > 0) return fail(h, VOF_EINVAL, "the handle has no gauges and at least one record is due");
+  if (nsteps == 0) {
+    if (records_written) *records_written = 0;
+    return VOF_OK;
+  }
+  return step_gauges_n(h, nsteps, every, mg_cycles, criterion, out, records_written);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

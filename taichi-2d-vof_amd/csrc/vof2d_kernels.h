@@ -24,6 +24,7 @@
 //   interface.h  k_iface, k_iface_scan   (extension: the interface as PLIC segments, counted, scanned and emitted in (i, j) order)
 //   blobs.h      k_blob_init, k_blob_merge, k_blob_flatten, k_blob_number, k_blob_label, k_blob_stats, k_blob_summary, k_blob_plan, k_blob_sums, k_blob_rows   (extension: droplets and bubbles labelled by union-find, numbered by first cell, measured in a fixed order)
 //   tracers.h    k_tracer_advance, k_tracer_sample, k_tracer_finish   (extension: passive particles, one per lane: bilinear gather on the staggered grid, midpoint rule, walls)
+//   depths.h     k_depths, k_depths_fold, k_depths_finish, k_gauge_sample   (extension: both marginals of F, the top of the liquid per row and the front in one pass over F; fixed sensors that sample u, v, F, p and read them)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
@@ -41,3 +42,4 @@
 #include "kernels/interface.h"
 #include "kernels/blobs.h"
 #include "kernels/tracers.h"
+#include "kernels/depths.h"

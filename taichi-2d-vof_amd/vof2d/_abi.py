@@ -30,6 +30,12 @@ VOF_TRACER_X, VOF_TRACER_Y, VOF_TRACER_U, VOF_TRACER_V, VOF_TRACER_F = range(5)
 VOF_TRACER_N = 8
 VOF_TRACER_SUM_COUNT, VOF_TRACER_SUM_LOST, VOF_TRACER_SUM_IN_LIQUID, VOF_TRACER_SUM_ISTEP, VOF_TRACER_SUM_TIME = range(5)
 VOF_TRACER_SUM_N = 8
+# vof_depths and vof_gauges_*: the slots of the summaries and of a gauge's row (vof2d/gauges.py)
+VOF_DEPTH_SUM_ROWS, VOF_DEPTH_SUM_ISTEP, VOF_DEPTH_SUM_FRONT_LO, VOF_DEPTH_SUM_FRONT_HI, VOF_DEPTH_SUM_TOP_J, VOF_DEPTH_SUM_SUM = range(6)
+VOF_DEPTH_SUM_N = 8
+VOF_GAUGE_X, VOF_GAUGE_Y, VOF_GAUGE_U, VOF_GAUGE_V, VOF_GAUGE_F, VOF_GAUGE_P, VOF_GAUGE_DEPTH, VOF_GAUGE_TOP, VOF_GAUGE_N = range(9)
+VOF_GAUGE_SUM_COUNT, VOF_GAUGE_SUM_ISTEP, VOF_GAUGE_SUM_RECORDS = range(3)
+VOF_GAUGE_SUM_N = 8
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -100,6 +106,10 @@ SIGNATURES = {
     "tracers_advance": (C.c_int, [H, _dbl]),
     "tracers_get": (C.c_int, [H, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
     "step_tracers": (C.c_int, [H, _i64, _i64, _i32, _i32, _i64, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
+    "depths": (C.c_int, [H, C.POINTER(_dbl), _i64, C.POINTER(_dbl), _i64, C.POINTER(_i32), _i64, C.POINTER(_dbl)]),
+    "gauges_set": (C.c_int, [H, C.POINTER(_dbl), _i64]),
+    "gauges_get": (C.c_int, [H, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
+    "step_gauges": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
     "get_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "set_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "get_rows": (C.c_int, [H, _str, _i32, _i32, C.c_void_p, C.c_size_t]),
@@ -137,7 +147,7 @@ SIGNATURES = {
 GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_profile", "reset_profile",
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
             "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "blobs",
-            "tracers_set", "tracers_advance", "tracers_get", "step_tracers")
+            "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges")
 
 
 class Api:

@@ -86,6 +86,17 @@ def build_parser():
     ext.add_argument('--tracers-save-every', type=int, default=None, metavar='M',
                      help='every M steps write data/tracers_NNNNNN.npy -- rows of x, y, u, v, F per tracer, in the order they were seeded '
                           '(vof_tracers_get) -- and append istep, time, count, lost, in_liquid to data/tracers.csv')
+    ext.add_argument('--gauge', action='append', default=[], metavar='X,Y',
+                     help='a fixed sensor at the physical position X,Y inside the closed domain (repeatable): u, v, F, p sampled there, the '
+                          'liquid depth over the floor and the top of the liquid at X, read on the device (vof_gauges_*); one GPU')
+    ext.add_argument('--gauges-file', default=None, metavar='FILE', help='more gauges, one `x y` per line (# starts a comment)')
+    ext.add_argument('--gauges-every', type=int, default=None, metavar='N',
+                     help='every N steps append one line per gauge to data/gauges.csv: istep, gauge, x, y, u, v, f, p, depth, top '
+                          '(vof_step_gauges; with --jacobi-tol, --verbs, --mg-cycles, --diag-every or --tracers vof_gauges_get at the multiples of N)')
+    ext.add_argument('--depths-every', type=int, default=None, metavar='N',
+                     help='every N steps write data/depths_NNNNNN.npy -- rows of x_i, liquid depth over the floor in metres, top j of the '
+                          'liquid per grid row, from one pass over F on the device (vof_depths) -- and append istep, front_lo, front_hi, '
+                          'top, volume to data/depths.csv; works with --gpus N')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
 
@@ -112,6 +123,15 @@ def parse_args(argv=None):
         parser.error("--tracers-save-every writes the tracers of --tracers N: pass that too")
     if args.tracers and args.gpus > 1:
         parser.error("--tracers runs on one GPU (a tracer would leave a strip's rows): drop --gpus")
+    if args.gauges_every is not None and args.gauges_every < 1:
+        parser.error("--gauges-every needs N >= 1")
+    if args.depths_every is not None and args.depths_every < 1:
+        parser.error("--depths-every needs N >= 1")
+    if (args.gauge or args.gauges_file or args.gauges_every is not None) and args.gpus > 1:
+        parser.error("--gauge, --gauges-file and --gauges-every run on one GPU (a gauge reads rows a strip may not hold): drop --gpus, "
+                     "or use --depths-every, which works on strips")
+    if args.gauges_every is not None and not (args.gauge or args.gauges_file or args.resume):
+        parser.error("--gauges-every records the gauges of --gauge X,Y / --gauges-file FILE: pass at least one")
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -205,6 +225,45 @@ class _Single:
         self.tr_pending = 0
         self.tr_time0 = 0.0
         self.tr_lost0 = 0
+        # --gauges-every: the plain fused steps take their records on the device (vof_step_gauges); every other loop is cut at
+        # the multiples of N and asks there (vof_gauges_get)
+        self.gauges_every = getattr(args, "gauges_every", None) or 0
+        self.gauges_in_advance = bool(self.gauges_every) and not (args.jacobi_tol > 0.0 or args.verbs or self.diag_in_advance
+                                                                  or getattr(args, "mg_cycles", 0) > 0 or self.tr_every)
+        self.gauge_recs = []                         # (istep, rows) not yet written
+
+    def set_gauges(self, xy):
+        self.eng.gauges_set(xy)
+
+    def save_gauges(self, path, istep):
+        rows, _ = self.eng.gauges_get()
+        tmp = path + ".tmp.npz"
+        np.savez(tmp, xy=rows[:, :2], istep=np.int64(istep))
+        os.replace(tmp, path)
+
+    def record_gauges(self):
+        self.gauge_recs.append((self.sim.istep, self.eng.gauges_get()[0]))
+
+    def take_gauges(self):
+        recs, self.gauge_recs = self.gauge_recs, []
+        return recs
+
+    def depths(self):
+        return self.eng.depths()
+
+    def _advance_gauges(self, n):
+        """n fused steps with a record at every multiple of N: plain steps up to the first multiple (a resumed run may start
+        anywhere), then one vof_step_gauges for the rest."""
+        N = self.gauges_every
+        head = min(n, -self.sim.istep % N)
+        if head:
+            self.sim.step(head)
+            if self.sim.istep % N == 0:
+                self.record_gauges()
+        if n - head:
+            first = self.sim.istep
+            recs = self.sim.step_gauges(n - head, N)
+            self.gauge_recs += [(first + (r + 1) * N, rows) for r, rows in enumerate(recs)]
 
     def init(self, ic):
         self.sim.set_init_F(ic)
@@ -282,6 +341,8 @@ class _Single:
                 sim.solve_VOF_rudman(sim.istep); sim.post_process_f(); sim.set_BC()
         elif self.diag_in_advance:
             self._advance_diag(n)
+        elif self.gauges_in_advance:
+            self._advance_gauges(n)
         elif getattr(a, "mg_cycles", 0) > 0:
             self._step_mg(n)
         elif a.verbs:
@@ -381,6 +442,9 @@ class _Strips:
             e.update_uv(); e.set_BC()
             e.solve_VOF_rudman(e.istep); e.post_process_f(); e.set_BC()
             self.s.exchange()                         # F, u, v, p: the 8 rows the step consumed are well inside the halo
+
+    def depths(self):
+        return self.s.depths()                       # (collective: rank 0 holds the domain's profile, the others None)
 
     def record_diag(self):
         self.diag_rows.append(self.s.diagnostics())   # (collective: every rank holds the combined row, rank 0 writes it)
@@ -483,6 +547,35 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             with open(tr_path, 'w') as f:
                 f.write(tracers_mod.CSV_HEADER + '\n')
 
+    # fixed sensors (vof_gauges_*): from the command line, or the set beside the checkpoint
+    gauges_every = (getattr(args, "gauges_every", None) or 0) if world == 1 else 0
+    gauges_on, gauges_path = False, 'data/gauges.csv'
+    if world == 1 and (getattr(args, "gauge", None) or getattr(args, "gauges_file", None) or gauges_every):
+        from . import gauges as gauges_mod
+        xy = gauges_mod.parse_positions(args.gauge, args.gauges_file)
+        state = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'gauges_state.npz') if args.resume else None
+        if not len(xy) and state and os.path.exists(state):
+            xy = np.load(state, allow_pickle=False)["xy"]
+            say(f'>>> Gauges restored from {state}.')
+        if not len(xy):
+            raise SystemExit("--gauges-every: no gauges given and none beside the checkpoint (--gauge X,Y, --gauges-file FILE)")
+        drv.set_gauges(xy)
+        gauges_on = True
+        say(f'>>> {len(xy)} gauges set.')
+        if gauges_every and not (args.resume and os.path.exists(gauges_path) and os.path.getsize(gauges_path) > 0):
+            with open(gauges_path, 'w') as f:
+                f.write(gauges_mod.GAUGES_CSV_HEADER + '\n')
+    stop_at_gauges = bool(gauges_every) and not drv.gauges_in_advance
+
+    # the free-surface profile (vof_depths) is read between calls, like the interface
+    depths_every = getattr(args, "depths_every", None) or 0
+    depths_path = 'data/depths.csv'
+    if depths_every:
+        from . import gauges as gauges_mod
+        if lead and not (args.resume and os.path.exists(depths_path) and os.path.getsize(depths_path) > 0):
+            with open(depths_path, 'w') as f:
+                f.write(gauges_mod.DEPTHS_CSV_HEADER + '\n')
+
     diag_every = drv.diag_every
     stop_at_diag = bool(diag_every) and not drv.diag_in_advance
     diag_last = None
@@ -533,6 +626,10 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             n = min(n, args.save_every - i % args.save_every)
         if tr_save:
             n = min(n, tr_save - i % tr_save)
+        if stop_at_gauges:
+            n = min(n, gauges_every - i % gauges_every)
+        if depths_every:
+            n = min(n, depths_every - i % depths_every)
         if args.steps:
             n = min(n, args.steps - i)
         return n
@@ -565,6 +662,21 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                 np.save('data/tracers_%06d.npy' % istep, rows)
                 with open(tr_path, 'a') as f:
                     f.write(tracers_mod.csv_line(dict(summ, ISTEP=istep)) + '\n')
+            if gauges_every:
+                if stop_at_gauges and istep % gauges_every == 0:
+                    drv.record_gauges()
+                recs = drv.take_gauges()
+                if recs:
+                    with open(gauges_path, 'a') as f:
+                        for k, rows in recs:
+                            f.writelines(line + '\n' for line in gauges_mod.gauges_csv_lines(k, rows))
+            if depths_every and istep % depths_every == 0:
+                prof = drv.depths()
+                if lead:
+                    d = gauges_mod.derive(prof[0], prof[3], eng.get_param("dx"), eng.get_param("dy"))
+                    np.save('data/depths_%06d.npy' % istep, np.stack([d["x"], d["depth"], prof[2].astype(np.float64)], axis=1))
+                    with open(depths_path, 'a') as f:
+                        f.write(gauges_mod.depths_csv_line(dict(prof[3], ISTEP=istep), eng.get_param("dx"), eng.get_param("dy")) + '\n')
             if args.save_every and istep % args.save_every == 0:
                 fields = {f: drv.full(f) for f in STATE}
                 warn = drv.courant()
@@ -572,6 +684,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                     save_state('data/%08d.npz' % istep, fields, istep, nx, ny, args.dtype, args.ic, warn, numerics)
                 if tracers_on:
                     drv.save_tracers('data/tracers_state.npz', istep)   # (beside the checkpoint, whose format stays as it is)
+                if gauges_on:
+                    drv.save_gauges('data/gauges_state.npz', istep)
             if (istep % nstep) == 0:  # Output data every <nstep> steps            (:530)
                 warn = drv.courant()
                 extra = drv.report()

@@ -274,6 +274,52 @@ class Engine:
                                        out.ctypes.data_as(C.POINTER(C.c_double)) if due else None, due, C.byref(done)), "step_tracers")
         return out[:done.value]
 
+    def depths(self):
+        """vof_depths: one pass over F on the owned interior cells; returns (depth_i, depth_j, top, summary): the sums of F
+        along j per owned row and along the owned i per column (float64), the largest j with F >= 0.5 per owned row (int32,
+        0: none) and the summary as a dict keyed by gauges.DEPTH_SUMMARY (a strip's value is its partial: gauges.combine;
+        the physical quantities: gauges.derive)."""
+        from . import gauges
+        rows = max(min(self.own_hi, self.nx) - max(self.own_lo, 1) + 1, 0)
+        di, dj, top = np.empty(rows, dtype=np.float64), np.empty(self.ny, dtype=np.float64), np.empty(rows, dtype=np.int32)
+        summ = (C.c_double * _abi.VOF_DEPTH_SUM_N)()
+        self._ck(self.api.depths(self._h, di.ctypes.data_as(C.POINTER(C.c_double)) if rows else None, rows, dj.ctypes.data_as(C.POINTER(C.c_double)), self.ny,
+                                 top.ctypes.data_as(C.POINTER(C.c_int32)) if rows else None, rows, summ), "depths")
+        return di, dj, top, gauges.depth_summary_of(list(summ))
+
+    def gauges_set(self, xy):
+        """vof_gauges_set: replaces the handle's gauges by the (n, 2) positions xy (physical x, y inside the closed domain) and
+        zeroes RECORDS; an empty array clears the set."""
+        a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        self._ck(self.api.gauges_set(self._h, a.ctypes.data_as(C.POINTER(C.c_double)) if len(a) else None, len(a)), "gauges_set")
+
+    def gauges_get(self, rows=True):
+        """vof_gauges_get: (rows, summary): the (COUNT, VOF_GAUGE_N) float64 array of X, Y, U, V, F, P, DEPTH, TOP in the order
+        the gauges were given (the slots: vof2d/gauges.py) and the summary as a dict keyed by gauges.SUMMARY.  rows=False
+        reads the summary alone and returns (None, summary)."""
+        from . import gauges
+        summ = (C.c_double * _abi.VOF_GAUGE_SUM_N)()
+        if not rows:
+            self._ck(self.api.gauges_get(self._h, None, 0, summ), "gauges_get")
+            return None, gauges.summary_of(list(summ))
+        out = self._sized_rows("_gauges_cap", 0, _abi.VOF_GAUGE_N, summ, _abi.VOF_GAUGE_SUM_COUNT, "gauges_get",
+                               lambda ptr, cap: self.api.gauges_get(self._h, ptr, cap, summ))
+        return out, gauges.summary_of(list(summ))
+
+    def step_gauges(self, nsteps, every=1, mg_cycles=0, criterion="rel"):
+        """vof_step_gauges: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), a record of every gauge taken on
+        the device behind every `every` of them, one read-back at the end; returns the (records, COUNT, VOF_GAUGE_N)
+        float64 array."""
+        crit = criterion_code(criterion)
+        nsteps, every = int(nsteps), int(every)
+        due = max(nsteps, 0) // every if every >= 1 else 0
+        count = int(self.gauges_get(rows=False)[1]["COUNT"]) if due else 0
+        out = np.zeros((due, count, _abi.VOF_GAUGE_N), dtype=np.float64)
+        done = C.c_int64()
+        self._ck(self.api.step_gauges(self._h, nsteps, every, int(mg_cycles), crit,
+                                      out.ctypes.data_as(C.POINTER(C.c_double)) if due else None, due, C.byref(done)), "step_gauges")
+        return out[:done.value]
+
     def _sized_rows(self, cap_attr, first_cap, width, summ, count_slot, what, call):
         """The rows of a verb that fills at most `cap` of them and reports in summ[count_slot] how many there are:
         call(rows pointer, cap) with the capacity the last call needed (plus a margin), once more if the list has outgrown it."""

@@ -159,6 +159,23 @@ class VOF2D:
         """nsteps steps with the tracers advanced every `every` of them and snapshots recorded on the device (vof_step_tracers)."""
         return self.eng.step_tracers(nsteps, every, mg_cycles, criterion, snap_every)
 
+    def depths(self):
+        """Both marginals of F, the top of the liquid per row and the front on the floor from one pass on the device (vof_depths):
+        (depth_i, depth_j, top, summary), vof2d/gauges.py."""
+        return self.eng.depths()
+
+    def gauges_set(self, xy):
+        """Give the handle fixed sensors at the (n, 2) physical positions xy (vof_gauges_set)."""
+        self.eng.gauges_set(xy)
+
+    def gauges_get(self, rows=True):
+        """What the gauges read now: rows X, Y, U, V, F, P, DEPTH, TOP and the summary (vof_gauges_get): (rows, summary), vof2d/gauges.py."""
+        return self.eng.gauges_get(rows)
+
+    def step_gauges(self, nsteps, every=1, mg_cycles=0, criterion="rel"):
+        """nsteps steps with a record of every gauge taken on the device every `every` steps (vof_step_gauges)."""
+        return self.eng.step_gauges(nsteps, every, mg_cycles, criterion)
+
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)

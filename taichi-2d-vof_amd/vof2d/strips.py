@@ -498,6 +498,17 @@ class StripSolver:
         out = blobs.combine(parts, self.ny)
         return out if labels else out[:2]
 
+    def depths(self):
+        """vof_depths of the whole domain on rank 0 (None elsewhere): every strip runs the pass on its own rows, rank 0 gathers
+        (depth_i, depth_j, top, summary) in rank order and joins them (gauges.combine): depth_i and top concatenated, the
+        depth_j partials and SUM added in rank order, min / max for the fronts.  world == 1: the single-domain value."""
+        from . import gauges
+        mine = self.eng.depths()
+        if self.world == 1:
+            return mine
+        parts = self.comm.gather_object(mine)
+        return gauges.combine(parts) if self.rank == 0 else None
+
     def sync(self):
         self.eng.sync()
 
