@@ -456,6 +456,55 @@ int vof_gauges_set(vof2d_handle h, const double* xy /* n x 2 */, int64_t n);
 int vof_gauges_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summary /* VOF_GAUGE_SUM_N */);
 int vof_step_gauges(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
                     double* out, int64_t cap_records, int64_t* records_written);
+/* Extension: a dye.  A second colour function C in the layout of F, owned by the handle and carried by the same transport as F: where the
+ * liquid of a drop ends up, how much of one body reaches a wall, how well two bodies have mixed.  A dye seeded equal to F stays equal to F
+ * bit for bit.
+ *   vof_dye_set      src: a dense (nx+2, ny+2) array of the handle's dtype, ghost cells included, stored as given (the vof_set_field
+ *                    convention; no boundary pass runs).  Replaces the handle's dye; src == NULL with nbytes == 0 releases it.  A wrong
+ *                    nbytes is VOF_EINVAL and the old dye stays.  The values are expected to be finite
+ *   vof_dye_get      the same layout; synchronises
+ *   vof_dye_advance  one transport of the dye on the u, v vof_get_field would return at that moment (ghost cells a fused step left
+ *                    virtual are settled first), with the handle's istep: solve_VOF_rudman(istep) (2dvof.py:312-318) with C for F, then
+ *                    post_process_f (:452-455), then the F lines of set_BC (:168, 174, 181, 187) on C.  Enqueues only
+ *   vof_dye_stats    one row of VOF_DYE_N doubles (unused slots read 0) reduced over the interior cells, every operand converted to
+ *                    double: ISTEP, CELLS; SUM_C; SUM_CI, SUM_CJ (sum C * i, sum C * j, global integer indices as in vof_diagnostics);
+ *                    SUM_C2; SUM_CF = sum C * Fc with the plain clamp Fc of vof_diagnostics; SUM_CU, SUM_CV = sum C * uc, sum C * vc with
+ *                    uc, vc of interp_velocity in the expressions of vof_diagnostics; MIN_C, MAX_C; MAX_EXCESS = max(C - F).  A NaN operand
+ *                    of a maximum counts as +inf (MIN_C: -inf); the sums propagate it.  The order of the sums is fixed (kernels/dye.h,
+ *                    kernels/reduce.h): the same state gives the same bits
+ *   vof_step_dye     nsteps times: one step -- exactly vof_step(h, 1) if mg_cycles == 0, exactly vof_step_mg(h, 1, mg_cycles, criterion,
+ *                    NULL, NULL, NULL) if mg_cycles >= 1 --, then one vof_dye_advance; behind every `every`-th step row r of VOF_DYE_N
+ *                    doubles is recorded on the device, bit for bit what vof_dye_stats yields behind the same steps.  every == 0 records
+ *                    nothing (out may be NULL).  Nothing waits for the device before the end of the call; then one copy writes `out` and
+ *                    *rows_written (may be NULL) is set.  The steps replay the handle's captured step graphs (VOF_FLAG_NO_GRAPH: eager
+ *                    launches, the same bits); the dye needs u, v of every step in memory, so the batch graphs of vof_step are not
+ *                    used.  The argument errors are those of vof_step_diag (every < 0 here, nsteps < 0, cap_rows < nsteps / every, out ==
+ *                    NULL with a row due, mg_cycles < 0, a bad criterion with mg_cycles >= 1); the handle is untouched
+ * Without a dye, advance, get, stats and step_dye return VOF_ESTATE.  Whole-domain handles only (a strip returns VOF_ESTATE and is left
+ * untouched); VOF_ESTATE too while a phased step is in progress.  The dye never changes F, u, v, p, istep, a counter or a cached graph;
+ * its sweeps count no Courant violations; every readable field, istep and courant_violations end where a single vof_step(nsteps) /
+ * vof_step_mg(nsteps, ...) leaves them, and a step verb that follows gives the bits it would have given without the dye and leaves the dye
+ * where it was.  vof_set_init_F and vof_set_field leave the dye alone; vof_destroy releases it.  Knob "dye_fused" (vof_set_param; default
+ * 1): 0 runs the advance as the two sweep kernels and the post kernel instead of the one-pass k_dye -- the same bits. */
+#define VOF_DYE_ISTEP 0
+#define VOF_DYE_CELLS 1
+#define VOF_DYE_SUM_C 2
+#define VOF_DYE_SUM_CI 3
+#define VOF_DYE_SUM_CJ 4
+#define VOF_DYE_SUM_C2 5
+#define VOF_DYE_SUM_CF 6
+#define VOF_DYE_SUM_CU 7
+#define VOF_DYE_SUM_CV 8
+#define VOF_DYE_MIN_C 9
+#define VOF_DYE_MAX_C 10
+#define VOF_DYE_MAX_EXCESS 11
+#define VOF_DYE_N 16
+int vof_dye_set(vof2d_handle h, const void* src, size_t nbytes);
+int vof_dye_get(vof2d_handle h, void* dst, size_t nbytes);
+int vof_dye_advance(vof2d_handle h);
+int vof_dye_stats(vof2d_handle h, double* out /* VOF_DYE_N */);
+int vof_step_dye(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
+                 double* out, int64_t cap_rows, int64_t* rows_written);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

@@ -73,6 +73,9 @@ struct WorkBufs {
   DevBuf gauge_pos;    // vof_gauges_* (runtime/depths.h): the positions, n x 2 doubles -- state, not scratch: replaced by vof_gauges_set alone
   DevBuf gauge_rows;   // ... the rows of vof_gauges_get (VOF_GAUGE_N doubles each), grown on demand
   DevBuf gauge_recs;   // ... the records vof_step_gauges takes, grown on demand
+  DevBuf dye;          // vof_dye_* (runtime/dye.h): the dye and its twin, two arrays in the fields' layout -- state, not scratch: replaced by vof_dye_set alone
+  DevBuf dye_part;     // ... one partial per block of k_dye_stats
+  DevBuf dye_rows;     // ... the rows recorded on the device, VOF_DYE_N doubles each, grown on demand
   DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
   DevBuf red;          // device scalar of vof_comm_allreduce_max
 

@@ -227,7 +227,11 @@ struct vof2d_ctx {
   // vof_gauges_* (runtime/depths.h): the gauges of buf.gauge_pos, and the records vof_step_gauges has taken since vof_gauges_set
   int64_t gauge_n = 0;
   int64_t gauge_records = 0;
-  char* h_depths = nullptr;       // pinned host copy of the results of a vof_depths pass (one copy out, then memcpy to the caller's arrays)
+  // vof_dye_* (runtime/dye.h): the handle has a dye in buf.dye, and which of the two arrays there holds it
+  bool dye_on = false;
+  int dye_cur = 0;
+  int dye_fused = 1;              // knob "dye_fused": the dye's transport as ONE launch (k_dye); 0: the two sweeps, k_post (same bits: the A/B partner)
+  char* h_depths = nullptr;      // pinned host copy of the results of a vof_depths pass (one copy out, then memcpy to the caller's arrays)
   size_t h_depths_bytes = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)

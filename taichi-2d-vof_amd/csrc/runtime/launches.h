@@ -171,9 +171,16 @@ struct L {
     dim3 grid((h->g.ny + 2 + 255) / 256, h->g.row_hi - h->g.row_lo + 1);
     launch(h, kOther, k_nu_rho<T>, grid, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fRHO), F_<T>(h, fNU));
   }
-  static void post(vof2d_ctx* h) {
+  // (a, a2: another pair in the fields' layout in the place of F and its twin -- the dye, runtime/dye.h)
+  static void post(vof2d_ctx* h, T* a = nullptr, T* a2 = nullptr) {
     dim3 grid((h->g.ny + 2 + 255) / 256, h->g.row_hi - h->g.row_lo + 1);
-    launch(h, kOther, k_post<T>, grid, 0, h->g, F_<T>(h, fF), F_<T>(h, fF2));
+    launch(h, kOther, k_post<T>, grid, 0, h->g, a ? a : F_<T>(h, fF), a ? a2 : F_<T>(h, fF2));
+  }
+  // the F lines of set_BC (2dvof.py:168, 174, 181, 187) on such a pair, all stored rows of a full domain
+  static void bc_F_pair(vof2d_ctx* h, T* a, T* a2) {
+    const int nr = h->g.row_hi - h->g.row_lo + 1;
+    const int n = nr > h->g.ny + 2 ? nr : h->g.ny + 2;
+    launch(h, kSetBC, k_set_bc<T, BC_F>, dim3((n + 255) / 256), 0, h->g, F_<T>(h, fU), F_<T>(h, fV), a, a2, F_<T>(h, fP), F_<T>(h, fRHO), h->d.row_lo, h->d.row_hi);
   }
   static void normals(vof2d_ctx* h) {
     const int R = pick_rows(h, h->g.ntj);
@@ -329,21 +336,22 @@ struct L {
   // sweeps read fld[fF], write fld[fF2]; the caller swaps the two afterwards.
   // CORR: the sweep also performs update_uv (reads u*, v*, p; writes u, v) -- see k_fct_x.
   // rows [first, last] of the sweep's output (0, 0: all computable rows)
+  // src, dst: another pair in the fields' layout in the place of F and its twin (the dye, runtime/dye.h; not with CORR)
   template <bool POST, bool CORR>
-  static void fct_x(vof2d_ctx* h, int first = 0, int last = 0) {
+  static void fct_x(vof2d_ctx* h, int first = 0, int last = 0, const T* src = nullptr, T* dst = nullptr) {
     if (first == 0 && last == 0) { first = h->g.ilo; last = h->g.ihi; }
     const int forced = CORR && h->fctx_corr_rows > 0 ? h->fctx_corr_rows : h->fctx_rows;
     const int R = forced > 0 ? forced : chunk_rows(h, h->g.ntj, 4, 16);
     launch(h, kFctX, k_fct_x<T, V, POST, CORR>, dim3(blocks_rows(last - first + 1, h->g.ntj, R)), 0, h->g, C(h),
-           (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fU), F_<T>(h, fF2), R, (const T*)F_<T>(h, fUS),
+           src ? src : (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fU), src ? dst : F_<T>(h, fF2), R, (const T*)F_<T>(h, fUS),
            (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV), h->d_courant, first, last);
   }
   template <bool POST, bool CORR>
-  static void fct_y(vof2d_ctx* h, int first = 0, int last = 0) {
+  static void fct_y(vof2d_ctx* h, int first = 0, int last = 0, const T* src = nullptr, T* dst = nullptr) {
     if (first == 0 && last == 0) { first = h->g.ilo; last = h->g.ihi; }
     const int R = h->rows_override > 0 ? h->rows_override : 1;   // rows are independent in this sweep
     launch(h, kFctY, k_fct_y<T, V, POST, CORR>, dim3(blocks_rows(last - first + 1, h->nty, R)), 0, h->g, C(h),
-           (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fV), F_<T>(h, fF2), R, h->nty, (const T*)F_<T>(h, fUS),
+           src ? src : (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fV), src ? dst : F_<T>(h, fF2), R, h->nty, (const T*)F_<T>(h, fUS),
            (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV), h->d_courant, first, last);
   }
   // k_transport of this step + k_momentum of the next in one launch (k_tm): reads fld[fF], fld[fUS], fld[fVS], fld[fP];

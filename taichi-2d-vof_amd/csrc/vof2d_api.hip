@@ -23,6 +23,7 @@
 //   runtime/blobs.h      the buffers, launches and copies of vof_blobs
 //   runtime/tracers.h    the buffers, launches and copies of vof_tracers_*, the loop of vof_step_tracers
 //   runtime/depths.h     the buffers, launches and copies of vof_depths and vof_gauges_*, the loop of vof_step_gauges
+//   runtime/dye.h        the dye arrays, launches and copies of vof_dye_*, the loop of vof_step_dye
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -37,6 +38,7 @@
 #include "runtime/blobs.h"
 #include "runtime/tracers.h"
 #include "runtime/depths.h"
+#include "runtime/dye.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -65,7 +67,7 @@ const Knob kKnobs[] = {
   KNOB("pair_slow10", pair_slow10, false), KNOB("solve_pairs", solve_pairs, false),
   KNOB("tb_slow10", tb_slow10, false), KNOB("tune_period", tune.period, false),
   KNOB("mg_nu", mg_nu, true), KNOB("mg_levels", mg_levels, true), KNOB("mg_graph", mg_graph, true),
-  KNOB("mg_coarse_block", mg_coarse_block, false),
+  KNOB("mg_coarse_block", mg_coarse_block, false), KNOB("dye_fused", dye_fused, true),
 };
 #undef KNOB
 const Knob* find_knob(const char* name) {
@@ -545,6 +547,57 @@ int vof_step_gauges(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cy
     return VOF_OK;
   }
   return step_gauges_n(h, nsteps, every, mg_cycles, criterion, out, records_written);
+}
+
+// ---- a marker field carried by the FCT transport (kernels/dye.h, runtime/dye.h)
+namespace {
+int check_dye_allowed(vof2d_ctx* h, bool needs_dye) {
+  if (const int rc = check_whole_domain(h, "the vof_dye_* verbs and vof_step_dye need the whole domain in one handle (a strip's sweeps need their exchanges)")) return rc;
+  if (const int rc = check_no_phased_step(h)) return rc;
+  return needs_dye && !h->dye_on ? fail(h, VOF_ESTATE, "the handle has no dye (vof_dye_set)") : VOF_OK;
+}
+}  // namespace
+int vof_dye_set(vof2d_handle h, const void* src, size_t nbytes) {
+  if (!h) return VOF_EINVAL;
+  if (src ? nbytes != dye_dense_bytes(h) : nbytes != 0) return fail(h, VOF_EINVAL, "nbytes is not (nx+2) x (ny+2) of the field dtype (or not 0 with src NULL)");
+  if (const int rc = check_dye_allowed(h, false)) return rc;
+  return dye_set(h, src);
+}
+int vof_dye_get(vof2d_handle h, void* dst, size_t nbytes) {
+  if (!h || !dst) return VOF_EINVAL;
+  if (nbytes != dye_dense_bytes(h)) return fail(h, VOF_EINVAL, "nbytes is not (nx+2) x (ny+2) of the field dtype");
+  if (const int rc = check_dye_allowed(h, true)) return rc;
+  return dye_copy_host(h, h->dye_cur, dst, true);
+}
+int vof_dye_advance(vof2d_handle h) {
+  if (!h) return VOF_EINVAL;
+  if (const int rc = check_dye_allowed(h, true)) return rc;
+  return dye_advance(h);
+}
+int vof_dye_stats(vof2d_handle h, double* out) {
+  if (!h || !out) return VOF_EINVAL;
+  int rc = check_dye_allowed(h, true);
+  if (rc) return rc;
+  if ((rc = dye_stats_prepare(h, 1))) return rc;
+  if ((rc = dye_stats_enqueue(h, 0))) return rc;
+  return read_back(h, out, h->buf.dye_rows.p, VOF_DYE_N * sizeof(double));
+}
+int vof_step_dye(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
+                 int64_t* rows_written) {
+  if (!h) return VOF_EINVAL;
+  if (every < 0) return fail(h, VOF_EINVAL, "every must be >= 0 (0: no rows)");
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
+  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  const int64_t due = every > 0 ? nsteps / every : 0;
+  if (cap_rows < due) return fail(h, VOF_EINVAL, "cap_rows is smaller than nsteps / every");
+  if (!out && due > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one row is due");
+  if (const int rc = check_dye_allowed(h, true)) return rc;
+  if (nsteps == 0) {
+    if (rows_written) *rows_written = 0;
+    return VOF_OK;
+  }
+  return step_dye_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

@@ -25,6 +25,7 @@
 //   blobs.h      k_blob_init, k_blob_merge, k_blob_flatten, k_blob_number, k_blob_label, k_blob_stats, k_blob_summary, k_blob_plan, k_blob_sums, k_blob_rows   (extension: droplets and bubbles labelled by union-find, numbered by first cell, measured in a fixed order)
 //   tracers.h    k_tracer_advance, k_tracer_sample, k_tracer_finish   (extension: passive particles, one per lane: bilinear gather on the staggered grid, midpoint rule, walls)
 //   depths.h     k_depths, k_depths_fold, k_depths_finish, k_gauge_sample   (extension: both marginals of F, the top of the liquid per row and the front in one pass over F; fixed sensors that sample u, v, F, p and read them)
+//   dye.h        k_dye, k_dye_stats, k_dye_stats_finish   (extension: a marker field moved by both FCT sweeps in one pass over C, u, v; its sums and extrema in one fixed-order pass)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
@@ -43,3 +44,4 @@
 #include "kernels/blobs.h"
 #include "kernels/tracers.h"
 #include "kernels/depths.h"
+#include "kernels/dye.h"

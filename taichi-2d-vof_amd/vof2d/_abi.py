@@ -36,6 +36,10 @@ VOF_DEPTH_SUM_N = 8
 VOF_GAUGE_X, VOF_GAUGE_Y, VOF_GAUGE_U, VOF_GAUGE_V, VOF_GAUGE_F, VOF_GAUGE_P, VOF_GAUGE_DEPTH, VOF_GAUGE_TOP, VOF_GAUGE_N = range(9)
 VOF_GAUGE_SUM_COUNT, VOF_GAUGE_SUM_ISTEP, VOF_GAUGE_SUM_RECORDS = range(3)
 VOF_GAUGE_SUM_N = 8
+# vof_dye_*: the slots of a row of vof_dye_stats (vof2d/dye.py)
+(VOF_DYE_ISTEP, VOF_DYE_CELLS, VOF_DYE_SUM_C, VOF_DYE_SUM_CI, VOF_DYE_SUM_CJ, VOF_DYE_SUM_C2, VOF_DYE_SUM_CF, VOF_DYE_SUM_CU, VOF_DYE_SUM_CV,
+ VOF_DYE_MIN_C, VOF_DYE_MAX_C, VOF_DYE_MAX_EXCESS) = range(12)
+VOF_DYE_N = 16
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -110,6 +114,11 @@ SIGNATURES = {
     "gauges_set": (C.c_int, [H, C.POINTER(_dbl), _i64]),
     "gauges_get": (C.c_int, [H, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
     "step_gauges": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
+    "dye_set": (C.c_int, [H, C.c_void_p, C.c_size_t]),
+    "dye_get": (C.c_int, [H, C.c_void_p, C.c_size_t]),
+    "dye_advance": (C.c_int, [H]),
+    "dye_stats": (C.c_int, [H, C.POINTER(_dbl)]),
+    "step_dye": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
     "get_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "set_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "get_rows": (C.c_int, [H, _str, _i32, _i32, C.c_void_p, C.c_size_t]),
@@ -147,7 +156,8 @@ SIGNATURES = {
 GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_profile", "reset_profile",
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
             "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "blobs",
-            "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges")
+            "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges",
+            "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye")
 
 
 class Api:

@@ -97,8 +97,47 @@ def build_parser():
                      help='every N steps write data/depths_NNNNNN.npy -- rows of x_i, liquid depth over the floor in metres, top j of the '
                           'liquid per grid row, from one pass over F on the device (vof_depths) -- and append istep, front_lo, front_hi, '
                           'top, volume to data/depths.csv; works with --gpus N')
+    ext.add_argument('--dye-box', action='append', default=[], metavar='X0,X1,Y0,Y1',
+                     help='a dye: a marker field equal to F inside the physical box [X0, X1] x [Y0, Y1] (decided at the cell centres; repeatable, '
+                          'the boxes are joined) and 0 elsewhere, carried by the transport of F behind every step on the device (vof_step_dye); one GPU')
+    ext.add_argument('--dye-file', default=None, metavar='FILE.npy', help='the dye as an (nx+2, ny+2) array, ghost cells included, instead of boxes')
+    ext.add_argument('--dye-every', type=int, default=None, metavar='N',
+                     help='every N steps append a row to data/dye.csv: amount, centroid, mean, variance, share outside the liquid, the '
+                          "dye's velocity, min and max of the dye and max(C - F), reduced on the device")
+    ext.add_argument('--dye-save-every', type=int, default=None, metavar='M', help='every M steps write the dye to data/dye_NNNNNN.npy')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
+
+
+def dye_conflicts(args):
+    """The options a dye cannot be combined with, each with the reason ('' where there is none): its steps are those of
+    vof_step_dye, one call that steps and moves the dye on the device."""
+    dye = bool(args.dye_box or args.dye_file or args.dye_every is not None or args.dye_save_every is not None)
+    if not dye:
+        return ''
+    for on, name, why in ((args.gpus > 1, "--gpus N", "the dye's sweeps on a strip would need their own halo exchanges"),
+                          (args.verbs, "--verbs", "the verb-by-verb loop has no place for the dye's transport"),
+                          (args.jacobi_tol > 0.0, "--jacobi-tol", "the residual-terminated loop runs verb by verb"),
+                          (args.diag_every is not None, "--diag-every", "vof_step_diag and vof_step_dye are two stepping loops"),
+                          (bool(args.tracers), "--tracers", "vof_step_tracers and vof_step_dye are two stepping loops"),
+                          (args.gauges_every is not None, "--gauges-every", "vof_step_gauges and vof_step_dye are two stepping loops")):
+        if on:
+            return "the dye options (--dye-box, --dye-file, --dye-every, --dye-save-every) cannot be combined with %s: %s" % (name, why)
+    return ''
+
+
+def parse_dye_boxes(specs):
+    """[(x0, x1, y0, y1)] of the --dye-box values."""
+    out = []
+    for spec in specs:
+        try:
+            x0, x1, y0, y1 = (float(t) for t in spec.split(','))
+        except ValueError:
+            raise SystemExit("--dye-box needs X0,X1,Y0,Y1 (four numbers), not %r" % spec)
+        if not (x0 <= x1 and y0 <= y1):
+            raise SystemExit("--dye-box %s: needs X0 <= X1 and Y0 <= Y1" % spec)
+        out.append((x0, x1, y0, y1))
+    return out
 
 
 def parse_args(argv=None):
@@ -132,6 +171,16 @@ def parse_args(argv=None):
                      "or use --depths-every, which works on strips")
     if args.gauges_every is not None and not (args.gauge or args.gauges_file or args.resume):
         parser.error("--gauges-every records the gauges of --gauge X,Y / --gauges-file FILE: pass at least one")
+    if args.dye_every is not None and args.dye_every < 1:
+        parser.error("--dye-every needs N >= 1")
+    if args.dye_save_every is not None and args.dye_save_every < 1:
+        parser.error("--dye-save-every needs M >= 1")
+    if args.dye_box and args.dye_file:
+        parser.error("--dye-box and --dye-file both give the dye: pass one of them")
+    if (args.dye_every is not None or args.dye_save_every is not None) and not (args.dye_box or args.dye_file or args.resume):
+        parser.error("--dye-every and --dye-save-every report the dye of --dye-box X0,X1,Y0,Y1 / --dye-file FILE.npy: pass one")
+    if dye_conflicts(args):
+        parser.error(dye_conflicts(args))
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -231,6 +280,34 @@ class _Single:
         self.gauges_in_advance = bool(self.gauges_every) and not (args.jacobi_tol > 0.0 or args.verbs or self.diag_in_advance
                                                                   or getattr(args, "mg_cycles", 0) > 0 or self.tr_every)
         self.gauge_recs = []                         # (istep, rows) not yet written
+        # a dye (--dye-box / --dye-file): every step is a step of vof_step_dye, the rows of --dye-every recorded on the device
+        self.dye_on = False
+        self.dye_every = getattr(args, "dye_every", None) or 0
+        self.dye_rows = []                           # raw rows not yet written
+
+    def set_dye(self, C):
+        self.eng.dye_set(C)
+        self.dye_on = True
+
+    def dye(self):
+        return self.eng.dye_get()
+
+    def take_dye(self):
+        rows, self.dye_rows = self.dye_rows, []
+        return rows
+
+    def _advance_dye(self, n):
+        """n steps of vof_step_dye with a row at every multiple of N: no rows up to the first multiple (a resumed run may start
+        anywhere), then one call for the rest."""
+        from . import dye
+        N, K, crit = self.dye_every, getattr(self.args, "mg_cycles", 0), self.args.jacobi_crit
+        head = min(n, -self.sim.istep % N) if N else n
+        if head:
+            self.sim.step_dye(head, 0, K, crit)
+            if N and self.sim.istep % N == 0:
+                self.dye_rows.append(self.eng.dye_stats())
+        if n - head:
+            self.dye_rows += [dye.raw_of(r) for r in self.sim.step_dye(n - head, N, K, crit)]
 
     def set_gauges(self, xy):
         self.eng.gauges_set(xy)
@@ -339,6 +416,8 @@ class _Single:
                     self.eng.solve_p(a.jacobi_tol, a.jacobi_max, 10, a.jacobi_crit)
                 sim.update_uv(); sim.set_BC()
                 sim.solve_VOF_rudman(sim.istep); sim.post_process_f(); sim.set_BC()
+        elif self.dye_on:
+            self._advance_dye(n)
         elif self.diag_in_advance:
             self._advance_diag(n)
         elif self.gauges_in_advance:
@@ -385,7 +464,7 @@ class _Single:
 
     def report(self):
         """What the status line adds for this run ('' for most), and a fresh start of whatever it accumulates."""
-        if getattr(self.args, "mg_cycles", 0) <= 0 or self.diag_in_advance:
+        if getattr(self.args, "mg_cycles", 0) <= 0 or self.diag_in_advance or self.dye_on:
             return ''
         worst, at = self.mg_worst
         self.mg_worst = (0.0, 0)
@@ -567,6 +646,36 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                 f.write(gauges_mod.GAUGES_CSV_HEADER + '\n')
     stop_at_gauges = bool(gauges_every) and not drv.gauges_in_advance
 
+    # a dye (vof_dye_*): seeded from F inside the boxes, read from a file, or restored beside the checkpoint
+    dye_every = getattr(args, "dye_every", None) or 0
+    dye_save = getattr(args, "dye_save_every", None) or 0
+    dye_on, dye_path = False, 'data/dye.csv'
+    if getattr(args, "dye_box", None) or getattr(args, "dye_file", None) or dye_every or dye_save:
+        from . import dye as dye_mod
+        if dye_conflicts(args) or world > 1:
+            raise SystemExit(dye_conflicts(args) or "the dye options run on one GPU (drop --gpus)")
+        if not hasattr(api, "step_dye"):
+            raise SystemExit("the dye options need the dye verbs of the HIP library (vof_dye_*, vof_step_dye): this backend has none")
+        state = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'dye_state.npz') if args.resume else None
+        # (a resumed run continues the dye it saved, whatever boxes the command line repeats: they describe step 0)
+        if state and os.path.exists(state) and int(np.load(state, allow_pickle=False)["istep"]) == istep:
+            C = np.load(state, allow_pickle=False)["C"]
+            say(f'>>> Dye restored from {state}.')
+        elif args.dye_file:
+            C = np.load(args.dye_file, allow_pickle=False)
+            if C.shape != (nx + 2, ny + 2):
+                raise SystemExit("--dye-file: %s holds an array of shape %s, the dye is (nx+2, ny+2) = %s" % (args.dye_file, C.shape, (nx + 2, ny + 2)))
+        elif args.dye_box:
+            C = dye_mod.boxes(drv.full("F"), eng.get_param("dx"), eng.get_param("dy"), parse_dye_boxes(args.dye_box))
+        else:
+            raise SystemExit("--dye-every / --dye-save-every: no dye given and none of this step beside the checkpoint (--dye-box X0,X1,Y0,Y1, --dye-file FILE.npy)")
+        drv.set_dye(C)
+        dye_on = True
+        say(f'>>> Dye set: {float(np.asarray(C, dtype=np.float64)[1:-1, 1:-1].sum()) * eng.get_param("dx") * eng.get_param("dy"):.6e} m^2.')
+        if dye_every and not (args.resume and os.path.exists(dye_path) and os.path.getsize(dye_path) > 0):
+            with open(dye_path, 'w') as f:
+                f.write(','.join(('istep', 'time') + dye_mod.DERIVED) + '\n')
+
     # the free-surface profile (vof_depths) is read between calls, like the interface
     depths_every = getattr(args, "depths_every", None) or 0
     depths_path = 'data/depths.csv'
@@ -630,6 +739,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             n = min(n, gauges_every - i % gauges_every)
         if depths_every:
             n = min(n, depths_every - i % depths_every)
+        if dye_save:
+            n = min(n, dye_save - i % dye_save)
         if args.steps:
             n = min(n, args.steps - i)
         return n
@@ -677,7 +788,19 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                     np.save('data/depths_%06d.npy' % istep, np.stack([d["x"], d["depth"], prof[2].astype(np.float64)], axis=1))
                     with open(depths_path, 'a') as f:
                         f.write(gauges_mod.depths_csv_line(dict(prof[3], ISTEP=istep), eng.get_param("dx"), eng.get_param("dy")) + '\n')
+            if dye_on:
+                rows = drv.take_dye()
+                if rows:
+                    with open(dye_path, 'a') as f:
+                        for raw in rows:
+                            d, k = dye_mod.derive(raw, eng.get_param("dx"), eng.get_param("dy")), int(raw["ISTEP"])
+                            f.write(','.join([str(k), repr(k * dt)] + [repr(float(d[c])) for c in dye_mod.DERIVED]) + '\n')
+                if dye_save and istep % dye_save == 0:
+                    np.save('data/dye_%06d.npy' % istep, drv.dye())
             if args.save_every and istep % args.save_every == 0:
+                if dye_on:                                          # (beside the checkpoint, whose format stays as it is)
+                    np.savez('data/dye_state.tmp.npz', C=drv.dye(), istep=np.int64(istep))
+                    os.replace('data/dye_state.tmp.npz', 'data/dye_state.npz')
                 fields = {f: drv.full(f) for f in STATE}
                 warn = drv.courant()
                 if lead:

@@ -320,6 +320,49 @@ class Engine:
                                       out.ctypes.data_as(C.POINTER(C.c_double)) if due else None, due, C.byref(done)), "step_gauges")
         return out[:done.value]
 
+    def dye_set(self, arr):
+        """vof_dye_set: replaces the handle's dye by the (nx+2, ny+2) array arr, ghost cells included, stored as given;
+        None releases it."""
+        if arr is None:
+            self._ck(self.api.dye_set(self._h, None, 0), "dye_set")
+            return
+        a = np.ascontiguousarray(arr, dtype=self.np_dtype)
+        if a.shape != (self.nx + 2, self.ny + 2):
+            raise ValueError("dye: expected shape %s, got %s" % ((self.nx + 2, self.ny + 2), a.shape))
+        self._ck(self.api.dye_set(self._h, a.ctypes.data_as(C.c_void_p), a.nbytes), "dye_set")
+
+    def dye_get(self):
+        """vof_dye_get: the dye as an (nx+2, ny+2) array of the handle's dtype."""
+        out = np.empty((self.nx + 2, self.ny + 2), dtype=self.np_dtype)
+        self._ck(self.api.dye_get(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes), "dye_get")
+        return out
+
+    def dye_advance(self):
+        """vof_dye_advance: one transport of the dye (both FCT sweeps in the order of the handle's istep, post_process_f, the
+        boundary condition of F) on the current u, v (enqueues only)."""
+        self._ck(self.api.dye_advance(self._h), "dye_advance")
+
+    def dye_stats(self):
+        """vof_dye_stats: one fixed-order pass over the dye, F, u, v on the interior cells; the raw row as a dict keyed by
+        dye.NAMES (the physical quantities: dye.derive)."""
+        from . import dye
+        row = (C.c_double * _abi.VOF_DYE_N)()
+        self._ck(self.api.dye_stats(self._h, row), "dye_stats")
+        return dye.raw_of(list(row))
+
+    def step_dye(self, nsteps, every=0, mg_cycles=0, criterion="rel"):
+        """vof_step_dye: nsteps times one step (of vof_step; of vof_step_mg with mg_cycles >= 1) and one advance of the dye, a
+        row of statistics recorded on the device behind every `every`-th step (0: none), one read-back at the end; returns
+        the (rows, VOF_DYE_N) float64 array."""
+        crit = criterion_code(criterion)
+        nsteps, every = int(nsteps), int(every)
+        rows = max(nsteps, 0) // every if every >= 1 else 0
+        out = np.zeros((rows, _abi.VOF_DYE_N), dtype=np.float64)
+        done = C.c_int64()
+        self._ck(self.api.step_dye(self._h, nsteps, every, int(mg_cycles), crit,
+                                   out.ctypes.data_as(C.POINTER(C.c_double)) if rows else None, rows, C.byref(done)), "step_dye")
+        return out[:done.value]
+
     def _sized_rows(self, cap_attr, first_cap, width, summ, count_slot, what, call):
         """The rows of a verb that fills at most `cap` of them and reports in summ[count_slot] how many there are:
         call(rows pointer, cap) with the capacity the last call needed (plus a margin), once more if the list has outgrown it."""

@@ -176,6 +176,26 @@ class VOF2D:
         """nsteps steps with a record of every gauge taken on the device every `every` steps (vof_step_gauges)."""
         return self.eng.step_gauges(nsteps, every, mg_cycles, criterion)
 
+    def dye_set(self, arr):
+        """Give the handle a dye: an (nx+2, ny+2) marker field carried by the transport of F (vof_dye_set; None releases it; vof2d/dye.py: box)."""
+        self.eng.dye_set(arr)
+
+    def dye_get(self):
+        """The dye as an (nx+2, ny+2) array (vof_dye_get)."""
+        return self.eng.dye_get()
+
+    def dye_advance(self):
+        """One transport of the dye with the current u, v and the step parity of istep (vof_dye_advance)."""
+        self.eng.dye_advance()
+
+    def dye_stats(self):
+        """The raw row of vof_dye_stats as a dict (vof2d/dye.py: NAMES, derive)."""
+        return self.eng.dye_stats()
+
+    def step_dye(self, nsteps, every=0, mg_cycles=0, criterion="rel"):
+        """nsteps steps, the dye moved behind each, a row of its statistics recorded on the device every `every` steps (vof_step_dye)."""
+        return self.eng.step_dye(nsteps, every, mg_cycles, criterion)
+
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)
