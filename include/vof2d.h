@@ -505,6 +505,81 @@ int vof_dye_advance(vof2d_handle h);
 int vof_dye_stats(vof2d_handle h, double* out /* VOF_DYE_N */);
 int vof_step_dye(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
                  double* out, int64_t cap_rows, int64_t* rows_written);
+/* Extension: pictures.  One quantity box-averaged over bx x by cells per pixel, mapped through a 256-entry colour table to 8-bit RGB, the
+ * interface marked on top, all on the device: pw x ph x 3 bytes leave it instead of whole fields (0.8 MB for a 512^2 picture of any grid).
+ * The values are those vof_get_field would return at that moment (the ghost cells are settled first); every operand is converted to double
+ * on load (one code path for both dtypes) and every product, sum, difference, quotient and root below is rounded on its own, in the
+ * FMA-contracted build too.
+ *   geometry    pw = ceil(nx / bx), ph = ceil(ny / by).  Pixel (a, b) covers the cells i in [a bx + 1, min((a+1) bx, nx)], j in [b by + 1,
+ *               min((b+1) by, ny)]: cnt cells, fewer in the last pixel row and column.  rgb is dense (ph, pw, 3): image row r is pixel row
+ *               b = ph - 1 - r (the top of the domain is the top of the picture), image column c is a -- the orientation of
+ *               vis.colour_image.  means is dense (pw, ph), indexed [a, b] like a field
+ *   cell value  F: F[i,j], raw.  P: p[i,j].  DYE: C[i,j] (without a dye: VOF_ESTATE).  U: uc = (u[i,j] + u[i+1,j]) * 0.5.  V: vc = (v[i,j] +
+ *               v[i,j+1]) * 0.5 (the expressions of vof_diagnostics).  SPEED: sqrt(uc * uc + vc * vc).  VORT: (vc(i+1,j) - vc(i-1,j)) * hx -
+ *               (uc(i,j+1) - uc(i,j-1)) * hy with hx = 0.5 * dxi, hy = 0.5 * dyi of the doubles of vof_get_param and vc(.), uc(.) the
+ *               expressions above at the neighbouring cell -- at the walls a ghost cell
+ *   mean        for every column j of the pixel c_j = 0.0; c_j += q[i,j] for i ascending; then S = 0.0; S += c_j for j ascending; then
+ *               m = S / (double)cnt.  The order depends on the geometry alone.  A NaN cell makes exactly its own pixel NaN
+ *   range       hi > lo: the fixed range.  lo == hi: auto, lo the minimum and hi the maximum of the non-NaN means (by integer atomics on an
+ *               order-preserving key of the double, under which -0.0 lies below +0.0: no order of arrival matters); with
+ *               VOF_FRAME_SYMMETRIC the auto range becomes [-A, A], A = max(|lo|, |hi|) (on a fixed range the flag is ignored); no non-NaN
+ *               pixel gives lo = hi = 0
+ *   colour      t = (m - lo) / (hi - lo); idx = 0 if t <= 0 or hi == lo (or t is NaN: an infinite mean over an infinite range), 255 if
+ *               t >= 1, (int)(t * 255.0 + 0.5) otherwise, truncating; the pixel is lut[idx]
+ *   contour     with VOF_FRAME_CONTOUR the pass also forms the means mF of F (for quantity F the same array); s(a,b) = (mF(a,b) >= 0.5), a NaN
+ *               gives false; pixel (a,b) takes lut[256] if s(a,b) != s(a+1,b) with a + 1 < pw or s(a,b) != s(a,b+1) with b + 1 < ph
+ *   NaN         a pixel whose own mean m is NaN takes lut[257], whatever else holds
+ *   table       VOF_FRAME_LUT_ROWS x 3 bytes owned by the handle: entries 0..255 the map, 256 the contour colour, 257 the NaN colour.
+ *               vof_frame_set_lut copies it in (synchronises); NULL restores the default, the grey ramp (k,k,k), contour (0,0,0), NaN
+ *               (255,0,255).  The table is data: the library knows no colour map (vof2d/frames.py samples matplotlib's into it)
+ *   summary     VOF_FRAME_SUM_N doubles (unused slots read 0): PW, PH, ISTEP; LO, HI, the range used; NAN_PIXELS; CONTOUR_PIXELS, the
+ *               pixels that took lut[256]
+ *   vof_frame        rgb and means may each be NULL and are then skipped (the cap only has to be >= 0); the summary always describes the
+ *                    whole frame.  A non-NULL rgb needs cap_bytes >= pw ph 3, a non-NULL means cap_means >= pw ph; nothing behind that
+ *                    is touched.  The results go through one pinned host buffer: one copy, one wait
+ *   vof_step_frames  for r = 0 .. nsteps / every - 1: `every` steps -- exactly vof_step(h, every) if mg_cycles == 0, exactly
+ *                    vof_step_mg(h, every, mg_cycles, criterion, NULL, NULL, NULL) if mg_cycles >= 1 --, then frame r: pw ph 3 bytes and
+ *                    VOF_FRAME_SUM_N doubles, written on the device into buffers the handle owns (grown before anything is enqueued),
+ *                    byte for byte what vof_frame yields behind the same steps.  A remainder of nsteps % every steps is stepped and gets
+ *                    no frame.  Nothing waits for the device before the end of the call; then one copy each writes out_rgb and
+ *                    out_summaries, and *frames_written (may be NULL) is set.  The argument errors are those of vof_step_gauges (every < 1,
+ *                    nsteps < 0, cap_frames < nsteps / every, out_rgb or out_summaries NULL with a frame due, mg_cycles < 0, a bad
+ *                    criterion with mg_cycles >= 1)
+ * VOF_EINVAL too, the handle and the outputs untouched: spec == NULL, a quantity or a flag outside the lists, bx < 1 or by < 1, hi < lo or a
+ * NaN or infinite lo / hi, summary == NULL, a negative cap or one too small for a non-NULL output, pw ph 3 > 2^31 - 1.  Whole-domain handles
+ * only (a strip returns VOF_ESTATE and is left untouched); VOF_ESTATE too while a phased step is in progress.  No field, istep, counter or
+ * cached graph changes; every readable field, istep and courant_violations end where vof_step(nsteps) / vof_step_mg(nsteps, ...) alone
+ * leaves them, and a step verb that follows gives the bits it would have given without the call.  The order of every sum is stated in
+ * csrc/kernels/frames.h; no floating-point atomics: the same state gives the same bytes.  vof_destroy releases the table and the buffers. */
+#define VOF_FRAME_F 0
+#define VOF_FRAME_U 1
+#define VOF_FRAME_V 2
+#define VOF_FRAME_SPEED 3
+#define VOF_FRAME_P 4
+#define VOF_FRAME_VORT 5
+#define VOF_FRAME_DYE 6
+#define VOF_FRAME_CONTOUR 1
+#define VOF_FRAME_SYMMETRIC 2
+#define VOF_FRAME_LUT_ROWS 258
+#define VOF_FRAME_SUM_PW 0
+#define VOF_FRAME_SUM_PH 1
+#define VOF_FRAME_SUM_ISTEP 2
+#define VOF_FRAME_SUM_LO 3
+#define VOF_FRAME_SUM_HI 4
+#define VOF_FRAME_SUM_NAN_PIXELS 5
+#define VOF_FRAME_SUM_CONTOUR_PIXELS 6
+#define VOF_FRAME_SUM_N 8
+typedef struct vof2d_frame_spec {
+  int32_t quantity;   /* VOF_FRAME_F, _U, _V, _SPEED, _P, _VORT, _DYE */
+  int32_t bx, by;     /* cells per pixel along i and along j, >= 1 */
+  int32_t flags;      /* VOF_FRAME_CONTOUR | VOF_FRAME_SYMMETRIC */
+  double  lo, hi;     /* hi > lo: the fixed range; lo == hi: the range is taken from the picture (auto) */
+} vof2d_frame_spec;
+int vof_frame_set_lut(vof2d_handle h, const uint8_t* lut /* VOF_FRAME_LUT_ROWS x 3, or NULL */);
+int vof_frame(vof2d_handle h, const vof2d_frame_spec* spec, uint8_t* rgb, int64_t cap_bytes, double* means, int64_t cap_means,
+              double* summary /* VOF_FRAME_SUM_N */);
+int vof_step_frames(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
+                    const vof2d_frame_spec* spec, uint8_t* out_rgb, double* out_summaries, int64_t cap_frames, int64_t* frames_written);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

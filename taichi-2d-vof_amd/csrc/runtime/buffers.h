@@ -76,6 +76,9 @@ struct WorkBufs {
   DevBuf dye;          // vof_dye_* (runtime/dye.h): the dye and its twin, two arrays in the fields' layout -- state, not scratch: replaced by vof_dye_set alone
   DevBuf dye_part;     // ... one partial per block of k_dye_stats
   DevBuf dye_rows;     // ... the rows recorded on the device, VOF_DYE_N doubles each, grown on demand
+  DevBuf frame_work;   // vof_frame (runtime/frames.h, FrameCarve): the column partials, the means of F, the words; the means, the summary, the picture
+  DevBuf frame_lut;    // ... the colour table, 258 x 3 bytes -- state, not scratch: replaced by vof_frame_set_lut alone
+  DevBuf frame_recs;   // ... the pictures vof_step_frames records, their summaries behind them, grown on demand
   DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
   DevBuf red;          // device scalar of vof_comm_allreduce_max
 

@@ -77,4 +77,22 @@ inline DepthsCarve carve_depths(size_t rows, size_t ny, size_t row_partials, siz
   return c;
 }
 
+// vof_frame: the column partials of the quantity and, where the contour needs them beside it (f_partials, f_pixels: 0 otherwise),
+// of F; the means of F; the integer words (zeroed as one range in front of a pass); then what a call copies out, consecutive:
+// the means, the summary, three bytes a pixel
+struct FrameCarve { size_t colq, colF, mF, words, words_bytes, means, sum, rgb, rgb_bytes, total; };
+inline FrameCarve carve_frame(size_t col_partials, size_t pixels, size_t f_partials, size_t f_pixels) {
+  Carve a;
+  FrameCarve c;
+  c.colq = a.take(col_partials * sizeof(double), 16); c.colF = a.take(f_partials * sizeof(double), 16);
+  c.mF = a.doubles(f_pixels);
+  c.words_bytes = 4 * sizeof(unsigned long long);
+  c.words = a.take(c.words_bytes, sizeof(unsigned long long));
+  c.means = a.doubles(pixels); c.sum = a.doubles(8);
+  c.rgb_bytes = pixels * 3;
+  c.rgb = a.take(c.rgb_bytes);
+  c.total = a.total;
+  return c;
+}
+
 }  // namespace vof

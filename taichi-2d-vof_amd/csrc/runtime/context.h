@@ -233,6 +233,8 @@ struct vof2d_ctx {
   int dye_fused = 1;              // knob "dye_fused": the dye's transport as ONE launch (k_dye); 0: the two sweeps, k_post (same bits: the A/B partner)
   char* h_depths = nullptr;      // pinned host copy of the results of a vof_depths pass (one copy out, then memcpy to the caller's arrays)
   size_t h_depths_bytes = 0;
+  char* h_frame = nullptr;       // pinned host copy of the results of a vof_frame call (one copy out, then memcpy to the caller's arrays)
+  size_t h_frame_bytes = 0;
   int rows_override = 0;
   int tb = 5;           // Jacobi sweeps fused per launch (1 = plain kernel)
   int tb_rows = 0;      // rows per wave chunk of the fused kernel (0 = heuristic)

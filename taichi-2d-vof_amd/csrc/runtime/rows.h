@@ -83,6 +83,39 @@ inline DepthsGeom depths_geom(const ReportedRows& rep, int R) {
   return {R, chunks, rep.entries(), (int64_t)chunks * rep.ny, rep.blocks(R), (unsigned)((rep.rows() + 255) / 256), (unsigned)((rep.ny + 255) / 256)};
 }
 
+// vof_frame (kernels/frames.h) on a whole domain: pixel (a, b) covers bx x by cells, the last pixel row / column what is left.
+// Blocks larger than the grid count as the grid (one pixel that way either way; no product of theirs overflows).  A wave of
+// k_frame_cols marches K whole pixel rows: the cells-per-wave rule with 2 and 32 gives a length, K = max(1, length / bx) pixel
+// rows of it make a chunk of R = K bx rows (the last chunk ends at nx).  It leaves one partial per (pixel row, column), the
+// columns padded to whole tiles of `tile` = 64 V columns so that every lane stores its V partials as one vector: cpitch doubles
+// a pixel row.  k_frame_fold and k_frame_paint: one lane per pixel, 256 a block, at most kFramePixelBlocks blocks striding over the pixels.
+constexpr unsigned kFramePixelBlocks = 256;
+struct FrameGeom {
+  int bx, by;       // as used: min(bx, nx), min(by, ny)
+  int pw, ph;       // ceil(nx / bx), ceil(ny / by)
+  int K, R, chunks;
+  int cpitch;
+  int64_t col_partials;   // pw * cpitch
+  int64_t pixels;         // pw * ph
+  unsigned cols_blocks;   // of k_frame_cols: four waves a block
+  unsigned pixel_blocks;  // of k_frame_fold and k_frame_paint
+};
+inline FrameGeom frame_geom(int nx, int ny, int ntj, int tile, int bx, int by) {
+  FrameGeom f;
+  f.bx = bx < nx ? bx : nx; f.by = by < ny ? by : ny;
+  f.pw = (nx + f.bx - 1) / f.bx; f.ph = (ny + f.by - 1) / f.by;
+  const int len = cells_per_wave_rows(nx, ntj, 2, 32);
+  f.K = len / f.bx > 1 ? len / f.bx : 1;
+  f.R = f.K * f.bx;
+  f.chunks = (f.pw + f.K - 1) / f.K;
+  f.cpitch = ntj * tile;
+  f.col_partials = (int64_t)f.pw * f.cpitch;
+  f.pixels = (int64_t)f.pw * f.ph;
+  f.cols_blocks = (unsigned)(((long)f.chunks * ntj + 3) / 4);
+  f.pixel_blocks = (f.pixels + 255) / 256 < (int64_t)kFramePixelBlocks ? (unsigned)((f.pixels + 255) / 256) : kFramePixelBlocks;
+  return f;
+}
+
 // The kernels that end a step on a strip run on all owned rows at once, or on the bands first (the exchange waits for
 // them alone) and on the rest beside the exchange.
 enum StripPart { kAllOwned = 0, kEdgeBands = 1, kRest = 2 };

@@ -24,6 +24,7 @@
 //   runtime/tracers.h    the buffers, launches and copies of vof_tracers_*, the loop of vof_step_tracers
 //   runtime/depths.h     the buffers, launches and copies of vof_depths and vof_gauges_*, the loop of vof_step_gauges
 //   runtime/dye.h        the dye arrays, launches and copies of vof_dye_*, the loop of vof_step_dye
+//   runtime/frames.h     the colour table, the buffers, launches and copies of vof_frame, the loop of vof_step_frames
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -39,6 +40,7 @@
 #include "runtime/tracers.h"
 #include "runtime/depths.h"
 #include "runtime/dye.h"
+#include "runtime/frames.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -191,6 +193,7 @@ int vof_destroy(vof2d_handle h) {
   if (h->ev_gas) (void)hipEventDestroy(h->ev_gas);
   if (h->h_gas) (void)hipHostFree(h->h_gas);
   if (h->h_depths) (void)hipHostFree(h->h_depths);
+  if (h->h_frame) (void)hipHostFree(h->h_frame);
   comm_teardown(h);
 #ifdef VOF_SHORTCUT_STATS
   {
@@ -598,6 +601,60 @@ int vof_step_dye(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycle
     return VOF_OK;
   }
   return step_dye_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
+}
+
+// ---- colour-mapped pictures rendered on the device (kernels/frames.h, runtime/frames.h)
+namespace {
+int check_frames_allowed(vof2d_ctx* h) {
+  if (const int rc = check_whole_domain(h, "vof_frame_set_lut, vof_frame and vof_step_frames need the whole domain in one handle (frames over row strips are not built)")) return rc;
+  return check_no_phased_step(h);
+}
+// 0, or VOF_EINVAL with the message set: the spec alone (pixels: pw * ph of it)
+int check_frame_spec(vof2d_ctx* h, const vof2d_frame_spec* spec, int64_t* pixels) {
+  if (!spec) return fail(h, VOF_EINVAL, "spec is NULL");
+  if (spec->quantity < 0 || spec->quantity >= FQ_N) return fail(h, VOF_EINVAL, "spec.quantity is not one of VOF_FRAME_F .. VOF_FRAME_DYE");
+  if (spec->flags & ~(FRF_CONTOUR | FRF_SYMMETRIC)) return fail(h, VOF_EINVAL, "spec.flags has a bit outside VOF_FRAME_CONTOUR | VOF_FRAME_SYMMETRIC");
+  if (spec->bx < 1 || spec->by < 1) return fail(h, VOF_EINVAL, "spec.bx and spec.by must be >= 1");
+  if (!std::isfinite(spec->lo) || !std::isfinite(spec->hi) || spec->hi < spec->lo) return fail(h, VOF_EINVAL, "spec.lo and spec.hi must be finite with hi >= lo (lo == hi: the range of the picture)");
+  const FrameGeom fg = frame_geom(h->d.nx, h->d.ny, h->g.ntj, 64 * h->V, spec->bx, spec->by);
+  if (fg.pixels * 3 > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "the picture would have more than 2^31 - 1 bytes");
+  *pixels = fg.pixels;
+  return VOF_OK;
+}
+}  // namespace
+int vof_frame_set_lut(vof2d_handle h, const uint8_t* lut) {
+  if (!h) return VOF_EINVAL;
+  if (const int rc = check_frames_allowed(h)) return rc;
+  return frame_set_lut(h, lut);
+}
+int vof_frame(vof2d_handle h, const vof2d_frame_spec* spec, uint8_t* rgb, int64_t cap_bytes, double* means, int64_t cap_means, double* summary) {
+  if (!h || !summary) return VOF_EINVAL;
+  int64_t pixels = 0;
+  if (const int rc = check_frame_spec(h, spec, &pixels)) return rc;
+  if (cap_bytes < 0 || cap_means < 0) return fail(h, VOF_EINVAL, "a cap is negative");
+  if ((rgb && cap_bytes < pixels * 3) || (means && cap_means < pixels)) return fail(h, VOF_EINVAL, "cap_bytes is smaller than pw * ph * 3 or cap_means smaller than pw * ph");
+  if (const int rc = check_frames_allowed(h)) return rc;
+  if (spec->quantity == FQ_DYE && !h->dye_on) return fail(h, VOF_ESTATE, "the handle has no dye (vof_dye_set)");
+  return frame_run(h, *spec, rgb, means, summary);
+}
+int vof_step_frames(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, const vof2d_frame_spec* spec, uint8_t* out_rgb,
+                    double* out_summaries, int64_t cap_frames, int64_t* frames_written) {
+  if (!h) return VOF_EINVAL;
+  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
+  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  int64_t pixels = 0;
+  if (const int rc = check_frame_spec(h, spec, &pixels)) return rc;
+  if (cap_frames < nsteps / every) return fail(h, VOF_EINVAL, "cap_frames is smaller than nsteps / every");
+  if ((!out_rgb || !out_summaries) && nsteps / every > 0) return fail(h, VOF_EINVAL, "out_rgb or out_summaries is NULL and at least one frame is due");
+  if (const int rc = check_frames_allowed(h)) return rc;
+  if (spec->quantity == FQ_DYE && !h->dye_on) return fail(h, VOF_ESTATE, "the handle has no dye (vof_dye_set)");
+  if (nsteps == 0) {
+    if (frames_written) *frames_written = 0;
+    return VOF_OK;
+  }
+  return step_frames_n(h, nsteps, every, mg_cycles, criterion, *spec, out_rgb, out_summaries, frames_written);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

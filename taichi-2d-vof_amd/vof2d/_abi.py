@@ -40,6 +40,13 @@ VOF_GAUGE_SUM_N = 8
 (VOF_DYE_ISTEP, VOF_DYE_CELLS, VOF_DYE_SUM_C, VOF_DYE_SUM_CI, VOF_DYE_SUM_CJ, VOF_DYE_SUM_C2, VOF_DYE_SUM_CF, VOF_DYE_SUM_CU, VOF_DYE_SUM_CV,
  VOF_DYE_MIN_C, VOF_DYE_MAX_C, VOF_DYE_MAX_EXCESS) = range(12)
 VOF_DYE_N = 16
+# vof_frame, vof_step_frames: the quantities, the flags, the rows of the colour table and the slots of the summary (vof2d/frames.py)
+VOF_FRAME_F, VOF_FRAME_U, VOF_FRAME_V, VOF_FRAME_SPEED, VOF_FRAME_P, VOF_FRAME_VORT, VOF_FRAME_DYE = range(7)
+VOF_FRAME_CONTOUR, VOF_FRAME_SYMMETRIC = 1, 2
+VOF_FRAME_LUT_ROWS = 258
+(VOF_FRAME_SUM_PW, VOF_FRAME_SUM_PH, VOF_FRAME_SUM_ISTEP, VOF_FRAME_SUM_LO, VOF_FRAME_SUM_HI, VOF_FRAME_SUM_NAN_PIXELS,
+ VOF_FRAME_SUM_CONTOUR_PIXELS) = range(7)
+VOF_FRAME_SUM_N = 8
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -71,8 +78,19 @@ class Desc(C.Structure):
     ]
 
 
+class FrameSpec(C.Structure):
+    """struct vof2d_frame_spec"""
+    _fields_ = [
+        ("quantity", C.c_int32),
+        ("bx", C.c_int32), ("by", C.c_int32),
+        ("flags", C.c_int32),
+        ("lo", C.c_double), ("hi", C.c_double),
+    ]
+
+
 H = C.c_void_p
 _i32, _i64, _dbl, _str = C.c_int32, C.c_int64, C.c_double, C.c_char_p
+_u8p = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); the complete symbol list of include/vof2d.h
 SIGNATURES = {
@@ -119,6 +137,9 @@ SIGNATURES = {
     "dye_advance": (C.c_int, [H]),
     "dye_stats": (C.c_int, [H, C.POINTER(_dbl)]),
     "step_dye": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
+    "frame_set_lut": (C.c_int, [H, _u8p]),
+    "frame": (C.c_int, [H, C.POINTER(FrameSpec), _u8p, _i64, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
+    "step_frames": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(FrameSpec), _u8p, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
     "get_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "set_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "get_rows": (C.c_int, [H, _str, _i32, _i32, C.c_void_p, C.c_size_t]),
@@ -157,7 +178,7 @@ GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_pr
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
             "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "blobs",
             "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges",
-            "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye")
+            "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye", "frame_set_lut", "frame", "step_frames")
 
 
 class Api:

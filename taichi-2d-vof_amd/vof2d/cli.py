@@ -105,8 +105,40 @@ def build_parser():
                      help='every N steps append a row to data/dye.csv: amount, centroid, mean, variance, share outside the liquid, the '
                           "dye's velocity, min and max of the dye and max(C - F), reduced on the device")
     ext.add_argument('--dye-save-every', type=int, default=None, metavar='M', help='every M steps write the dye to data/dye_NNNNNN.npy')
+    ext.add_argument('--frames-every', type=int, default=None, metavar='N',
+                     help='every N steps write output/frame_NNNNNN.png (named by istep) -- a picture rendered on the device: box averages, a '
+                          'colour table, 8-bit RGB, three bytes a pixel copied out (vof_frame) -- and append istep, time, lo, hi, nan_pixels '
+                          'to data/frames.csv; needs no matplotlib with --frame-cmap grey; one GPU')
+    ext.add_argument('--frame', default='F:0:1', metavar='QUANTITY[:LO:HI]',
+                     help='what a frame shows: F, U, V, SPEED, P, VORT or DYE, over the fixed range LO..HI; without a range the range of each '
+                          'picture, symmetric about zero for U, V and VORT (default F:0:1)')
+    ext.add_argument('--frame-block', type=int, default=None, metavar='K',
+                     help='K x K cells per pixel (default: the smallest K that keeps the longer side within 1024 pixels)')
+    ext.add_argument('--frame-cmap', default=None, metavar='NAME',
+                     help="the colour map, one of matplotlib's or `grey` (default Blues for F and DYE, coolwarm for U, V, VORT, plasma for SPEED, P)")
+    ext.add_argument('--frame-contour', action='store_true', help='mark the interface (the 0.5 level of the box-averaged F) on the frames')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
+
+
+def parse_frame(text):
+    """(quantity, lo, hi) of a --frame value QUANTITY[:LO:HI]; lo == hi == 0.0 without a range.  ValueError with the reason."""
+    from . import frames
+    parts = text.split(':')
+    name = parts[0].upper()
+    if name not in frames.QUANTITIES:
+        raise ValueError("--frame: %r is not one of %s" % (parts[0], ', '.join(frames.QUANTITIES)))
+    if len(parts) == 1:
+        return name, 0.0, 0.0
+    if len(parts) != 3:
+        raise ValueError("--frame needs QUANTITY or QUANTITY:LO:HI, not %r" % text)
+    try:
+        lo, hi = float(parts[1]), float(parts[2])
+    except ValueError:
+        raise ValueError("--frame %s: LO and HI must be numbers" % text)
+    if not (lo < hi and abs(lo) != float('inf') and abs(hi) != float('inf')):
+        raise ValueError("--frame %s: needs finite LO < HI" % text)
+    return name, lo, hi
 
 
 def dye_conflicts(args):
@@ -181,6 +213,19 @@ def parse_args(argv=None):
         parser.error("--dye-every and --dye-save-every report the dye of --dye-box X0,X1,Y0,Y1 / --dye-file FILE.npy: pass one")
     if dye_conflicts(args):
         parser.error(dye_conflicts(args))
+    if args.frames_every is not None:
+        if args.frames_every < 1:
+            parser.error("--frames-every needs N >= 1")
+        if args.gpus > 1:
+            parser.error("--frames-every runs on one GPU (frames over row strips are not built): drop --gpus")
+        if args.frame_block is not None and args.frame_block < 1:
+            parser.error("--frame-block needs K >= 1")
+        try:
+            name = parse_frame(args.frame)[0]
+        except ValueError as e:
+            parser.error(str(e))
+        if name == "DYE" and not (args.dye_box or args.dye_file or args.resume):
+            parser.error("--frame DYE shows the dye of --dye-box X0,X1,Y0,Y1 / --dye-file FILE.npy: pass one")
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -685,6 +730,23 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             with open(depths_path, 'w') as f:
                 f.write(gauges_mod.DEPTHS_CSV_HEADER + '\n')
 
+    # pictures rendered on the device (vof_frame) are taken between calls too: three bytes a pixel leave the device
+    frames_every = (getattr(args, "frames_every", None) or 0) if world == 1 else 0
+    frames_path = 'data/frames.csv'
+    if frames_every:
+        from . import frames as frames_mod
+        if not hasattr(api, "frame"):
+            raise SystemExit("--frames-every needs the frame verbs of the HIP library (vof_frame): this backend has none")
+        fq, flo, fhi = parse_frame(args.frame)
+        block = args.frame_block or frames_mod.default_block(nx, ny)
+        cmap = args.frame_cmap or frames_mod.DEFAULT_CMAP[fq]
+        eng.set_frame_lut(None if cmap in ("grey", "gray") else frames_mod.lut(cmap))
+        frame_kw = dict(quantity=fq, bx=block, by=block, lo=flo, hi=fhi, contour=bool(args.frame_contour), symmetric=flo == fhi and fq in frames_mod.SIGNED)
+        os.makedirs('output', exist_ok=True)
+        if not (args.resume and os.path.exists(frames_path) and os.path.getsize(frames_path) > 0):
+            with open(frames_path, 'w') as f:
+                f.write('istep,time,lo,hi,nan_pixels\n')
+
     diag_every = drv.diag_every
     stop_at_diag = bool(diag_every) and not drv.diag_in_advance
     diag_last = None
@@ -741,6 +803,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             n = min(n, depths_every - i % depths_every)
         if dye_save:
             n = min(n, dye_save - i % dye_save)
+        if frames_every:
+            n = min(n, frames_every - i % frames_every)
         if args.steps:
             n = min(n, args.steps - i)
         return n
@@ -797,6 +861,11 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                             f.write(','.join([str(k), repr(k * dt)] + [repr(float(d[c])) for c in dye_mod.DERIVED]) + '\n')
                 if dye_save and istep % dye_save == 0:
                     np.save('data/dye_%06d.npy' % istep, drv.dye())
+            if frames_every and istep % frames_every == 0:
+                rgb, _, fs = eng.frame(**frame_kw)
+                frames_mod.write_png('output/frame_%06d.png' % istep, rgb)
+                with open(frames_path, 'a') as f:
+                    f.write('%d,%r,%r,%r,%d\n' % (istep, istep * dt, fs["LO"], fs["HI"], fs["NAN_PIXELS"]))
             if args.save_every and istep % args.save_every == 0:
                 if dye_on:                                          # (beside the checkpoint, whose format stays as it is)
                     np.savez('data/dye_state.tmp.npz', C=drv.dye(), istep=np.int64(istep))

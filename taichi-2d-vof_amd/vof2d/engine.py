@@ -363,6 +363,48 @@ class Engine:
                                    out.ctypes.data_as(C.POINTER(C.c_double)) if rows else None, rows, C.byref(done)), "step_dye")
         return out[:done.value]
 
+    def set_frame_lut(self, table=None):
+        """vof_frame_set_lut: replaces the handle's colour table by the (258, 3) uint8 array (frames.lut samples matplotlib's
+        maps into one); None restores the default."""
+        if table is None:
+            self._ck(self.api.frame_set_lut(self._h, None), "frame_set_lut")
+            return
+        t = np.ascontiguousarray(table, dtype=np.uint8)
+        if t.shape != (_abi.VOF_FRAME_LUT_ROWS, 3):
+            raise ValueError("frame lut: expected shape (%d, 3), got %s" % (_abi.VOF_FRAME_LUT_ROWS, t.shape))
+        self._ck(self.api.frame_set_lut(self._h, t.ctypes.data_as(C.POINTER(C.c_uint8))), "frame_set_lut")
+
+    def frame(self, quantity="F", bx=1, by=None, lo=0.0, hi=0.0, contour=False, symmetric=False, rgb=True, means=False):
+        """vof_frame: the quantity box-averaged over bx x by cells per pixel and coloured on the device; returns (rgb, means,
+        summary): the (ph, pw, 3) uint8 picture (top of the domain first), the (pw, ph) float64 means (each None unless asked
+        for) and the summary as a dict keyed by frames.SUMMARY.  lo == hi: the range of the picture."""
+        from . import frames
+        s = frames.spec(quantity, bx, by, lo, hi, contour, symmetric)
+        pw, ph = frames.shape(self.nx, self.ny, min(max(s.bx, 1), self.nx), min(max(s.by, 1), self.ny))
+        img = np.empty((ph, pw, 3), dtype=np.uint8) if rgb else None
+        mean = np.empty((pw, ph), dtype=np.float64) if means else None
+        summ = (C.c_double * _abi.VOF_FRAME_SUM_N)()
+        self._ck(self.api.frame(self._h, C.byref(s), img.ctypes.data_as(C.POINTER(C.c_uint8)) if rgb else None, img.nbytes if rgb else 0,
+                                mean.ctypes.data_as(C.POINTER(C.c_double)) if means else None, mean.size if means else 0, summ), "frame")
+        return img, mean, frames.summary_of(list(summ))
+
+    def step_frames(self, nsteps, every, quantity="F", bx=1, by=None, lo=0.0, hi=0.0, contour=False, symmetric=False, mg_cycles=0, criterion="rel"):
+        """vof_step_frames: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), a frame rendered on the device
+        behind every `every` of them, one read-back at the end; returns (pictures, summaries): the (frames, ph, pw, 3) uint8
+        array and a list of dicts keyed by frames.SUMMARY."""
+        from . import frames
+        crit = criterion_code(criterion)
+        nsteps, every = int(nsteps), int(every)
+        due = max(nsteps, 0) // every if every >= 1 else 0
+        s = frames.spec(quantity, bx, by, lo, hi, contour, symmetric)
+        pw, ph = frames.shape(self.nx, self.ny, min(max(s.bx, 1), self.nx), min(max(s.by, 1), self.ny))
+        out = np.zeros((due, ph, pw, 3), dtype=np.uint8)
+        summ = np.zeros((due, _abi.VOF_FRAME_SUM_N), dtype=np.float64)
+        done = C.c_int64()
+        self._ck(self.api.step_frames(self._h, nsteps, every, int(mg_cycles), crit, C.byref(s), out.ctypes.data_as(C.POINTER(C.c_uint8)) if due else None,
+                                      summ.ctypes.data_as(C.POINTER(C.c_double)) if due else None, due, C.byref(done)), "step_frames")
+        return out[:done.value], [frames.summary_of(list(r)) for r in summ[:done.value]]
+
     def _sized_rows(self, cap_attr, first_cap, width, summ, count_slot, what, call):
         """The rows of a verb that fills at most `cap` of them and reports in summ[count_slot] how many there are:
         call(rows pointer, cap) with the capacity the last call needed (plus a margin), once more if the list has outgrown it."""

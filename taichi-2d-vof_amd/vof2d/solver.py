@@ -196,6 +196,19 @@ class VOF2D:
         """nsteps steps, the dye moved behind each, a row of its statistics recorded on the device every `every` steps (vof_step_dye)."""
         return self.eng.step_dye(nsteps, every, mg_cycles, criterion)
 
+    def set_frame_lut(self, table=None):
+        """Give the handle a colour table for its frames: (258, 3) uint8, vof2d/frames.py: lut (vof_frame_set_lut; None: the grey ramp)."""
+        self.eng.set_frame_lut(table)
+
+    def frame(self, quantity="F", bx=1, by=None, lo=0.0, hi=0.0, contour=False, symmetric=False, rgb=True, means=False):
+        """A picture of F, U, V, SPEED, P, VORT or DYE rendered on the device, bx x by cells per pixel (vof_frame): (rgb, means, summary),
+        vof2d/frames.py."""
+        return self.eng.frame(quantity, bx, by, lo, hi, contour, symmetric, rgb, means)
+
+    def step_frames(self, nsteps, every, quantity="F", bx=1, by=None, lo=0.0, hi=0.0, contour=False, symmetric=False, mg_cycles=0, criterion="rel"):
+        """nsteps steps with such a picture rendered on the device every `every` steps (vof_step_frames): (pictures, summaries)."""
+        return self.eng.step_frames(nsteps, every, quantity, bx, by, lo, hi, contour, symmetric, mg_cycles, criterion)
+
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)
