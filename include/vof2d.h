@@ -580,6 +580,75 @@ int vof_frame(vof2d_handle h, const vof2d_frame_spec* spec, uint8_t* rgb, int64_
               double* summary /* VOF_FRAME_SUM_N */);
 int vof_step_frames(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
                     const vof2d_frame_spec* spec, uint8_t* out_rgb, double* out_summaries, int64_t cap_frames, int64_t* frames_written);
+/* Extension: statistics over a run.  Per interior cell (i in [1, nx], j in [1, ny]) the handle keeps running sums of F, u, v and their
+ * products, the envelopes of F and of the speed, the number of samples the cell was wet in and the step the front first arrived at: the
+ * time-mean, the variance and the Reynolds stress of a sloshing flow, a flood or arrival map -- without a field leaving the device between
+ * the samples.  The accumulators are planes of doubles for both dtypes, in two groups chosen by a mask:
+ *   VOF_STATS_MOMENTS   SUM_F, SUM_F2, SUM_U, SUM_V, SUM_UU, SUM_VV, SUM_UV, SUM_FU, SUM_FV
+ *   VOF_STATS_ENVELOPE  MAX_F, MAX_SPEED2, WET, ARRIVAL
+ * One sample takes the fields vof_get_field would return at that moment (the ghost cells are settled first); every operand is converted to
+ * double on load and every product and sum below is rounded on its own, in the FMA-contracted build too.  Per cell, in this order:
+ *   f = F[i,j]   Fc = fmin(fmax(f, 0), 1)   uc = (u[i,j] + u[i+1,j]) * 0.5   vc = (v[i,j] + v[i,j+1]) * 0.5      (Fc, uc, vc of vof_diagnostics)
+ *   SUM_F += Fc   SUM_F2 += Fc * Fc   SUM_U += uc   SUM_V += vc   SUM_UU += uc * uc   SUM_VV += vc * vc   SUM_UV += uc * vc
+ *   SUM_FU += Fc * uc   SUM_FV += Fc * vc
+ *   s2 = uc * uc + vc * vc   MAX_SPEED2 = max(MAX_SPEED2, s2)   MAX_F = max(MAX_F, Fc)     (a NaN operand counts as +inf, as in vof_diagnostics)
+ *   wet = (Fc >= level)   WET += wet ? 1.0 : 0.0   if (wet && ARRIVAL < 0) ARRIVAL = (double)istep
+ * The sums propagate a NaN of u or v; the plain clamp takes a NaN F to Fc = 0, a dry cell.  A cell's chain depends on the samples alone: the
+ * same samples give the same bits.  Pressure is left out on purpose: p is defined up to a constant that the ten sweeps move from step to
+ * step, so its time-mean means nothing (the gauges record it raw).
+ *   vof_stats_begin    allocates the planes of `mask` (VOF_STATS_MOMENTS | VOF_STATS_ENVELOPE) and clears them: the sums, MAX_F, MAX_SPEED2
+ *                      and WET to 0, ARRIVAL to -1, the sample count to 0.  A second call clears again.  mask == 0 releases the statistics
+ *                      (level is not looked at).  A mask outside {0, 1, 2, 3}, a level that is NaN or outside (0, 1]: VOF_EINVAL, the old
+ *                      statistics stay.  VOF_ENOMEM leaves the handle without statistics
+ *   vof_stats_sample   one sample of the state as it is, with the handle's istep.  Enqueues only; the handle counts the samples and keeps
+ *                      the istep of the first and of the last
+ *   vof_stats_get      one plane, dense (nx, ny) doubles indexed [i-1, j-1]; synchronises.  cap_elems < nx ny, dst == NULL or a slot outside
+ *                      [0, VOF_STATS_PLANES): VOF_EINVAL; a slot of a group that is off: VOF_ESTATE
+ *   vof_stats_summary  VOF_STATS_SUM_N doubles (unused slots read 0): SAMPLES, ISTEP_FIRST, ISTEP_LAST (0 before the first sample), MASK, LEVEL,
+ *                      CELLS = nx ny; EVER_WET, the cells with ARRIVAL >= 0, and MAX_SPEED2, the maximum of that plane, reduced on the device in
+ *                      a fixed order without floating-point atomics -- both read 0 if the envelope is off.  Synchronises
+ *   vof_step_stats     for r = 0 .. nsteps / every - 1: `every` steps -- exactly vof_step(h, every) if mg_cycles == 0, exactly
+ *                      vof_step_mg(h, every, mg_cycles, criterion, NULL, NULL, NULL) if mg_cycles >= 1 --, then one vof_stats_sample.  A
+ *                      remainder of nsteps % every steps is stepped and gets no sample.  Nothing waits for the device; *samples_taken (may
+ *                      be NULL) is set.  The argument errors are those of vof_step_gauges (every < 1, nsteps < 0, mg_cycles < 0, a bad
+ *                      criterion with mg_cycles >= 1)
+ * Without statistics begun, sample, get, summary and step_stats return VOF_ESTATE.  Whole-domain handles only (a strip returns VOF_ESTATE and
+ * is left untouched); VOF_ESTATE too while a phased step is in progress.  No field, istep, counter or cached graph changes; every readable
+ * field, istep and courant_violations end where vof_step(nsteps) / vof_step_mg(nsteps, ...) alone leaves them, and a step verb that follows
+ * gives the bits it would have given without the call.  Because vof_stats_sample only enqueues, it may be called between any other stepping
+ * verbs (vof_step_diag, vof_step_dye, vof_step_frames, ...).  vof_set_init_F, vof_set_field and the dye leave the statistics alone;
+ * vof_destroy releases them.  A refused call leaves the handle and the outputs untouched.  Knob "stats_chunk_rows"
+ * (vof_set_param; default 0: the rule of vof_diagnostics) sets the rows a wave of the pass marches -- the same bits. */
+#define VOF_STATS_MOMENTS 1
+#define VOF_STATS_ENVELOPE 2
+#define VOF_STATS_SUM_F 0
+#define VOF_STATS_SUM_F2 1
+#define VOF_STATS_SUM_U 2
+#define VOF_STATS_SUM_V 3
+#define VOF_STATS_SUM_UU 4
+#define VOF_STATS_SUM_VV 5
+#define VOF_STATS_SUM_UV 6
+#define VOF_STATS_SUM_FU 7
+#define VOF_STATS_SUM_FV 8
+#define VOF_STATS_MAX_F 9
+#define VOF_STATS_MAX_SPEED2 10
+#define VOF_STATS_WET 11
+#define VOF_STATS_ARRIVAL 12
+#define VOF_STATS_PLANES 13
+#define VOF_STATS_SUM_SAMPLES 0
+#define VOF_STATS_SUM_ISTEP_FIRST 1
+#define VOF_STATS_SUM_ISTEP_LAST 2
+#define VOF_STATS_SUM_MASK 3
+#define VOF_STATS_SUM_LEVEL 4
+#define VOF_STATS_SUM_CELLS 5
+#define VOF_STATS_SUM_EVER_WET 6
+#define VOF_STATS_SUM_MAX_SPEED2 7
+#define VOF_STATS_SUM_N 16
+int vof_stats_begin(vof2d_handle h, int32_t mask, double level);
+int vof_stats_sample(vof2d_handle h);
+int vof_stats_get(vof2d_handle h, int32_t slot, double* dst, int64_t cap_elems);
+int vof_stats_summary(vof2d_handle h, double* out /* VOF_STATS_SUM_N */);
+int vof_step_stats(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, int64_t* samples_taken);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

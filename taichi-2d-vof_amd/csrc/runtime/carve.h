@@ -95,4 +95,24 @@ inline FrameCarve carve_frame(size_t col_partials, size_t pixels, size_t f_parti
   return c;
 }
 
+// vof_stats_*: one plane of doubles per accumulator of the groups chosen by `mask` (bit 0: the nine moments, bit 1: the four of the
+// envelope), in slot order; a plane is `rows` rows of `pitch` doubles, the pitch a whole number of wave tiles so that a lane's columns
+// are one aligned 16-byte vector and no lane of a launch leaves its row.  A plane of a group that is off has no range (kNoRange).
+// Behind the planes: the block partials of k_stats_summary, its two results.
+constexpr int kStatsPlanes = 13, kStatsMomentPlanes = 9;
+constexpr size_t kNoRange = ~(size_t)0;
+inline size_t stats_pitch(size_t ny, size_t tile_cols) { return (ny + tile_cols - 1) / tile_cols * tile_cols; }
+struct StatsCarve { size_t plane[kStatsPlanes], plane_bytes, planes_total, part, sum, total; };
+inline StatsCarve carve_stats(size_t rows, size_t pitch, int mask, size_t part_doubles) {
+  Carve a;
+  StatsCarve c;
+  c.plane_bytes = rows * pitch * sizeof(double);
+  for (int k = 0; k < kStatsPlanes; ++k) c.plane[k] = (mask & (k < kStatsMomentPlanes ? 1 : 2)) ? a.take(c.plane_bytes, 16) : kNoRange;
+  c.planes_total = a.total;
+  c.part = a.take(part_doubles * sizeof(double), 16);
+  c.sum = a.take(2 * sizeof(double), 16);
+  c.total = a.total;
+  return c;
+}
+
 }  // namespace vof

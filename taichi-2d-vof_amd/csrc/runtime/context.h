@@ -231,7 +231,13 @@ struct vof2d_ctx {
   bool dye_on = false;
   int dye_cur = 0;
   int dye_fused = 1;              // knob "dye_fused": the dye's transport as ONE launch (k_dye); 0: the two sweeps, k_post (same bits: the A/B partner)
-  char* h_depths = nullptr;      // pinned host copy of the results of a vof_depths pass (one copy out, then memcpy to the caller's arrays)
+  // vof_stats_* (runtime/stats.h): the groups of buf.stats (0: no statistics), the wet level, the samples taken since vof_stats_begin
+  // and the istep of the first and of the last of them
+  int stats_mask = 0;
+  double stats_level = 0.0;
+  int64_t stats_samples = 0, stats_first = 0, stats_last = 0;
+  int stats_chunk = 0;            // knob "stats_chunk_rows": rows per wave chunk of k_stats (0 = the rule of k_diag)
+  char* h_depths = nullptr;     // pinned host copy of the results of a vof_depths pass (one copy out, then memcpy to the caller's arrays)
   size_t h_depths_bytes = 0;
   char* h_frame = nullptr;       // pinned host copy of the results of a vof_frame call (one copy out, then memcpy to the caller's arrays)
   size_t h_frame_bytes = 0;

@@ -25,6 +25,7 @@
 //   runtime/depths.h     the buffers, launches and copies of vof_depths and vof_gauges_*, the loop of vof_step_gauges
 //   runtime/dye.h        the dye arrays, launches and copies of vof_dye_*, the loop of vof_step_dye
 //   runtime/frames.h     the colour table, the buffers, launches and copies of vof_frame, the loop of vof_step_frames
+//   runtime/stats.h      the accumulator planes, launches and copies of vof_stats_*, the loop of vof_step_stats
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -41,6 +42,7 @@
 #include "runtime/depths.h"
 #include "runtime/dye.h"
 #include "runtime/frames.h"
+#include "runtime/stats.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -70,6 +72,7 @@ const Knob kKnobs[] = {
   KNOB("tb_slow10", tb_slow10, false), KNOB("tune_period", tune.period, false),
   KNOB("mg_nu", mg_nu, true), KNOB("mg_levels", mg_levels, true), KNOB("mg_graph", mg_graph, true),
   KNOB("mg_coarse_block", mg_coarse_block, false), KNOB("dye_fused", dye_fused, true),
+  KNOB("stats_chunk_rows", stats_chunk, false),
 };
 #undef KNOB
 const Knob* find_knob(const char* name) {
@@ -655,6 +658,53 @@ int vof_step_frames(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cy
     return VOF_OK;
   }
   return step_frames_n(h, nsteps, every, mg_cycles, criterion, *spec, out_rgb, out_summaries, frames_written);
+}
+
+// ---- per-cell statistics over a run (kernels/stats.h, runtime/stats.h)
+namespace {
+int check_stats_allowed(vof2d_ctx* h, bool needs_stats) {
+  if (const int rc = check_whole_domain(h, "the vof_stats_* verbs and vof_step_stats need the whole domain in one handle (statistics over row strips are not built)")) return rc;
+  if (const int rc = check_no_phased_step(h)) return rc;
+  return needs_stats && !h->stats_mask ? fail(h, VOF_ESTATE, "the handle has no statistics (vof_stats_begin)") : VOF_OK;
+}
+}  // namespace
+int vof_stats_begin(vof2d_handle h, int32_t mask, double level) {
+  if (!h) return VOF_EINVAL;
+  if (mask < 0 || mask > (VOF_STATS_MOMENTS | VOF_STATS_ENVELOPE)) return fail(h, VOF_EINVAL, "mask must be 0 or VOF_STATS_MOMENTS | VOF_STATS_ENVELOPE");
+  if (mask != 0 && !(level > 0.0 && level <= 1.0)) return fail(h, VOF_EINVAL, "level must lie in (0, 1]");
+  if (const int rc = check_stats_allowed(h, false)) return rc;
+  return stats_begin(h, mask, level);
+}
+int vof_stats_sample(vof2d_handle h) {
+  if (!h) return VOF_EINVAL;
+  if (const int rc = check_stats_allowed(h, true)) return rc;
+  return stats_sample(h);
+}
+int vof_stats_get(vof2d_handle h, int32_t slot, double* dst, int64_t cap_elems) {
+  if (!h || !dst) return VOF_EINVAL;
+  if (slot < 0 || slot >= VOF_STATS_PLANES) return fail(h, VOF_EINVAL, "slot is not one of VOF_STATS_SUM_F .. VOF_STATS_ARRIVAL");
+  if (cap_elems < (int64_t)h->d.nx * h->d.ny) return fail(h, VOF_EINVAL, "cap_elems is smaller than nx ny");
+  if (const int rc = check_stats_allowed(h, true)) return rc;
+  if (!(h->stats_mask & (slot < kStatsMoments ? VOF_STATS_MOMENTS : VOF_STATS_ENVELOPE))) return fail(h, VOF_ESTATE, "the group of this slot is off (vof_stats_begin)");
+  return stats_get(h, slot, dst);
+}
+int vof_stats_summary(vof2d_handle h, double* out) {
+  if (!h || !out) return VOF_EINVAL;
+  if (const int rc = check_stats_allowed(h, true)) return rc;
+  return stats_summary(h, out);
+}
+int vof_step_stats(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, int64_t* samples_taken) {
+  if (!h) return VOF_EINVAL;
+  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
+  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (const int rc = check_stats_allowed(h, true)) return rc;
+  if (nsteps == 0) {
+    if (samples_taken) *samples_taken = 0;
+    return VOF_OK;
+  }
+  return step_stats_n(h, nsteps, every, mg_cycles, criterion, samples_taken);
 }
 
 int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void* dst, size_t nbytes) {

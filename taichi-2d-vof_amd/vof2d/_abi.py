@@ -47,6 +47,13 @@ VOF_FRAME_LUT_ROWS = 258
 (VOF_FRAME_SUM_PW, VOF_FRAME_SUM_PH, VOF_FRAME_SUM_ISTEP, VOF_FRAME_SUM_LO, VOF_FRAME_SUM_HI, VOF_FRAME_SUM_NAN_PIXELS,
  VOF_FRAME_SUM_CONTOUR_PIXELS) = range(7)
 VOF_FRAME_SUM_N = 8
+# vof_stats_*: the groups, the planes in slot order and the slots of the summary (vof2d/stats.py)
+VOF_STATS_MOMENTS, VOF_STATS_ENVELOPE = 1, 2
+(VOF_STATS_SUM_F, VOF_STATS_SUM_F2, VOF_STATS_SUM_U, VOF_STATS_SUM_V, VOF_STATS_SUM_UU, VOF_STATS_SUM_VV, VOF_STATS_SUM_UV, VOF_STATS_SUM_FU,
+ VOF_STATS_SUM_FV, VOF_STATS_MAX_F, VOF_STATS_MAX_SPEED2, VOF_STATS_WET, VOF_STATS_ARRIVAL, VOF_STATS_PLANES) = range(14)
+(VOF_STATS_SUM_SAMPLES, VOF_STATS_SUM_ISTEP_FIRST, VOF_STATS_SUM_ISTEP_LAST, VOF_STATS_SUM_MASK, VOF_STATS_SUM_LEVEL, VOF_STATS_SUM_CELLS,
+ VOF_STATS_SUM_EVER_WET, VOF_STATS_SUM_MAX_SPEED2) = range(8)
+VOF_STATS_SUM_N = 16
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -140,6 +147,11 @@ SIGNATURES = {
     "frame_set_lut": (C.c_int, [H, _u8p]),
     "frame": (C.c_int, [H, C.POINTER(FrameSpec), _u8p, _i64, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
     "step_frames": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(FrameSpec), _u8p, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
+    "stats_begin": (C.c_int, [H, _i32, _dbl]),
+    "stats_sample": (C.c_int, [H]),
+    "stats_get": (C.c_int, [H, _i32, C.POINTER(_dbl), _i64]),
+    "stats_summary": (C.c_int, [H, C.POINTER(_dbl)]),
+    "step_stats": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_i64)]),
     "get_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "set_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "get_rows": (C.c_int, [H, _str, _i32, _i32, C.c_void_p, C.c_size_t]),
@@ -178,7 +190,8 @@ GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_pr
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
             "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "blobs",
             "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges",
-            "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye", "frame_set_lut", "frame", "step_frames")
+            "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye", "frame_set_lut", "frame", "step_frames",
+            "stats_begin", "stats_sample", "stats_get", "stats_summary", "step_stats")
 
 
 class Api:

@@ -117,6 +117,19 @@ def build_parser():
     ext.add_argument('--frame-cmap', default=None, metavar='NAME',
                      help="the colour map, one of matplotlib's or `grey` (default Blues for F and DYE, coolwarm for U, V, VORT, plasma for SPEED, P)")
     ext.add_argument('--frame-contour', action='store_true', help='mark the interface (the 0.5 level of the box-averaged F) on the frames')
+    ext.add_argument('--stats-every', type=int, default=None, metavar='N',
+                     help='every N steps take one sample of per-cell statistics on the device (vof_stats_sample): running sums of F, u, v and '
+                          'their products, the envelopes of F and of the speed, the wet time and the step the front first arrived; works beside '
+                          '--diag-every, --dye-*, --frames-every, --gauges-every, --tracers and --mg-cycles; one GPU.  With --resume the '
+                          'statistics start anew: the planes are not part of a checkpoint')
+    ext.add_argument('--stats', default='MOMENTS,ENVELOPE', metavar='GROUPS',
+                     help='the groups --stats-every keeps, comma-separated: MOMENTS (means, variances, Reynolds stress, liquid-phase velocity), '
+                          'ENVELOPE (max F, max speed, wet fraction, arrival time); default both')
+    ext.add_argument('--stats-level', type=float, default=0.5, metavar='L', help='a cell counts as wet in a sample if its clamped F is >= L, in (0, 1] (default 0.5)')
+    ext.add_argument('--stats-from', type=int, default=0, metavar='STEP', help='no sample before that step (to skip a spin-up)')
+    ext.add_argument('--stats-save-every', type=int, default=None, metavar='M',
+                     help='every M steps, and at the end of the run, write data/stats_NNNNNN.npz -- the raw planes, the sample count N and the '
+                          'derived arrays -- and append a line of the summary to data/stats.csv (default: at the end of the run only)')
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
 
@@ -226,6 +239,25 @@ def parse_args(argv=None):
             parser.error(str(e))
         if name == "DYE" and not (args.dye_box or args.dye_file or args.resume):
             parser.error("--frame DYE shows the dye of --dye-box X0,X1,Y0,Y1 / --dye-file FILE.npy: pass one")
+    if args.stats_every is not None:
+        from . import stats as stats_mod
+        if args.stats_every < 1:
+            parser.error("--stats-every needs N >= 1")
+        if args.gpus > 1:
+            parser.error("--stats-every runs on one GPU (statistics over row strips are not built): drop --gpus")
+        if args.stats_save_every is not None and args.stats_save_every < 1:
+            parser.error("--stats-save-every needs M >= 1")
+        if not 0.0 < args.stats_level <= 1.0:
+            parser.error("--stats-level needs 0 < L <= 1")
+        if args.stats_from < 0:
+            parser.error("--stats-from needs STEP >= 0")
+        try:
+            if not stats_mod.mask_of(args.stats):
+                raise ValueError("--stats names no group")
+        except ValueError as e:
+            parser.error("--stats: %s" % e)
+    elif args.stats_save_every is not None:
+        parser.error("--stats-save-every writes the statistics of --stats-every N: pass that too")
     if args.mg_cycles != 0:
         if args.mg_cycles < 1:
             parser.error("--mg-cycles needs K >= 1")
@@ -747,6 +779,34 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             with open(frames_path, 'w') as f:
                 f.write('istep,time,lo,hi,nan_pixels\n')
 
+    # per-cell statistics over the run (vof_stats_*): a sample only enqueues, so it is taken between the calls of whatever loop steps
+    stats_every = (getattr(args, "stats_every", None) or 0) if world == 1 else 0
+    stats_save = getattr(args, "stats_save_every", None) or 0
+    stats_from = getattr(args, "stats_from", 0)
+    stats_path, stats_saved_at = 'data/stats.csv', -1
+    if stats_every:
+        from . import stats as stats_mod
+        if not hasattr(api, "stats_sample"):
+            raise SystemExit("--stats-every needs the statistics verbs of the HIP library (vof_stats_*): this backend has none")
+        stats_mask = stats_mod.mask_of(args.stats)
+        eng.stats_begin(stats_mask, args.stats_level)
+        say(f'>>> Statistics begun: {", ".join(g for g, b in stats_mod.GROUPS.items() if stats_mask & b)}, a sample every {stats_every} steps'
+            + (f' from step {stats_from} on' if stats_from else '') + (' (they start anew: not part of a checkpoint).' if args.resume else '.'))
+        if not (args.resume and os.path.exists(stats_path) and os.path.getsize(stats_path) > 0):
+            with open(stats_path, 'w') as f:
+                f.write(','.join(('istep', 'time') + tuple(k.lower() for k in stats_mod.SUMMARY)) + '\n')
+
+    def save_stats(k):
+        """data/stats_NNNNNN.npz: the raw planes, N and the derived arrays; a line of the summary to data/stats.csv."""
+        summ = eng.stats_summary()
+        planes = {p: eng.stats_plane(p) for p in stats_mod.planes_of(stats_mask)}
+        tmp = 'data/stats_%06d.tmp.npz' % k
+        np.savez(tmp, N=np.int64(summ["SAMPLES"]), istep=np.int64(k), mask=np.int64(stats_mask), level=np.float64(args.stats_level), **planes,
+                 **stats_mod.derive(planes, summ["SAMPLES"], dt))
+        os.replace(tmp, 'data/stats_%06d.npz' % k)
+        with open(stats_path, 'a') as f:
+            f.write(','.join([str(k), repr(k * dt)] + [repr(float(summ[c])) for c in stats_mod.SUMMARY]) + '\n')
+
     diag_every = drv.diag_every
     stop_at_diag = bool(diag_every) and not drv.diag_in_advance
     diag_last = None
@@ -805,6 +865,10 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
             n = min(n, dye_save - i % dye_save)
         if frames_every:
             n = min(n, frames_every - i % frames_every)
+        if stats_every and i + stats_every - i % stats_every >= stats_from:
+            n = min(n, stats_every - i % stats_every)
+        if stats_save:
+            n = min(n, stats_save - i % stats_save)
         if args.steps:
             n = min(n, args.steps - i)
         return n
@@ -866,6 +930,12 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                 frames_mod.write_png('output/frame_%06d.png' % istep, rgb)
                 with open(frames_path, 'a') as f:
                     f.write('%d,%r,%r,%r,%d\n' % (istep, istep * dt, fs["LO"], fs["HI"], fs["NAN_PIXELS"]))
+            if stats_every:
+                if istep % stats_every == 0 and istep >= stats_from:
+                    eng.stats_sample()
+                if stats_save and istep % stats_save == 0:
+                    save_stats(istep)
+                    stats_saved_at = istep
             if args.save_every and istep % args.save_every == 0:
                 if dye_on:                                          # (beside the checkpoint, whose format stays as it is)
                     np.savez('data/dye_state.tmp.npz', C=drv.dye(), istep=np.int64(istep))
@@ -909,6 +979,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
                     plt.close()
     except KeyboardInterrupt:
         pass
+    if stats_every and stats_saved_at != eng.istep:
+        save_stats(eng.istep)                                       # the end of the run
     drv.close()
     return 0
 

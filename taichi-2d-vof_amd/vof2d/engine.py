@@ -405,6 +405,37 @@ class Engine:
                                       summ.ctypes.data_as(C.POINTER(C.c_double)) if due else None, due, C.byref(done)), "step_frames")
         return out[:done.value], [frames.summary_of(list(r)) for r in summ[:done.value]]
 
+    def stats_begin(self, mask=3, level=0.5):
+        """vof_stats_begin: allocates and clears the accumulator planes of the groups in `mask` (stats.MOMENTS | stats.ENVELOPE, or
+        a sequence of group names); a cell counts as wet in a sample if its clamped F is >= level.  mask 0 releases them."""
+        from . import stats
+        self._ck(self.api.stats_begin(self._h, stats.mask_of(mask), float(level)), "stats_begin")
+
+    def stats_sample(self):
+        """vof_stats_sample: one sample of the fields as they are into the planes (enqueues only)."""
+        self._ck(self.api.stats_sample(self._h), "stats_sample")
+
+    def stats_plane(self, slot):
+        """vof_stats_get: one plane (a slot number or a name of stats.PLANES) as an (nx, ny) float64 array indexed [i-1, j-1]."""
+        from . import stats
+        out = np.empty((self.nx, self.ny), dtype=np.float64)
+        self._ck(self.api.stats_get(self._h, stats.slot_of(slot), out.ctypes.data_as(C.POINTER(C.c_double)), out.size), "stats_get")
+        return out
+
+    def stats_summary(self):
+        """vof_stats_summary: the summary as a dict keyed by stats.SUMMARY."""
+        from . import stats
+        summ = (C.c_double * _abi.VOF_STATS_SUM_N)()
+        self._ck(self.api.stats_summary(self._h, summ), "stats_summary")
+        return stats.summary_of(list(summ))
+
+    def step_stats(self, nsteps, every, mg_cycles=0, criterion="rel"):
+        """vof_step_stats: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), a sample taken on the device behind every
+        `every` of them; nothing is read back.  Returns the number of samples taken."""
+        done = C.c_int64()
+        self._ck(self.api.step_stats(self._h, int(nsteps), int(every), int(mg_cycles), criterion_code(criterion), C.byref(done)), "step_stats")
+        return done.value
+
     def _sized_rows(self, cap_attr, first_cap, width, summ, count_slot, what, call):
         """The rows of a verb that fills at most `cap` of them and reports in summ[count_slot] how many there are:
         call(rows pointer, cap) with the capacity the last call needed (plus a margin), once more if the list has outgrown it."""

@@ -209,6 +209,27 @@ class VOF2D:
         """nsteps steps with such a picture rendered on the device every `every` steps (vof_step_frames): (pictures, summaries)."""
         return self.eng.step_frames(nsteps, every, quantity, bx, by, lo, hi, contour, symmetric, mg_cycles, criterion)
 
+    def stats_begin(self, mask=3, level=0.5):
+        """Start (or clear) per-cell statistics over the run: running sums of F, u, v and their products, envelopes, wet time and
+        arrival step (vof_stats_begin; mask 0 releases them; vof2d/stats.py: PLANES, derive)."""
+        self.eng.stats_begin(mask, level)
+
+    def stats_sample(self):
+        """One sample of the current state into the statistics (vof_stats_sample)."""
+        self.eng.stats_sample()
+
+    def stats_plane(self, slot):
+        """One accumulator plane as an (nx, ny) float64 array (vof_stats_get)."""
+        return self.eng.stats_plane(slot)
+
+    def stats_summary(self):
+        """The summary of the statistics as a dict (vof_stats_summary; vof2d/stats.py: SUMMARY)."""
+        return self.eng.stats_summary()
+
+    def step_stats(self, nsteps, every, mg_cycles=0, criterion="rel"):
+        """nsteps steps with a sample taken on the device every `every` steps (vof_step_stats): the samples taken."""
+        return self.eng.step_stats(nsteps, every, mg_cycles, criterion)
+
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)
