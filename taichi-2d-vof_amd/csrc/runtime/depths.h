@@ -138,9 +138,8 @@ int gauges_get(vof2d_ctx* h, double* rows, int64_t cap_rows, double* summary) {
   return VOF_OK;
 }
 
-// nsteps steps in groups of `every` (the `steps` choice of step_diag_n), a record of all gauges behind every group, one
-// read-back at the end.  The entry point has checked the arguments, that the handle is a full domain with gauges where a
-// record is due and that no phased step is in progress.
+// step_groups_n (runtime/step.h) with a record of all gauges behind every group, one read-back at the end.  (The entry point
+// has checked that the handle has gauges where a record is due.)
 int step_gauges_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, double* out, int64_t* records_written) {
   const int64_t records = nsteps / every;
   const size_t rec_bytes = (size_t)h->gauge_n * kGaugeRowBytes;
@@ -149,12 +148,8 @@ int step_gauges_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int c
     if ((rc = depths_prepare(h))) return rc;
     if ((rc = h->buf.gauge_recs.reserve(h, (size_t)records * rec_bytes, "vof_step_gauges: no memory for the records"))) return rc;
   }
-  auto steps = [&](int64_t n) { return cycles > 0 ? step_mg_n(h, n, cycles, criterion, nullptr, nullptr, nullptr) : step_n(h, n); };
-  for (int64_t r = 0; r < records; ++r) {
-    if ((rc = steps(every))) return rc;
-    if ((rc = gauges_record(h, h->buf.gauge_recs.as<double>((size_t)r * rec_bytes)))) return rc;
-  }
-  if (nsteps % every && (rc = steps(nsteps % every))) return rc;
+  if ((rc = step_groups_n(h, nsteps, every, cycles, criterion, [&](int64_t r) { return gauges_record(h, h->buf.gauge_recs.as<double>((size_t)r * rec_bytes)); })))
+    return rc;
   if (records > 0 && (rc = read_back(h, out, h->buf.gauge_recs.p, (size_t)records * rec_bytes))) return rc;
   h->gauge_records += records;
   if (records_written) *records_written = records;

@@ -47,18 +47,12 @@ int diag_enqueue(vof2d_ctx* h, int64_t slot) {
   return ensure_ok(h);
 }
 
-// nsteps steps in groups of `every`, a row behind every group, one read-back at the end.  The entry point has checked
-// the arguments, that the handle is a full domain and that no phased step is in progress.
+// step_groups_n (runtime/step.h) with a row behind every group, one read-back at the end
 int step_diag_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, double* out, int64_t* rows_written) {
   const int64_t rows = nsteps / every;
   int rc = diag_prepare(h, rows);
   if (rc) return rc;
-  auto steps = [&](int64_t n) { return cycles > 0 ? step_mg_n(h, n, cycles, criterion, nullptr, nullptr, nullptr) : step_n(h, n); };
-  for (int64_t r = 0; r < rows; ++r) {
-    if ((rc = steps(every))) return rc;
-    if ((rc = diag_enqueue(h, r))) return rc;
-  }
-  if (nsteps % every && (rc = steps(nsteps % every))) return rc;
+  if ((rc = step_groups_n(h, nsteps, every, cycles, criterion, [&](int64_t r) { return diag_enqueue(h, r); }))) return rc;
   if (rows > 0 && (rc = read_back(h, out, h->buf.diag_rows.p, (size_t)rows * DG_N * sizeof(double)))) return rc;
   if (rows_written) *rows_written = rows;
   return VOF_OK;

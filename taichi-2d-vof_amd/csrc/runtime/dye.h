@@ -107,19 +107,17 @@ int dye_stats_enqueue(vof2d_ctx* h, int64_t slot) {
   return ensure_ok(h);
 }
 
-// nsteps times: one step (the `steps` choice of step_diag_n, one at a time: the dye needs u, v of every step in memory, so no
-// batch graph), one advance of the dye; a row behind every `every`-th step (0: none), one read-back at the end.  The entry
-// point has checked the arguments, that the handle is a full domain with a dye and that no phased step is in progress.
+// step_groups_n (runtime/step.h) in groups of ONE step (the dye needs u, v of every step in memory, so no batch graph) with
+// one advance of the dye behind each, and a row behind every `every`-th step (0: none); one read-back at the end
 int step_dye_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, double* out, int64_t* rows_written) {
   const int64_t rows = every > 0 ? nsteps / every : 0;
   int rc;
   if (rows > 0 && (rc = dye_stats_prepare(h, rows))) return rc;
-  int64_t taken = 0;
-  for (int64_t s = 0; s < nsteps; ++s) {
-    if ((rc = cycles > 0 ? step_mg_n(h, 1, cycles, criterion, nullptr, nullptr, nullptr) : step_n(h, 1))) return rc;
-    if ((rc = dye_advance(h))) return rc;
-    if (every > 0 && (s + 1) % every == 0 && (rc = dye_stats_enqueue(h, taken++))) return rc;
-  }
+  rc = step_groups_n(h, nsteps, 1, cycles, criterion, [&](int64_t s) {
+    if (const int rc = dye_advance(h)) return rc;
+    return every > 0 && (s + 1) % every == 0 ? dye_stats_enqueue(h, (s + 1) / every - 1) : VOF_OK;
+  });
+  if (rc) return rc;
   if (rows > 0 && (rc = read_back(h, out, h->buf.dye_rows.p, (size_t)rows * DY_N * sizeof(double)))) return rc;
   if (rows_written) *rows_written = rows;
   return VOF_OK;

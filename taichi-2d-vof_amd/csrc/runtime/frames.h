@@ -129,10 +129,8 @@ int frame_run(vof2d_ctx* h, const vof2d_frame_spec& spec, uint8_t* rgb, double* 
   return VOF_OK;
 }
 
-// nsteps steps in groups of `every` (the `steps` choice of step_gauges_n), a frame behind every group -- its picture and its
-// summary written by k_frame_paint into slot r of buf.frame_recs (the pictures first, the summaries behind them) --, one
-// read-back each at the end.  The entry point has checked the arguments, that the handle is a whole domain (with a dye where
-// the quantity is the dye) and that no phased step is in progress.
+// step_groups_n (runtime/step.h) with a frame behind every group -- its picture and its summary written by k_frame_paint
+// into slot r of buf.frame_recs (the pictures first, the summaries behind them) --, one read-back each at the end
 int step_frames_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, const vof2d_frame_spec& spec, uint8_t* out_rgb, double* out_summaries,
                   int64_t* frames_written) {
   const int64_t frames = nsteps / every;
@@ -145,12 +143,10 @@ int step_frames_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int c
     if ((rc = frame_prepare(h, pl))) return rc;
     if ((rc = h->buf.frame_recs.reserve(h, recs.total, "vof_step_frames: no memory for the frames"))) return rc;
   }
-  auto steps = [&](int64_t n) { return cycles > 0 ? step_mg_n(h, n, cycles, criterion, nullptr, nullptr, nullptr) : step_n(h, n); };
-  for (int64_t r = 0; r < frames; ++r) {
-    if ((rc = steps(every))) return rc;
-    if ((rc = frame_enqueue(h, spec, pl, h->buf.frame_recs.as<unsigned char>(at_rgb + (size_t)r * rgb_bytes), h->buf.frame_recs.as<double>(at_sum) + r * FRS_N))) return rc;
-  }
-  if (nsteps % every && (rc = steps(nsteps % every))) return rc;
+  rc = step_groups_n(h, nsteps, every, cycles, criterion, [&](int64_t r) {
+    return frame_enqueue(h, spec, pl, h->buf.frame_recs.as<unsigned char>(at_rgb + (size_t)r * rgb_bytes), h->buf.frame_recs.as<double>(at_sum) + r * FRS_N);
+  });
+  if (rc) return rc;
   if (frames > 0) {
     HIPCHK(h, hipMemcpyAsync(out_rgb, h->buf.frame_recs.as<char>(at_rgb), (size_t)frames * rgb_bytes, hipMemcpyDeviceToHost, h->stream));
     if ((rc = read_back(h, out_summaries, h->buf.frame_recs.as<char>(at_sum), (size_t)frames * kFrameSumBytes))) return rc;

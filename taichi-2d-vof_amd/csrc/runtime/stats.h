@@ -117,18 +117,10 @@ int stats_summary(vof2d_ctx* h, double* out) {
   return VOF_OK;
 }
 
-// nsteps steps in groups of `every` (the `steps` choice of step_diag_n), a sample behind every group; nothing is read back.  The entry
-// point has checked the arguments, that the handle is a full domain with statistics and that no phased step is in progress.
+// step_groups_n (runtime/step.h) with a sample behind every group; nothing is read back
 int step_stats_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, int64_t* samples_taken) {
-  const int64_t samples = nsteps / every;
-  int rc;
-  auto steps = [&](int64_t n) { return cycles > 0 ? step_mg_n(h, n, cycles, criterion, nullptr, nullptr, nullptr) : step_n(h, n); };
-  for (int64_t r = 0; r < samples; ++r) {
-    if ((rc = steps(every))) return rc;
-    if ((rc = stats_sample(h))) return rc;
-  }
-  if (nsteps % every && (rc = steps(nsteps % every))) return rc;
-  if (samples_taken) *samples_taken = samples;
+  if (const int rc = step_groups_n(h, nsteps, every, cycles, criterion, [&](int64_t) { return stats_sample(h); })) return rc;
+  if (samples_taken) *samples_taken = nsteps / every;
   return VOF_OK;
 }
 

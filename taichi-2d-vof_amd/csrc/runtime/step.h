@@ -3,6 +3,7 @@
 //
 // Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
+#include "groups.h"
 #include "schedule.h"
 #include "multigrid.h"
 
@@ -287,6 +288,19 @@ int step_mg_n(vof2d_ctx* h, int64_t nsteps, int cycles, int criterion, double* l
   if (worst_residual) *worst_residual = rec[MGR_WORST];
   if (worst_step) *worst_step = rec[MGR_COUNT] > 0.0 ? istep0 + (int64_t)rec[MGR_WORST_AT] : 0;
   return VOF_OK;
+}
+
+// The steps of every vof_step_<verb> (their loop: step_groups, runtime/groups.h): those of vof_step_mg with `cycles` V-cycles and no
+// record read back where cycles > 0, else those of vof_step
+int step_n_or_mg(vof2d_ctx* h, int64_t nsteps, int cycles, int criterion) {
+  return cycles > 0 ? step_mg_n(h, nsteps, cycles, criterion, nullptr, nullptr, nullptr) : step_n(h, nsteps);
+}
+// ... nsteps of them in groups of `every` with after(r) behind group r, then the remainder: the loop of the six step_<verb>_n.
+// Reserving buffers before anything is enqueued, the read-backs at the end and the counters are each verb's own; its entry point
+// has checked the arguments, that the handle is a whole domain with what the verb works on and that no phased step is in progress.
+template <class After>
+int step_groups_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, After&& after) {
+  return step_groups(nsteps, every, [&](int64_t n) { return step_n_or_mg(h, n, cycles, criterion); }, after);
 }
 
 // One phase of a step (vof_step_phase: the caller has checked the order of the phases)

@@ -96,30 +96,27 @@ int tracers_get(vof2d_ctx* h, double* rows, int64_t cap_rows, double* summary) {
 // The snapshots a call of vof_step_tracers owes
 inline int64_t tracer_snaps_due(int64_t nsteps, int64_t every, int64_t snap_every) { return snap_every >= 1 ? (nsteps / every) / snap_every : 0; }
 
-// nsteps steps in groups of `every` (the `steps` choice of step_diag_n), an advance by every * dt behind every group, a
-// snapshot of all rows behind every snap_every-th advance, one read-back at the end.  The entry point has checked the
-// arguments, that the handle is a full domain and that no phased step is in progress.
+// step_groups_n (runtime/step.h) with an advance by every * dt behind every group and a snapshot of all rows behind every
+// snap_every-th advance, one read-back at the end
 int step_tracers_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, int64_t snap_every, double* snaps, int64_t* snaps_written) {
-  const int64_t groups = nsteps / every, due = tracer_snaps_due(nsteps, every, snap_every);
+  const int64_t due = tracer_snaps_due(nsteps, every, snap_every);
   const size_t snap_bytes = (size_t)h->tracer_n * kTracerRowBytes;
   int rc;
   if (due > 0 && snap_bytes > 0 && (rc = h->buf.tracer_snaps.reserve(h, (size_t)due * snap_bytes, "vof_step_tracers: no memory for the snapshots"))) return rc;
-  auto steps = [&](int64_t n) { return cycles > 0 ? step_mg_n(h, n, cycles, criterion, nullptr, nullptr, nullptr) : step_n(h, n); };
   const double span = (double)every * h->cd.dt;
   int64_t taken = 0;
-  for (int64_t r = 0; r < groups; ++r) {
-    if ((rc = steps(every))) return rc;
-    if ((rc = tracers_advance(h, span))) return rc;
-    if (snap_every >= 1 && (r + 1) % snap_every == 0) {
-      if (snap_bytes > 0) {
-        double* const slot = h->buf.tracer_snaps.as<double>((size_t)taken * snap_bytes);
-        DISPATCH_T(h, tracer_sample_launch<double>(h, slot, false), tracer_sample_launch<float>(h, slot, false));
-        if ((rc = ensure_ok(h))) return rc;
-      }
-      ++taken;
+  rc = step_groups_n(h, nsteps, every, cycles, criterion, [&](int64_t r) {
+    if (const int rc = tracers_advance(h, span)) return rc;
+    if (snap_every < 1 || (r + 1) % snap_every != 0) return VOF_OK;
+    if (snap_bytes > 0) {
+      double* const slot = h->buf.tracer_snaps.as<double>((size_t)taken * snap_bytes);
+      DISPATCH_T(h, tracer_sample_launch<double>(h, slot, false), tracer_sample_launch<float>(h, slot, false));
+      if (const int rc = ensure_ok(h)) return rc;
     }
-  }
-  if (nsteps % every && (rc = steps(nsteps % every))) return rc;
+    ++taken;
+    return VOF_OK;
+  });
+  if (rc) return rc;
   if (taken > 0 && snap_bytes > 0 && (rc = read_back(h, snaps, h->buf.tracer_snaps.p, (size_t)taken * snap_bytes))) return rc;
   if (snaps_written) *snaps_written = taken;
   return VOF_OK;

@@ -91,6 +91,29 @@ int check_whole_domain(vof2d_ctx* h, const char* why_not_a_strip) {   // (the me
 int check_no_phased_step(vof2d_ctx* h) {
   return phased_step_in_progress(h->state) ? fail(h, VOF_ESTATE, "a phased step (vof_step_phase) is in progress") : VOF_OK;
 }
+// ... of the verbs that need the whole domain in one handle and no phased step under way (the message names them and the reason);
+// lacks: the message where the handle lacks what the verb works on (a dye, statistics), else NULL
+int check_verb_allowed(vof2d_ctx* h, const char* why_not_a_strip, const char* lacks = nullptr) {
+  if (const int rc = check_whole_domain(h, why_not_a_strip)) return rc;
+  if (const int rc = check_no_phased_step(h)) return rc;
+  return lacks ? fail(h, VOF_ESTATE, lacks) : VOF_OK;
+}
+// What every vof_step_<verb> checks first, in this order: the handle, every (the verb's minimum and its message), nsteps, `between`
+// (the message of a failed check of the verb's own that stands here, else NULL), mg_cycles, the criterion where it is used
+int check_step_args(vof2d_ctx* h, int64_t nsteps, int64_t every, int mg_cycles, int criterion, const char* between = nullptr, int64_t min_every = 1,
+                    const char* every_msg = "every must be >= 1") {
+  if (!h) return VOF_EINVAL;
+  if (every < min_every) return fail(h, VOF_EINVAL, every_msg);
+  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
+  if (between) return fail(h, VOF_EINVAL, between);
+  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
+  return mg_cycles >= 1 ? check_criterion(h, criterion) : VOF_OK;
+}
+// ... and last: a call of no steps does nothing but report that it recorded nothing
+bool no_steps(int64_t nsteps, int64_t* written) {
+  if (nsteps == 0 && written) *written = 0;
+  return nsteps == 0;
+}
 bool full_domain(const vof2d_ctx* h) { return h->g.wall_lo && h->g.wall_hi; }
 
 }  // namespace
@@ -425,19 +448,12 @@ int vof_diagnostics(vof2d_handle h, double* out) {
 }
 int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
                   int64_t* rows_written) {
-  if (!h) return VOF_EINVAL;
-  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
-  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
-  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (const int rc = check_step_args(h, nsteps, every, mg_cycles, criterion)) return rc;
   if (cap_rows < nsteps / every) return fail(h, VOF_EINVAL, "cap_rows is smaller than nsteps / every");
   if (!out && nsteps / every > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one row is due");
   if (const int rc = check_whole_domain(h, "vof_step_diag needs the whole domain in one handle (a strip's steps need their exchanges: call vof_diagnostics between them)")) return rc;
   if (const int rc = check_no_phased_step(h)) return rc;
-  if (nsteps == 0) {
-    if (rows_written) *rows_written = 0;
-    return VOF_OK;
-  }
+  if (no_steps(nsteps, rows_written)) return VOF_OK;
   return step_diag_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
 }
 
@@ -463,10 +479,7 @@ int vof_blobs(vof2d_handle h, int32_t phase, double threshold, double* rows, int
 
 // ---- passive tracers moved with the flow (kernels/tracers.h, runtime/tracers.h)
 namespace {
-int check_tracers_allowed(vof2d_ctx* h) {
-  if (const int rc = check_whole_domain(h, "the vof_tracers_* verbs and vof_step_tracers need the whole domain in one handle (a tracer would leave a strip's rows)")) return rc;
-  return check_no_phased_step(h);
-}
+int check_tracers_allowed(vof2d_ctx* h) { return check_verb_allowed(h, "the vof_tracers_* verbs and vof_step_tracers need the whole domain in one handle (a tracer would leave a strip's rows)"); }
 }  // namespace
 int vof_tracers_set(vof2d_handle h, const double* xy, int64_t n) {
   if (!h) return VOF_EINVAL;
@@ -490,20 +503,12 @@ int vof_tracers_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summ
 }
 int vof_step_tracers(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, int64_t snap_every, double* snaps,
                      int64_t cap_snaps, int64_t* snaps_written) {
-  if (!h) return VOF_EINVAL;
-  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
-  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (snap_every < 0) return fail(h, VOF_EINVAL, "snap_every must be >= 0 (0: no snapshots)");
-  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
-  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (const int rc = check_step_args(h, nsteps, every, mg_cycles, criterion, snap_every < 0 ? "snap_every must be >= 0 (0: no snapshots)" : nullptr)) return rc;
   const int64_t due = tracer_snaps_due(nsteps, every, snap_every);
   if (cap_snaps < due) return fail(h, VOF_EINVAL, "cap_snaps is smaller than the snapshots due, (nsteps / every) / snap_every");
   if (!snaps && due > 0) return fail(h, VOF_EINVAL, "snaps is NULL and at least one snapshot is due");
   if (const int rc = check_tracers_allowed(h)) return rc;
-  if (nsteps == 0) {
-    if (snaps_written) *snaps_written = 0;
-    return VOF_OK;
-  }
+  if (no_steps(nsteps, snaps_written)) return VOF_OK;
   return step_tracers_n(h, nsteps, every, mg_cycles, criterion, snap_every, snaps, snaps_written);
 }
 
@@ -518,10 +523,7 @@ int vof_depths(vof2d_handle h, double* depth_i, int64_t cap_i, double* depth_j, 
   return depths_run(h, depth_i, depth_j, top, summary);
 }
 namespace {
-int check_gauges_allowed(vof2d_ctx* h) {
-  if (const int rc = check_whole_domain(h, "the vof_gauges_* verbs and vof_step_gauges need the whole domain in one handle (a gauge may lie outside a strip's rows: call vof_depths on the strips)")) return rc;
-  return check_no_phased_step(h);
-}
+int check_gauges_allowed(vof2d_ctx* h) { return check_verb_allowed(h, "the vof_gauges_* verbs and vof_step_gauges need the whole domain in one handle (a gauge may lie outside a strip's rows: call vof_depths on the strips)"); }
 }  // namespace
 int vof_gauges_set(vof2d_handle h, const double* xy, int64_t n) {
   if (!h) return VOF_EINVAL;
@@ -539,28 +541,19 @@ int vof_gauges_get(vof2d_handle h, double* rows, int64_t cap_rows, double* summa
 }
 int vof_step_gauges(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_records,
                     int64_t* records_written) {
-  if (!h) return VOF_EINVAL;
-  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
-  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
-  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (const int rc = check_step_args(h, nsteps, every, mg_cycles, criterion)) return rc;
   if (cap_records < nsteps / every) return fail(h, VOF_EINVAL, "cap_records is smaller than nsteps / every");
   if (!out && nsteps / every > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one record is due");
   if (const int rc = check_gauges_allowed(h)) return rc;
   if (h->gauge_n == 0 && nsteps / every > 0) return fail(h, VOF_EINVAL, "the handle has no gauges and at least one record is due");
-  if (nsteps == 0) {
-    if (records_written) *records_written = 0;
-    return VOF_OK;
-  }
+  if (no_steps(nsteps, records_written)) return VOF_OK;
   return step_gauges_n(h, nsteps, every, mg_cycles, criterion, out, records_written);
 }
 
 // ---- a marker field carried by the FCT transport (kernels/dye.h, runtime/dye.h)
 namespace {
 int check_dye_allowed(vof2d_ctx* h, bool needs_dye) {
-  if (const int rc = check_whole_domain(h, "the vof_dye_* verbs and vof_step_dye need the whole domain in one handle (a strip's sweeps need their exchanges)")) return rc;
-  if (const int rc = check_no_phased_step(h)) return rc;
-  return needs_dye && !h->dye_on ? fail(h, VOF_ESTATE, "the handle has no dye (vof_dye_set)") : VOF_OK;
+  return check_verb_allowed(h, "the vof_dye_* verbs and vof_step_dye need the whole domain in one handle (a strip's sweeps need their exchanges)", needs_dye && !h->dye_on ? "the handle has no dye (vof_dye_set)" : nullptr);
 }
 }  // namespace
 int vof_dye_set(vof2d_handle h, const void* src, size_t nbytes) {
@@ -590,28 +583,18 @@ int vof_dye_stats(vof2d_handle h, double* out) {
 }
 int vof_step_dye(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
                  int64_t* rows_written) {
-  if (!h) return VOF_EINVAL;
-  if (every < 0) return fail(h, VOF_EINVAL, "every must be >= 0 (0: no rows)");
-  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
-  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (const int rc = check_step_args(h, nsteps, every, mg_cycles, criterion, nullptr, 0, "every must be >= 0 (0: no rows)")) return rc;
   const int64_t due = every > 0 ? nsteps / every : 0;
   if (cap_rows < due) return fail(h, VOF_EINVAL, "cap_rows is smaller than nsteps / every");
   if (!out && due > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one row is due");
   if (const int rc = check_dye_allowed(h, true)) return rc;
-  if (nsteps == 0) {
-    if (rows_written) *rows_written = 0;
-    return VOF_OK;
-  }
+  if (no_steps(nsteps, rows_written)) return VOF_OK;
   return step_dye_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
 }
 
 // ---- colour-mapped pictures rendered on the device (kernels/frames.h, runtime/frames.h)
 namespace {
-int check_frames_allowed(vof2d_ctx* h) {
-  if (const int rc = check_whole_domain(h, "vof_frame_set_lut, vof_frame and vof_step_frames need the whole domain in one handle (frames over row strips are not built)")) return rc;
-  return check_no_phased_step(h);
-}
+int check_frames_allowed(vof2d_ctx* h) { return check_verb_allowed(h, "vof_frame_set_lut, vof_frame and vof_step_frames need the whole domain in one handle (frames over row strips are not built)"); }
 // 0, or VOF_EINVAL with the message set: the spec alone (pixels: pw * ph of it)
 int check_frame_spec(vof2d_ctx* h, const vof2d_frame_spec* spec, int64_t* pixels) {
   if (!spec) return fail(h, VOF_EINVAL, "spec is NULL");
@@ -642,30 +625,21 @@ int vof_frame(vof2d_handle h, const vof2d_frame_spec* spec, uint8_t* rgb, int64_
 }
 int vof_step_frames(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, const vof2d_frame_spec* spec, uint8_t* out_rgb,
                     double* out_summaries, int64_t cap_frames, int64_t* frames_written) {
-  if (!h) return VOF_EINVAL;
-  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
-  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
-  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (const int rc = check_step_args(h, nsteps, every, mg_cycles, criterion)) return rc;
   int64_t pixels = 0;
   if (const int rc = check_frame_spec(h, spec, &pixels)) return rc;
   if (cap_frames < nsteps / every) return fail(h, VOF_EINVAL, "cap_frames is smaller than nsteps / every");
   if ((!out_rgb || !out_summaries) && nsteps / every > 0) return fail(h, VOF_EINVAL, "out_rgb or out_summaries is NULL and at least one frame is due");
   if (const int rc = check_frames_allowed(h)) return rc;
   if (spec->quantity == FQ_DYE && !h->dye_on) return fail(h, VOF_ESTATE, "the handle has no dye (vof_dye_set)");
-  if (nsteps == 0) {
-    if (frames_written) *frames_written = 0;
-    return VOF_OK;
-  }
+  if (no_steps(nsteps, frames_written)) return VOF_OK;
   return step_frames_n(h, nsteps, every, mg_cycles, criterion, *spec, out_rgb, out_summaries, frames_written);
 }
 
 // ---- per-cell statistics over a run (kernels/stats.h, runtime/stats.h)
 namespace {
 int check_stats_allowed(vof2d_ctx* h, bool needs_stats) {
-  if (const int rc = check_whole_domain(h, "the vof_stats_* verbs and vof_step_stats need the whole domain in one handle (statistics over row strips are not built)")) return rc;
-  if (const int rc = check_no_phased_step(h)) return rc;
-  return needs_stats && !h->stats_mask ? fail(h, VOF_ESTATE, "the handle has no statistics (vof_stats_begin)") : VOF_OK;
+  return check_verb_allowed(h, "the vof_stats_* verbs and vof_step_stats need the whole domain in one handle (statistics over row strips are not built)", needs_stats && !h->stats_mask ? "the handle has no statistics (vof_stats_begin)" : nullptr);
 }
 }  // namespace
 int vof_stats_begin(vof2d_handle h, int32_t mask, double level) {
@@ -694,16 +668,9 @@ int vof_stats_summary(vof2d_handle h, double* out) {
   return stats_summary(h, out);
 }
 int vof_step_stats(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, int64_t* samples_taken) {
-  if (!h) return VOF_EINVAL;
-  if (every < 1) return fail(h, VOF_EINVAL, "every must be >= 1");
-  if (nsteps < 0) return fail(h, VOF_EINVAL, "nsteps must be >= 0");
-  if (mg_cycles < 0) return fail(h, VOF_EINVAL, "mg_cycles must be >= 0 (0: the steps of vof_step)");
-  if (mg_cycles >= 1 && check_criterion(h, criterion)) return VOF_EINVAL;
+  if (const int rc = check_step_args(h, nsteps, every, mg_cycles, criterion)) return rc;
   if (const int rc = check_stats_allowed(h, true)) return rc;
-  if (nsteps == 0) {
-    if (samples_taken) *samples_taken = 0;
-    return VOF_OK;
-  }
+  if (no_steps(nsteps, samples_taken)) return VOF_OK;
   return step_stats_n(h, nsteps, every, mg_cycles, criterion, samples_taken);
 }
 

@@ -11,6 +11,7 @@ and a torch.distributed (gloo) carrier to exercise the multi-rank host logic wit
 import argparse
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -189,12 +190,11 @@ def parse_args(argv=None):
     """build_parser().parse_args plus the combinations argparse cannot express."""
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.diag_every is not None and args.diag_every < 1:
-        parser.error("--diag-every needs N >= 1")
-    if args.interface_every is not None and args.interface_every < 1:
-        parser.error("--interface-every needs N >= 1")
-    if args.blobs_every is not None and args.blobs_every < 1:
-        parser.error("--blobs-every needs N >= 1")
+    def at_least_1(*options):                        # (in this order: the first refusal is the one reported)
+        for opt in options:
+            if getattr(args, opt + "_every") is not None and getattr(args, opt + "_every") < 1:
+                parser.error("--%s-every needs N >= 1" % opt)
+    at_least_1("diag", "interface", "blobs")
     if not 0.0 < args.blobs_threshold < 1.0:
         parser.error("--blobs-threshold needs 0 < T < 1")
     if args.tracers < 0:
@@ -207,17 +207,13 @@ def parse_args(argv=None):
         parser.error("--tracers-save-every writes the tracers of --tracers N: pass that too")
     if args.tracers and args.gpus > 1:
         parser.error("--tracers runs on one GPU (a tracer would leave a strip's rows): drop --gpus")
-    if args.gauges_every is not None and args.gauges_every < 1:
-        parser.error("--gauges-every needs N >= 1")
-    if args.depths_every is not None and args.depths_every < 1:
-        parser.error("--depths-every needs N >= 1")
+    at_least_1("gauges", "depths")
     if (args.gauge or args.gauges_file or args.gauges_every is not None) and args.gpus > 1:
         parser.error("--gauge, --gauges-file and --gauges-every run on one GPU (a gauge reads rows a strip may not hold): drop --gpus, "
                      "or use --depths-every, which works on strips")
     if args.gauges_every is not None and not (args.gauge or args.gauges_file or args.resume):
         parser.error("--gauges-every records the gauges of --gauge X,Y / --gauges-file FILE: pass at least one")
-    if args.dye_every is not None and args.dye_every < 1:
-        parser.error("--dye-every needs N >= 1")
+    at_least_1("dye")
     if args.dye_save_every is not None and args.dye_save_every < 1:
         parser.error("--dye-save-every needs M >= 1")
     if args.dye_box and args.dye_file:
@@ -362,69 +358,14 @@ class _Single:
         self.dye_every = getattr(args, "dye_every", None) or 0
         self.dye_rows = []                           # raw rows not yet written
 
-    def set_dye(self, C):
-        self.eng.dye_set(C)
-        self.dye_on = True
-
-    def dye(self):
-        return self.eng.dye_get()
-
-    def take_dye(self):
-        rows, self.dye_rows = self.dye_rows, []
-        return rows
-
-    def _advance_dye(self, n):
-        """n steps of vof_step_dye with a row at every multiple of N: no rows up to the first multiple (a resumed run may start
-        anywhere), then one call for the rest."""
-        from . import dye
-        N, K, crit = self.dye_every, getattr(self.args, "mg_cycles", 0), self.args.jacobi_crit
-        head = min(n, -self.sim.istep % N) if N else n
-        if head:
-            self.sim.step_dye(head, 0, K, crit)
-            if N and self.sim.istep % N == 0:
-                self.dye_rows.append(self.eng.dye_stats())
-        if n - head:
-            self.dye_rows += [dye.raw_of(r) for r in self.sim.step_dye(n - head, N, K, crit)]
-
-    def set_gauges(self, xy):
-        self.eng.gauges_set(xy)
-
-    def save_gauges(self, path, istep):
-        rows, _ = self.eng.gauges_get()
-        tmp = path + ".tmp.npz"
-        np.savez(tmp, xy=rows[:, :2], istep=np.int64(istep))
-        os.replace(tmp, path)
-
     def record_gauges(self):
         self.gauge_recs.append((self.sim.istep, self.eng.gauges_get()[0]))
-
-    def take_gauges(self):
-        recs, self.gauge_recs = self.gauge_recs, []
-        return recs
 
     def depths(self):
         return self.eng.depths()
 
-    def _advance_gauges(self, n):
-        """n fused steps with a record at every multiple of N: plain steps up to the first multiple (a resumed run may start
-        anywhere), then one vof_step_gauges for the rest."""
-        N = self.gauges_every
-        head = min(n, -self.sim.istep % N)
-        if head:
-            self.sim.step(head)
-            if self.sim.istep % N == 0:
-                self.record_gauges()
-        if n - head:
-            first = self.sim.istep
-            recs = self.sim.step_gauges(n - head, N)
-            self.gauge_recs += [(first + (r + 1) * N, rows) for r, rows in enumerate(recs)]
-
     def init(self, ic):
         self.sim.set_init_F(ic)
-
-    def seed_tracers(self):
-        from . import tracers
-        return len(tracers.seed(self.eng, self.args.tracers, self.args.tracers_phase))
 
     def tracer_rows(self):
         """(rows, summary) with TIME and the counts continued over a resume."""
@@ -481,6 +422,7 @@ class _Single:
 
     def _advance(self, n):
         a, sim = self.args, self.sim
+        K, crit = getattr(a, "mg_cycles", 0), a.jacobi_crit
         if a.jacobi_tol > 0.0:
             for _ in range(n):   # main loop :513-528 with the residual-terminated solve (extension)
                 sim.istep = sim.istep + 1
@@ -494,12 +436,24 @@ class _Single:
                 sim.update_uv(); sim.set_BC()
                 sim.solve_VOF_rudman(sim.istep); sim.post_process_f(); sim.set_BC()
         elif self.dye_on:
-            self._advance_dye(n)
+            from . import dye
+            N = self.dye_every
+            self._advance_recording(n, N, lambda m: sim.step_dye(m, 0, K, crit), lambda: self.dye_rows.append(self.eng.dye_stats()),
+                                    lambda m: self.dye_rows.extend(dye.raw_of(r) for r in sim.step_dye(m, N, K, crit)))
         elif self.diag_in_advance:
-            self._advance_diag(n)
+            # (with --mg-cycles the rows of vof_step_diag replace the residual record of vof_step_mg: the status line reports div_max)
+            from . import diag
+            N = self.diag_every
+            self._advance_recording(n, N, self._step_mg if K > 0 else sim.step, self.record_diag,
+                                    lambda m: self.diag_rows.extend(diag.raw_of(r) for r in sim.step_diag(m, N, K, crit)))
         elif self.gauges_in_advance:
-            self._advance_gauges(n)
-        elif getattr(a, "mg_cycles", 0) > 0:
+            N = self.gauges_every
+
+            def rest(m):                             # (record r of the call belongs to step first + (r + 1) N)
+                first = sim.istep
+                self.gauge_recs += [(first + (r + 1) * N, rows) for r, rows in enumerate(sim.step_gauges(m, N))]
+            self._advance_recording(n, N, sim.step, self.record_gauges, rest)
+        elif K > 0:
             self._step_mg(n)
         elif a.verbs:
             sim.step_verbs(n)
@@ -511,20 +465,16 @@ class _Single:
         if not worst <= self.mg_worst[0]:
             self.mg_worst = (worst, at)
 
-    def _advance_diag(self, n):
-        """n fused steps with a row at every multiple of N: plain steps up to the first multiple (a resumed run may start
-        anywhere), then one vof_step_diag for the rest."""
-        from . import diag
-        N, K = self.diag_every, getattr(self.args, "mg_cycles", 0)
-        head = min(n, -self.sim.istep % N)
+    def _advance_recording(self, n, N, plain, ask, rest):
+        """n steps with a record at every multiple of N: plain(head) for the steps up to the first multiple (a resumed run may start
+        anywhere) and ask() once there, then rest(n - head), one device call that records on the device.  N = 0: plain steps alone."""
+        head = min(n, -self.sim.istep % N) if N else n
         if head:
-            self._step_mg(head) if K > 0 else self.sim.step(head)
-            if self.sim.istep % N == 0:
-                self.diag_rows.append(self.eng.diagnostics())
+            plain(head)
+            if N and self.sim.istep % N == 0:
+                ask()
         if n - head:
-            # (with --mg-cycles the rows replace the residual record of vof_step_mg: the status line reports div_max)
-            rows = self.sim.step_diag(n - head, N, K, self.args.jacobi_crit)
-            self.diag_rows += [diag.raw_of(r) for r in rows]
+            rest(n - head)
 
     def record_diag(self):
         self.diag_rows.append(self.eng.diagnostics())
@@ -534,10 +484,6 @@ class _Single:
 
     def blobs(self):
         return self.eng.blobs(self.args.blobs_phase, self.args.blobs_threshold)
-
-    def take_diag(self):
-        rows, self.diag_rows = self.diag_rows, []
-        return rows
 
     def report(self):
         """What the status line adds for this run ('' for most), and a fresh start of whatever it accumulates."""
@@ -611,10 +557,6 @@ class _Strips:
     def blobs(self):
         return self.s.blobs(self.args.blobs_phase, self.args.blobs_threshold)   # (collective, likewise)
 
-    def take_diag(self):
-        rows, self.diag_rows = self.diag_rows, []
-        return rows
-
     def report(self):
         return ''
 
@@ -666,7 +608,6 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
     rho_l, rho_g = eng.get_param("rho_l"), eng.get_param("rho_g")
     nu_l, nu_g = eng.get_param("nu_l"), eng.get_param("nu_g")
     gy, sigma = eng.get_param("gy"), eng.get_param("sigma")
-    Lx, Ly = eng.get_param("Lx"), eng.get_param("Ly")
     lead = rank == 0
 
     if lead:
@@ -676,7 +617,6 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         say(f'>>> Viscosity ratio: {nu_l / nu_g : 4.2f}')
 
     istep = 0
-    nstep = 100  # Interval to update output                       (2dvof.py:497)
     drv.init(args.ic)
     if lead:
         os.makedirs('output', exist_ok=True)  # Make dir for output                 (:500)
@@ -688,299 +628,24 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         if lead:
             say(f'>>> Resumed from {args.resume} at step {istep}.')
 
-    # passive tracers (vof_tracers_*): seeded from the initial F, or restored beside the checkpoint
-    tracers_on = bool(getattr(args, "tracers", 0)) and world == 1
-    tr_save = (getattr(args, "tracers_save_every", None) or 0) if tracers_on else 0
-    tr_path = 'data/tracers.csv'
-    if tracers_on:
-        from . import tracers as tracers_mod
-        state = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'tracers_state.npz') if args.resume else None
-        if state and drv.load_tracers(state, istep):
-            say(f'>>> Tracers restored from {state}.')
-        else:
-            say(f'>>> {drv.seed_tracers()} tracers seeded ({args.tracers_phase}).')
-        if tr_save and not (args.resume and os.path.exists(tr_path) and os.path.getsize(tr_path) > 0):
-            with open(tr_path, 'w') as f:
-                f.write(tracers_mod.CSV_HEADER + '\n')
-
-    # fixed sensors (vof_gauges_*): from the command line, or the set beside the checkpoint
-    gauges_every = (getattr(args, "gauges_every", None) or 0) if world == 1 else 0
-    gauges_on, gauges_path = False, 'data/gauges.csv'
-    if world == 1 and (getattr(args, "gauge", None) or getattr(args, "gauges_file", None) or gauges_every):
-        from . import gauges as gauges_mod
-        xy = gauges_mod.parse_positions(args.gauge, args.gauges_file)
-        state = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'gauges_state.npz') if args.resume else None
-        if not len(xy) and state and os.path.exists(state):
-            xy = np.load(state, allow_pickle=False)["xy"]
-            say(f'>>> Gauges restored from {state}.')
-        if not len(xy):
-            raise SystemExit("--gauges-every: no gauges given and none beside the checkpoint (--gauge X,Y, --gauges-file FILE)")
-        drv.set_gauges(xy)
-        gauges_on = True
-        say(f'>>> {len(xy)} gauges set.')
-        if gauges_every and not (args.resume and os.path.exists(gauges_path) and os.path.getsize(gauges_path) > 0):
-            with open(gauges_path, 'w') as f:
-                f.write(gauges_mod.GAUGES_CSV_HEADER + '\n')
-    stop_at_gauges = bool(gauges_every) and not drv.gauges_in_advance
-
-    # a dye (vof_dye_*): seeded from F inside the boxes, read from a file, or restored beside the checkpoint
-    dye_every = getattr(args, "dye_every", None) or 0
-    dye_save = getattr(args, "dye_save_every", None) or 0
-    dye_on, dye_path = False, 'data/dye.csv'
-    if getattr(args, "dye_box", None) or getattr(args, "dye_file", None) or dye_every or dye_save:
-        from . import dye as dye_mod
-        if dye_conflicts(args) or world > 1:
-            raise SystemExit(dye_conflicts(args) or "the dye options run on one GPU (drop --gpus)")
-        if not hasattr(api, "step_dye"):
-            raise SystemExit("the dye options need the dye verbs of the HIP library (vof_dye_*, vof_step_dye): this backend has none")
-        state = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'dye_state.npz') if args.resume else None
-        # (a resumed run continues the dye it saved, whatever boxes the command line repeats: they describe step 0)
-        if state and os.path.exists(state) and int(np.load(state, allow_pickle=False)["istep"]) == istep:
-            C = np.load(state, allow_pickle=False)["C"]
-            say(f'>>> Dye restored from {state}.')
-        elif args.dye_file:
-            C = np.load(args.dye_file, allow_pickle=False)
-            if C.shape != (nx + 2, ny + 2):
-                raise SystemExit("--dye-file: %s holds an array of shape %s, the dye is (nx+2, ny+2) = %s" % (args.dye_file, C.shape, (nx + 2, ny + 2)))
-        elif args.dye_box:
-            C = dye_mod.boxes(drv.full("F"), eng.get_param("dx"), eng.get_param("dy"), parse_dye_boxes(args.dye_box))
-        else:
-            raise SystemExit("--dye-every / --dye-save-every: no dye given and none of this step beside the checkpoint (--dye-box X0,X1,Y0,Y1, --dye-file FILE.npy)")
-        drv.set_dye(C)
-        dye_on = True
-        say(f'>>> Dye set: {float(np.asarray(C, dtype=np.float64)[1:-1, 1:-1].sum()) * eng.get_param("dx") * eng.get_param("dy"):.6e} m^2.')
-        if dye_every and not (args.resume and os.path.exists(dye_path) and os.path.getsize(dye_path) > 0):
-            with open(dye_path, 'w') as f:
-                f.write(','.join(('istep', 'time') + dye_mod.DERIVED) + '\n')
-
-    # the free-surface profile (vof_depths) is read between calls, like the interface
-    depths_every = getattr(args, "depths_every", None) or 0
-    depths_path = 'data/depths.csv'
-    if depths_every:
-        from . import gauges as gauges_mod
-        if lead and not (args.resume and os.path.exists(depths_path) and os.path.getsize(depths_path) > 0):
-            with open(depths_path, 'w') as f:
-                f.write(gauges_mod.DEPTHS_CSV_HEADER + '\n')
-
-    # pictures rendered on the device (vof_frame) are taken between calls too: three bytes a pixel leave the device
-    frames_every = (getattr(args, "frames_every", None) or 0) if world == 1 else 0
-    frames_path = 'data/frames.csv'
-    if frames_every:
-        from . import frames as frames_mod
-        if not hasattr(api, "frame"):
-            raise SystemExit("--frames-every needs the frame verbs of the HIP library (vof_frame): this backend has none")
-        fq, flo, fhi = parse_frame(args.frame)
-        block = args.frame_block or frames_mod.default_block(nx, ny)
-        cmap = args.frame_cmap or frames_mod.DEFAULT_CMAP[fq]
-        eng.set_frame_lut(None if cmap in ("grey", "gray") else frames_mod.lut(cmap))
-        frame_kw = dict(quantity=fq, bx=block, by=block, lo=flo, hi=fhi, contour=bool(args.frame_contour), symmetric=flo == fhi and fq in frames_mod.SIGNED)
-        os.makedirs('output', exist_ok=True)
-        if not (args.resume and os.path.exists(frames_path) and os.path.getsize(frames_path) > 0):
-            with open(frames_path, 'w') as f:
-                f.write('istep,time,lo,hi,nan_pixels\n')
-
-    # per-cell statistics over the run (vof_stats_*): a sample only enqueues, so it is taken between the calls of whatever loop steps
-    stats_every = (getattr(args, "stats_every", None) or 0) if world == 1 else 0
-    stats_save = getattr(args, "stats_save_every", None) or 0
-    stats_from = getattr(args, "stats_from", 0)
-    stats_path, stats_saved_at = 'data/stats.csv', -1
-    if stats_every:
-        from . import stats as stats_mod
-        if not hasattr(api, "stats_sample"):
-            raise SystemExit("--stats-every needs the statistics verbs of the HIP library (vof_stats_*): this backend has none")
-        stats_mask = stats_mod.mask_of(args.stats)
-        eng.stats_begin(stats_mask, args.stats_level)
-        say(f'>>> Statistics begun: {", ".join(g for g, b in stats_mod.GROUPS.items() if stats_mask & b)}, a sample every {stats_every} steps'
-            + (f' from step {stats_from} on' if stats_from else '') + (' (they start anew: not part of a checkpoint).' if args.resume else '.'))
-        if not (args.resume and os.path.exists(stats_path) and os.path.getsize(stats_path) > 0):
-            with open(stats_path, 'w') as f:
-                f.write(','.join(('istep', 'time') + tuple(k.lower() for k in stats_mod.SUMMARY)) + '\n')
-
-    def save_stats(k):
-        """data/stats_NNNNNN.npz: the raw planes, N and the derived arrays; a line of the summary to data/stats.csv."""
-        summ = eng.stats_summary()
-        planes = {p: eng.stats_plane(p) for p in stats_mod.planes_of(stats_mask)}
-        tmp = 'data/stats_%06d.tmp.npz' % k
-        np.savez(tmp, N=np.int64(summ["SAMPLES"]), istep=np.int64(k), mask=np.int64(stats_mask), level=np.float64(args.stats_level), **planes,
-                 **stats_mod.derive(planes, summ["SAMPLES"], dt))
-        os.replace(tmp, 'data/stats_%06d.npz' % k)
-        with open(stats_path, 'a') as f:
-            f.write(','.join([str(k), repr(k * dt)] + [repr(float(summ[c])) for c in stats_mod.SUMMARY]) + '\n')
-
-    diag_every = drv.diag_every
-    stop_at_diag = bool(diag_every) and not drv.diag_in_advance
-    diag_last = None
-    if diag_every and lead:
-        from . import diag
-        dx, dy = eng.get_param("dx"), eng.get_param("dy")
-        diag_path = 'data/diagnostics.csv'
-        if not (args.resume and os.path.exists(diag_path) and os.path.getsize(diag_path) > 0):
-            with open(diag_path, 'w') as f:      # the header once; a resumed run appends to what is there
-                f.write(','.join(('istep', 'time') + diag.DERIVED) + '\n')
-
-    # the interface is read between calls (vof_interface records nothing in advance): every step loop is cut at the multiples of N
-    iface_every = getattr(args, "interface_every", None) or 0
-    iface_last = None
-    iface_path = 'data/interface.csv'
-    if iface_every and lead and not (args.resume and os.path.exists(iface_path) and os.path.getsize(iface_path) > 0):
-        with open(iface_path, 'w') as f:
-            f.write('istep,segments,degenerate,length\n')
-
-    def write_diag(rows):
-        """Append the rows (raw dicts) to data/diagnostics.csv; returns the derived values of the last one."""
-        last = None
-        with open(diag_path, 'a') as f:
-            for raw in rows:
-                last = diag.derive(raw, dx, dy, dt, nx, ny)
-                k = int(raw["ISTEP"])
-                f.write(','.join([str(k), repr(k * dt)] + [repr(float(last[c])) for c in diag.DERIVED]) + '\n')
-        return last
-
-    # ... and so are the blobs (vof_blobs)
-    blobs_every = getattr(args, "blobs_every", None) or 0
-    blobs_path = 'data/blobs.csv'
-    if blobs_every and lead:
-        from . import blobs as blobs_mod
-        if not (args.resume and os.path.exists(blobs_path) and os.path.getsize(blobs_path) > 0):
-            with open(blobs_path, 'w') as f:
-                f.write(blobs_mod.CSV_HEADER + '\n')
-
-    def next_stop(i):
-        n = nstep - i % nstep
-        if stop_at_diag:
-            n = min(n, diag_every - i % diag_every)
-        if iface_every:
-            n = min(n, iface_every - i % iface_every)
-        if blobs_every:
-            n = min(n, blobs_every - i % blobs_every)
-        if args.save_every:
-            n = min(n, args.save_every - i % args.save_every)
-        if tr_save:
-            n = min(n, tr_save - i % tr_save)
-        if stop_at_gauges:
-            n = min(n, gauges_every - i % gauges_every)
-        if depths_every:
-            n = min(n, depths_every - i % depths_every)
-        if dye_save:
-            n = min(n, dye_save - i % dye_save)
-        if frames_every:
-            n = min(n, frames_every - i % frames_every)
-        if stats_every and i + stats_every - i % stats_every >= stats_from:
-            n = min(n, stats_every - i % stats_every)
-        if stats_save:
-            n = min(n, stats_save - i % stats_save)
-        if args.steps:
-            n = min(n, args.steps - i)
-        return n
-
+    # every recording option is one recorder (vof2d/recorders.py); the loop steps to the nearest stop any of them asks for
+    from . import recorders
+    recs = recorders.recorders_of(args, drv, world)
+    ctx = SimpleNamespace(args=args, api=api, drv=drv, eng=eng, world=world, lead=lead, say=say, istep=istep, nx=nx, ny=ny, dt=dt,
+                          dx=eng.get_param("dx"), dy=eng.get_param("dy"), numerics=numerics, recorders=recs, diag_last=None, iface_last=None)
+    for r in recs:
+        r.setup(ctx)
     try:
         while args.steps == 0 or istep < args.steps:
-            n = next_stop(istep)
+            n = recorders.next_stop(recs, istep, args.steps)
             drv.advance(n)
             istep += n
-            if diag_every:
-                if stop_at_diag and istep % diag_every == 0:
-                    drv.record_diag()
-                rows = drv.take_diag()
-                if lead and rows:
-                    diag_last = write_diag(rows)
-            if iface_every and istep % iface_every == 0:
-                iface_last = drv.interface()
-                if lead:
-                    seg, summ = iface_last
-                    np.save('data/interface_%06d.npy' % istep, seg)
-                    with open(iface_path, 'a') as f:
-                        f.write('%d,%d,%d,%r\n' % (istep, summ["SEGMENTS"], summ["DEGENERATE"], float(summ["LENGTH"])))
-            if blobs_every and istep % blobs_every == 0:
-                found = drv.blobs()
-                if lead:
-                    with open(blobs_path, 'a') as f:
-                        f.writelines(line + '\n' for line in blobs_mod.csv_lines(found[0], istep, eng.get_param("dx"), eng.get_param("dy")))
-            if tr_save and istep % tr_save == 0:
-                rows, summ = drv.tracer_rows()
-                np.save('data/tracers_%06d.npy' % istep, rows)
-                with open(tr_path, 'a') as f:
-                    f.write(tracers_mod.csv_line(dict(summ, ISTEP=istep)) + '\n')
-            if gauges_every:
-                if stop_at_gauges and istep % gauges_every == 0:
-                    drv.record_gauges()
-                recs = drv.take_gauges()
-                if recs:
-                    with open(gauges_path, 'a') as f:
-                        for k, rows in recs:
-                            f.writelines(line + '\n' for line in gauges_mod.gauges_csv_lines(k, rows))
-            if depths_every and istep % depths_every == 0:
-                prof = drv.depths()
-                if lead:
-                    d = gauges_mod.derive(prof[0], prof[3], eng.get_param("dx"), eng.get_param("dy"))
-                    np.save('data/depths_%06d.npy' % istep, np.stack([d["x"], d["depth"], prof[2].astype(np.float64)], axis=1))
-                    with open(depths_path, 'a') as f:
-                        f.write(gauges_mod.depths_csv_line(dict(prof[3], ISTEP=istep), eng.get_param("dx"), eng.get_param("dy")) + '\n')
-            if dye_on:
-                rows = drv.take_dye()
-                if rows:
-                    with open(dye_path, 'a') as f:
-                        for raw in rows:
-                            d, k = dye_mod.derive(raw, eng.get_param("dx"), eng.get_param("dy")), int(raw["ISTEP"])
-                            f.write(','.join([str(k), repr(k * dt)] + [repr(float(d[c])) for c in dye_mod.DERIVED]) + '\n')
-                if dye_save and istep % dye_save == 0:
-                    np.save('data/dye_%06d.npy' % istep, drv.dye())
-            if frames_every and istep % frames_every == 0:
-                rgb, _, fs = eng.frame(**frame_kw)
-                frames_mod.write_png('output/frame_%06d.png' % istep, rgb)
-                with open(frames_path, 'a') as f:
-                    f.write('%d,%r,%r,%r,%d\n' % (istep, istep * dt, fs["LO"], fs["HI"], fs["NAN_PIXELS"]))
-            if stats_every:
-                if istep % stats_every == 0 and istep >= stats_from:
-                    eng.stats_sample()
-                if stats_save and istep % stats_save == 0:
-                    save_stats(istep)
-                    stats_saved_at = istep
-            if args.save_every and istep % args.save_every == 0:
-                if dye_on:                                          # (beside the checkpoint, whose format stays as it is)
-                    np.savez('data/dye_state.tmp.npz', C=drv.dye(), istep=np.int64(istep))
-                    os.replace('data/dye_state.tmp.npz', 'data/dye_state.npz')
-                fields = {f: drv.full(f) for f in STATE}
-                warn = drv.courant()
-                if lead:
-                    save_state('data/%08d.npz' % istep, fields, istep, nx, ny, args.dtype, args.ic, warn, numerics)
-                if tracers_on:
-                    drv.save_tracers('data/tracers_state.npz', istep)   # (beside the checkpoint, whose format stays as it is)
-                if gauges_on:
-                    drv.save_gauges('data/gauges_state.npz', istep)
-            if (istep % nstep) == 0:  # Output data every <nstep> steps            (:530)
-                warn = drv.courant()
-                extra = drv.report()
-                Fnp = drv.full("F") if args.s else None
-                if args.s and iface_every and istep % iface_every != 0:
-                    iface_last = drv.interface()      # (the frame shows the interface of its own step)
-                if not lead:
-                    continue
-                from .vis import OPTIONS, save_display
-                say(f'>>> Number of steps:{istep:<5d}, Time:{istep*dt:5.2e} sec. Displaying {OPTIONS[args.vis][0]}.'
-                    + extra
-                    + (f' Volume: {diag_last["volume"]:.6e}, max|div u|: {diag_last["div_max"]:8.2e}, CFL: {diag_last["cfl"]:8.2e}.' if diag_last else '')
-                    + (f' [{warn} Courant warnings]' if warn else ''))
-                if args.s:
-                    import matplotlib
-                    matplotlib.use('Agg')
-                    import matplotlib.pyplot as plt
-                    count = istep // nstep - 1
-                    if world == 1:   # what gui.set_image / gui.arrows show in the reference (:531-559), as a file
-                        save_display(f'output/{count:06d}-vis.png', drv.sim, args.vis)
-                    fx, fy = 5, Ly / Lx * 5
-                    plt.figure(figsize=(fx, fy))
-                    plt.axis('off')
-                    plt.contourf(Fnp.T, cmap=plt.cm.Blues)
-                    if iface_every:
-                        from .vis import draw_segments
-                        draw_segments(plt.gca(), iface_last[0], eng.get_param("dx"), eng.get_param("dy"))
-                    plt.savefig(f'output/{count:06d}-f.png')
-                    plt.close()
+            for r in recs:
+                r.after(istep)
     except KeyboardInterrupt:
         pass
-    if stats_every and stats_saved_at != eng.istep:
-        save_stats(eng.istep)                                       # the end of the run
+    for r in recs:
+        r.end()                                      # (the statistics of the whole run)
     drv.close()
     return 0
 

@@ -32,6 +32,10 @@ def criterion_code(criterion):
     return {"abs": _abi.VOF_RESID_ABS, "rel": _abi.VOF_RESID_REL}[criterion]
 
 
+def _due(nsteps, every):   # the records a vof_step_<verb> call owes: one per whole group (0 for arguments the library refuses)
+    return max(nsteps, 0) // every if every >= 1 else 0
+
+
 def make_desc(api, nx, ny, dtype="f64", coord_cast="f32", rows=None, own=None, jacobi_iters=10,
               device=-1, flags=0, **consts):
     """vof_desc_default + overrides.  rows=(row_lo,row_hi), own=(own_lo,own_hi)."""
@@ -202,7 +206,7 @@ class Engine:
         """vof_step_diag: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), a row of diagnostics recorded on
         the device behind every `every` of them, one read-back at the end; returns the (rows, VOF_DIAG_N) float64 array."""
         crit = criterion_code(criterion)
-        rows = max(int(nsteps), 0) // int(every) if int(every) >= 1 else 0
+        rows = _due(int(nsteps), int(every))
         out = np.zeros((rows, _abi.VOF_DIAG_N), dtype=np.float64)
         done = C.c_int64()
         self._ck(self.api.step_diag(self._h, int(nsteps), int(every), int(mg_cycles), crit,
@@ -266,7 +270,7 @@ class Engine:
         (0: none), one read-back at the end; returns the (snapshots, COUNT, VOF_TRACER_N) float64 array."""
         crit = criterion_code(criterion)
         nsteps, every, snap_every = int(nsteps), int(every), int(snap_every)
-        due = (max(nsteps, 0) // every) // snap_every if every >= 1 and snap_every >= 1 else 0
+        due = _due(_due(nsteps, every), snap_every)
         count = int(self.tracers(rows=False)[1]["COUNT"]) if due else 0
         out = np.zeros((due, count, _abi.VOF_TRACER_N), dtype=np.float64)
         done = C.c_int64()
@@ -312,7 +316,7 @@ class Engine:
         float64 array."""
         crit = criterion_code(criterion)
         nsteps, every = int(nsteps), int(every)
-        due = max(nsteps, 0) // every if every >= 1 else 0
+        due = _due(nsteps, every)
         count = int(self.gauges_get(rows=False)[1]["COUNT"]) if due else 0
         out = np.zeros((due, count, _abi.VOF_GAUGE_N), dtype=np.float64)
         done = C.c_int64()
@@ -356,7 +360,7 @@ class Engine:
         the (rows, VOF_DYE_N) float64 array."""
         crit = criterion_code(criterion)
         nsteps, every = int(nsteps), int(every)
-        rows = max(nsteps, 0) // every if every >= 1 else 0
+        rows = _due(nsteps, every)
         out = np.zeros((rows, _abi.VOF_DYE_N), dtype=np.float64)
         done = C.c_int64()
         self._ck(self.api.step_dye(self._h, nsteps, every, int(mg_cycles), crit,
@@ -395,7 +399,7 @@ class Engine:
         from . import frames
         crit = criterion_code(criterion)
         nsteps, every = int(nsteps), int(every)
-        due = max(nsteps, 0) // every if every >= 1 else 0
+        due = _due(nsteps, every)
         s = frames.spec(quantity, bx, by, lo, hi, contour, symmetric)
         pw, ph = frames.shape(self.nx, self.ny, min(max(s.bx, 1), self.nx), min(max(s.by, 1), self.ny))
         out = np.zeros((due, ph, pw, 3), dtype=np.uint8)
