@@ -649,6 +649,63 @@ int vof_stats_sample(vof2d_handle h);
 int vof_stats_get(vof2d_handle h, int32_t slot, double* dst, int64_t cap_elems);
 int vof_stats_summary(vof2d_handle h, double* out /* VOF_STATS_SUM_N */);
 int vof_step_stats(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, int64_t* samples_taken);
+
+/* ---- an initial state painted from shapes (extension; kernels/scene.h) ----
+ * vof_set_scene rasterises an ordered list of shapes into F on the device, with samples x samples sample points a cell.  It is the
+ * input side next to vof_set_init_F: any state that is a union and difference of boxes, ellipses, half-planes and triangles, on a
+ * whole domain and on a strip alike (every handle paints the rows it stores from the same list), without an array on the host.
+ *   geometry    in doubles whatever the field type.  Cell (i, j) covers [(i-1) dx, i dx] x [(j-1) dy, j dy], dx and dy the doubles
+ *               vof_get_param reports; a ghost cell is a cell like any other, outside the domain
+ *   samples     S in {1, 2, 4, 8, 16}; sample (a, b), a, b in [0, S), of cell (i, j) sits at
+ *                 xs = ((double)(i-1) + ((double)a + 0.5) * (1.0/S)) * dx,   ys = ((double)(j-1) + ((double)b + 0.5) * (1.0/S)) * dy
+ *               (the bracket is exact: one rounding per coordinate)
+ *   a shape     VOF_SHAPE_N doubles: KIND, PHASE (VOF_SCENE_LIQUID or VOF_SCENE_GAS), A0 .. A5.  Every difference, product and sum
+ *               below is rounded on its own, in the order written (no fused multiply-add in either build); all tests are closed, so
+ *               two shapes that share an edge leave no seam; a comparison with a NaN (an overflow) is false
+ *     VOF_SHAPE_BOX        cx, cy, hx, hy, c, s:  px = xs - cx, py = ys - cy, lx = px*c + py*s, ly = py*c - px*s;
+ *                          inside if |lx| <= hx and |ly| <= hy.  c, s: the cosine and sine of the rotation, given by the caller
+ *     VOF_SHAPE_ELLIPSE    the same fields and lx, ly; inside if (lx*hy)*(lx*hy) + (ly*hx)*(ly*hx) <= (hx*hy)*(hx*hy)
+ *     VOF_SHAPE_HALFPLANE  px0, py0, nx, ny (A4, A5 are not used):  inside if (xs - px0)*nx + (ys - py0)*ny <= 0
+ *     VOF_SHAPE_TRIANGLE   x0, y0, x1, y1, x2, y2:  e0 = (x1-x0)*(ys-y0) - (y1-y0)*(xs-x0), e1 = (x2-x1)*(ys-y1) - (y2-y1)*(xs-x1),
+ *                          e2 = (x0-x2)*(ys-y2) - (y0-y2)*(xs-x2); inside if all three are >= 0 or all three are <= 0
+ *   painting    every sample starts as KEEP; the shapes are applied in list order, a sample inside a shape takes its phase: a later
+ *               shape overrides an earlier one
+ *   the value   n_liq, n_keep: the cell's samples that ended LIQUID, KEEP.  n_keep == S*S: the cell is not written, its bits stay
+ *               (a NaN, a -0.0).  Otherwise F = ((double)n_liq + (double)n_keep * (double)F_old) * (1.0/(S*S)), rounded once to the
+ *               field type; where n_keep == 0 F_old is not read (a NaN there does not leak).  With VOF_SCENE_CLEAR a KEEP sample counts
+ *               as GAS: F_old is never read and every stored cell is written, F = n_liq / (S*S)
+ *   written     F and its sweep twin, on every stored row and every column 0 .. ny + 1; u, v, p are not touched
+ *   summary     VOF_SCENE_SUM_N doubles (may be NULL; unused slots read 0): SHAPES = n, SAMPLES = S, PAINTED = the cells with
+ *               n_keep < S*S, MIXED = the cells whose samples are not all in one state (with VOF_SCENE_CLEAR: after KEEP became GAS),
+ *               ISTEP.  Both counts are over the interior cells of the rows the handle reports (vof_diagnostics): strips add up
+ * VOF_EINVAL, with nothing changed: a null handle; n < 0 or n > VOF_SCENE_MAX_SHAPES; shapes == NULL with n > 0; samples outside
+ * {1, 2, 4, 8, 16}; a flag bit outside VOF_SCENE_CLEAR; an unknown KIND or PHASE; a number in a record that is not finite; a
+ * negative half extent; |c*c + s*s - 1| > 1e-9; a half-plane with nx == ny == 0.  n == 0 is valid: the identity without
+ * VOF_SCENE_CLEAR (nothing at all happens), an empty domain with it.
+ * The handle's state is treated as vof_set_init_F treats it: pending ghost cells are settled first; afterwards F counts as written
+ * from outside (its ghost cells are whatever the shapes gave them: the first step applies the boundary conditions).  The call waits
+ * for the device (the counts are read back).  Knob "scene_shortcuts" (vof_set_param; default 1): 0 samples every cell against
+ * every shape, 1 skips the sampling where the corner samples prove all samples inside or all outside -- the same bytes. */
+#define VOF_SHAPE_N 8
+#define VOF_SHAPE_KIND 0
+#define VOF_SHAPE_PHASE 1
+#define VOF_SHAPE_A0 2
+#define VOF_SHAPE_BOX 0
+#define VOF_SHAPE_ELLIPSE 1
+#define VOF_SHAPE_HALFPLANE 2
+#define VOF_SHAPE_TRIANGLE 3
+#define VOF_SCENE_GAS 0
+#define VOF_SCENE_LIQUID 1
+#define VOF_SCENE_CLEAR 1
+#define VOF_SCENE_MAX_SHAPES 1024
+#define VOF_SCENE_SUM_SHAPES 0
+#define VOF_SCENE_SUM_SAMPLES 1
+#define VOF_SCENE_SUM_PAINTED 2
+#define VOF_SCENE_SUM_MIXED 3
+#define VOF_SCENE_SUM_ISTEP 4
+#define VOF_SCENE_SUM_N 8
+int vof_set_scene(vof2d_handle h, const double* shapes /* n x VOF_SHAPE_N */, int64_t n, int32_t samples, int32_t flags,
+                  double* summary /* VOF_SCENE_SUM_N, may be NULL */);
 /* = vof_solve_p(..., VOF_RESID_ABS, ...) */
 int vof_solve_p_residual(vof2d_handle h, double tol, int32_t max_iters, int32_t check_every,
                          int32_t* iters_done, double* residual);

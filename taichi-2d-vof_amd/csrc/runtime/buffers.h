@@ -80,6 +80,7 @@ struct WorkBufs {
   DevBuf frame_lut;    // ... the colour table, 258 x 3 bytes -- state, not scratch: replaced by vof_frame_set_lut alone
   DevBuf frame_recs;   // ... the pictures vof_step_frames records, their summaries behind them, grown on demand
   DevBuf stats;        // vof_stats_* (runtime/stats.h, StatsCarve): the accumulator planes -- state, not scratch: cleared by vof_stats_begin alone --, the partials and results of the summary
+  DevBuf scene;        // vof_set_scene (runtime/scene.h): the shape list as k_scene reads it (room for VOF_SCENE_MAX_SHAPES records), the slots of the two counters behind it
   DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
   DevBuf red;          // device scalar of vof_comm_allreduce_max
 

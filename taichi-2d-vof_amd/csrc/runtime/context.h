@@ -237,6 +237,9 @@ struct vof2d_ctx {
   double stats_level = 0.0;
   int64_t stats_samples = 0, stats_first = 0, stats_last = 0;
   int stats_chunk = 0;            // knob "stats_chunk_rows": rows per wave chunk of k_stats (0 = the rule of k_diag)
+  int scene_shortcuts = 1;        // knob "scene_shortcuts": k_scene skips the sampling of a cell against a shape where the corner samples decide it (same bytes)
+  std::vector<double> scene_host; // vof_set_scene: the host copy of the packed shape list the upload reads
+  std::vector<unsigned long long> scene_words;   // ... and of the counter slots read back
   char* h_depths = nullptr;     // pinned host copy of the results of a vof_depths pass (one copy out, then memcpy to the caller's arrays)
   size_t h_depths_bytes = 0;
   char* h_frame = nullptr;       // pinned host copy of the results of a vof_frame call (one copy out, then memcpy to the caller's arrays)

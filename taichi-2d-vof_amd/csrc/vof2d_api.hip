@@ -26,6 +26,7 @@
 //   runtime/dye.h        the dye arrays, launches and copies of vof_dye_*, the loop of vof_step_dye
 //   runtime/frames.h     the colour table, the buffers, launches and copies of vof_frame, the loop of vof_step_frames
 //   runtime/stats.h      the accumulator planes, launches and copies of vof_stats_*, the loop of vof_step_stats
+//   runtime/scene.h      plain C++: what vof_set_scene refuses, the packed records; the upload, the launch of k_scene, the summary
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -43,6 +44,7 @@
 #include "runtime/dye.h"
 #include "runtime/frames.h"
 #include "runtime/stats.h"
+#include "runtime/scene.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -72,7 +74,7 @@ const Knob kKnobs[] = {
   KNOB("tb_slow10", tb_slow10, false), KNOB("tune_period", tune.period, false),
   KNOB("mg_nu", mg_nu, true), KNOB("mg_levels", mg_levels, true), KNOB("mg_graph", mg_graph, true),
   KNOB("mg_coarse_block", mg_coarse_block, false), KNOB("dye_fused", dye_fused, true),
-  KNOB("stats_chunk_rows", stats_chunk, false),
+  KNOB("stats_chunk_rows", stats_chunk, false), KNOB("scene_shortcuts", scene_shortcuts, true),
 };
 #undef KNOB
 const Knob* find_knob(const char* name) {
@@ -245,6 +247,12 @@ int vof_set_init_F(vof2d_handle h, int32_t ic) {
   if (field_written(h->state, fF, full_domain(h), false)) forget_batch_form(h);
   if (tm_by_rule(h)) (void)post_gas_count(h);   // (the batch-form rule looks at the new F: the count is taken now, asynchronously, and read by the first batched step)
   return ensure_ok(h);
+}
+// ---- an initial state painted from shapes (kernels/scene.h, runtime/scene.h)
+int vof_set_scene(vof2d_handle h, const double* shapes, int64_t n, int32_t samples, int32_t flags, double* summary) {
+  if (!h) return VOF_EINVAL;
+  if (const char* const msg = scene_check(shapes, n, samples, flags)) return fail(h, VOF_EINVAL, msg);
+  return scene_run(h, shapes, n, samples, flags, summary);
 }
 int vof_set_BC(vof2d_handle h) {
   if (!h) return VOF_EINVAL;

@@ -28,6 +28,7 @@
 //   dye.h        k_dye, k_dye_stats, k_dye_stats_finish   (extension: a marker field moved by both FCT sweeps in one pass over C, u, v; its sums and extrema in one fixed-order pass)
 //   frames.h     k_frame_cols, k_frame_fold, k_frame_paint   (extension: a colour-mapped picture of F, u, v, the speed, p, the vorticity or the dye: box averages in a fixed order, a 256-entry colour table, the interface marked on top)
 //   stats.h      k_stats, k_stats_fill, k_stats_summary, k_stats_finish   (extension: per-cell running sums of F, u, v and their products, envelopes, wet time and arrival step over a run: one streaming pass per sample over the fields and planes of doubles)
+//   scene.h      k_scene   (extension: an initial state painted from an ordered list of boxes, ellipses, half-planes and triangles, S x S samples a cell as bit masks in registers)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
@@ -49,3 +50,4 @@
 #include "kernels/dye.h"
 #include "kernels/frames.h"
 #include "kernels/stats.h"
+#include "kernels/scene.h"

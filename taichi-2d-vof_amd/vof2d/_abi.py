@@ -54,6 +54,14 @@ VOF_STATS_MOMENTS, VOF_STATS_ENVELOPE = 1, 2
 (VOF_STATS_SUM_SAMPLES, VOF_STATS_SUM_ISTEP_FIRST, VOF_STATS_SUM_ISTEP_LAST, VOF_STATS_SUM_MASK, VOF_STATS_SUM_LEVEL, VOF_STATS_SUM_CELLS,
  VOF_STATS_SUM_EVER_WET, VOF_STATS_SUM_MAX_SPEED2) = range(8)
 VOF_STATS_SUM_N = 16
+# vof_set_scene: the fields of a shape record, the kinds, the phases, the flag, the limit and the slots of the summary (vof2d/scene.py)
+VOF_SHAPE_N, VOF_SHAPE_KIND, VOF_SHAPE_PHASE, VOF_SHAPE_A0 = 8, 0, 1, 2
+VOF_SHAPE_BOX, VOF_SHAPE_ELLIPSE, VOF_SHAPE_HALFPLANE, VOF_SHAPE_TRIANGLE = range(4)
+VOF_SCENE_GAS, VOF_SCENE_LIQUID = 0, 1
+VOF_SCENE_CLEAR = 1
+VOF_SCENE_MAX_SHAPES = 1024
+VOF_SCENE_SUM_SHAPES, VOF_SCENE_SUM_SAMPLES, VOF_SCENE_SUM_PAINTED, VOF_SCENE_SUM_MIXED, VOF_SCENE_SUM_ISTEP = range(5)
+VOF_SCENE_SUM_N = 8
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -105,6 +113,7 @@ SIGNATURES = {
     "create": (C.c_int, [C.POINTER(Desc), C.c_void_p, C.POINTER(H)]),
     "destroy": (C.c_int, [H]),
     "set_init_F": (C.c_int, [H, _i32]),
+    "set_scene": (C.c_int, [H, C.POINTER(_dbl), _i64, _i32, _i32, C.POINTER(_dbl)]),
     "set_BC": (C.c_int, [H]),
     "cal_nu_rho": (C.c_int, [H]),
     "get_normal_young": (C.c_int, [H]),
@@ -191,7 +200,7 @@ GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_pr
             "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "blobs",
             "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges",
             "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye", "frame_set_lut", "frame", "step_frames",
-            "stats_begin", "stats_sample", "stats_get", "stats_summary", "step_stats")
+            "stats_begin", "stats_sample", "stats_get", "stats_summary", "step_stats", "set_scene")
 
 
 class Api:

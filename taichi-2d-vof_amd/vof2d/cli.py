@@ -131,6 +131,13 @@ def build_parser():
     ext.add_argument('--stats-save-every', type=int, default=None, metavar='M',
                      help='every M steps, and at the end of the run, write data/stats_NNNNNN.npz -- the raw planes, the sample count N and the '
                           'derived arrays -- and append a line of the summary to data/stats.csv (default: at the end of the run only)')
+    ext.add_argument('--scene', default=None, metavar='FILE.json',
+                     help='the initial state: the shapes of FILE.json (rect, box, disc, ellipse, halfplane, triangle, polygon, each liquid or '
+                          'gas; vof2d/scene.py) painted in list order over an empty domain on the device (vof_set_scene), in place of -ic; '
+                          'works with --gpus N; not with --resume (a checkpoint holds its own state)')
+    ext.add_argument('--scene-over-ic', action='store_true', help='paint the scene over the state of -ic instead of an empty domain')
+    ext.add_argument('--scene-samples', type=int, default=None, metavar='S',
+                     help="sample points per cell and axis, 1, 2, 4, 8 or 16 (default: the file's \"samples\", 8 without one)")
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
     return parser
 
@@ -186,10 +193,32 @@ def parse_dye_boxes(specs):
     return out
 
 
+def load_scene(args):
+    """(records, samples) of --scene FILE.json with --scene-samples applied; SystemExit with the reason where the file cannot be used."""
+    from . import scene
+    try:
+        recs, samples = scene.load(args.scene)
+        if args.scene_samples is not None:
+            samples = scene.check_samples(args.scene_samples)
+    except OSError as e:
+        raise SystemExit("--scene %s: cannot be read: %s" % (args.scene, e.strerror or e))
+    except ValueError as e:                          # (a JSON syntax error is one too)
+        raise SystemExit("--scene %s: %s" % (args.scene, e))
+    return recs, samples
+
+
 def parse_args(argv=None):
     """build_parser().parse_args plus the combinations argparse cannot express."""
     parser = build_parser()
     args = parser.parse_args(argv)
+    args.scene_shapes = None
+    if args.scene is not None:
+        if args.resume:
+            raise SystemExit("--scene cannot be combined with --resume: a checkpoint holds the state the run continues from, "
+                             "and a scene would paint over it (drop one of them)")
+        args.scene_shapes, args.scene_samples = load_scene(args)
+    elif args.scene_over_ic or args.scene_samples is not None:
+        parser.error("--scene-over-ic and --scene-samples belong to --scene FILE.json: pass that too")
     def at_least_1(*options):                        # (in this order: the first refusal is the one reported)
         for opt in options:
             if getattr(args, opt + "_every") is not None and getattr(args, opt + "_every") < 1:
@@ -367,6 +396,11 @@ class _Single:
     def init(self, ic):
         self.sim.set_init_F(ic)
 
+    def paint_scene(self, shapes, samples, clear):
+        """(PAINTED, MIXED) of the scene painted on the device."""
+        summ = self.sim.set_scene(shapes, samples, clear)
+        return int(summ["PAINTED"]), int(summ["MIXED"])
+
     def tracer_rows(self):
         """(rows, summary) with TIME and the counts continued over a resume."""
         rows, summ = self.eng.tracers()
@@ -522,6 +556,12 @@ class _Strips:
     def init(self, ic):
         pass                                         # StripSolver ran set_init_F on its strip
 
+    def paint_scene(self, shapes, samples, clear):
+        """Every rank paints its strip from the same list; rank 0 holds the domain's (PAINTED, MIXED), the others (0, 0)."""
+        summ = self.s.set_scene(shapes, samples, clear)
+        parts = self.s.comm.gather_object((int(summ["PAINTED"]), int(summ["MIXED"])))
+        return (sum(p[0] for p in parts), sum(p[1] for p in parts)) if self.rank == 0 else (0, 0)
+
     def load(self, fields, istep, courant=0):
         lo, hi = self.s.rows
         for f in STATE:
@@ -618,6 +658,11 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
 
     istep = 0
     drv.init(args.ic)
+    if getattr(args, "scene_shapes", None) is not None:
+        painted, mixed = drv.paint_scene(args.scene_shapes, args.scene_samples, not args.scene_over_ic)
+        if lead:
+            say(f'>>> Scene {args.scene}: {len(args.scene_shapes)} shapes, {args.scene_samples} x {args.scene_samples} samples a cell, '
+                f'painted {painted} cells, {mixed} of them mixed.')
     if lead:
         os.makedirs('output', exist_ok=True)  # Make dir for output                 (:500)
         os.makedirs('data', exist_ok=True)    # Make dir for data save               (:501)

@@ -103,6 +103,17 @@ class Engine:
     def set_init_F(self, ic):
         self._ck(self.api.set_init_F(self._h, int(ic)), "set_init_F")
 
+    def set_scene(self, shapes, samples=8, clear=True):
+        """vof_set_scene: paints the shapes (a list of records of vof2d/scene.py, or the array of scene.pack) into F on the
+        rows this handle stores, samples x samples sample points a cell, in list order; clear=True empties the domain first,
+        clear=False paints over the F that is there.  Returns the summary as a dict keyed by scene.SUMMARY."""
+        from . import scene
+        recs = scene.pack(shapes)
+        summ = (C.c_double * _abi.VOF_SCENE_SUM_N)()
+        self._ck(self.api.set_scene(self._h, recs.ctypes.data_as(C.POINTER(C.c_double)) if len(recs) else None, len(recs),
+                                    scene.check_samples(samples), _abi.VOF_SCENE_CLEAR if clear else 0, summ), "set_scene")
+        return scene.summary_of(list(summ))
+
     def set_BC(self):
         self._ck(self.api.set_BC(self._h), "set_BC")
 

@@ -70,6 +70,10 @@ class VOF2D:
     def set_init_F(self, ic):
         self.eng.set_init_F(ic)
 
+    def set_scene(self, shapes, samples=8, clear=True):
+        """An initial state painted from shapes on the device (vof_set_scene; the shapes: vof2d/scene.py); the summary as a dict."""
+        return self.eng.set_scene(shapes, samples, clear)
+
     def set_BC(self):
         self.eng.set_BC()
 

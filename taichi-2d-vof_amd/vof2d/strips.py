@@ -162,6 +162,14 @@ class StripSolver:
         if self.exchange_kind == "torch" and not torch_free:
             self._build_views()
 
+    def set_scene(self, shapes, samples=8, clear=True):
+        """vof_set_scene on this strip: every rank paints the rows it stores, halo rows included, from the same list (no exchange
+        is needed); the strip is fresh again, as after set_init_F.  Returns this strip's summary: PAINTED and MIXED count its
+        owned rows, so the strips' counts add up to the domain's."""
+        summ = self.eng.set_scene(shapes, samples, clear)
+        self._fresh = True
+        return summ
+
     def _native_comm_init(self, strict):
         """One RCCL communicator per strip handle; its unique id travels over `self.comm`.  With a
         TorchComm every rank ends up in the same mode: failures are agreed on before committing."""
