@@ -38,7 +38,7 @@
 //
 // THE FIVE SUMS of blob b (no floating-point atomics), for the first min(BLOBS, cap_rows) blobs.  With f = F[i,j]:
 //   Fc = fmin(fmax(f, 0), 1)      w = Fc (liquid) | 1 - Fc (gas)
-//   uc = (u[i,j] + u[i+1,j]) * 0.5      vc = (v[i,j] + v[i,j+1]) * 0.5                      (interp_velocity, 2dvof.py:492; kernels/diag.h)
+//   uc = (u[i,j] + u[i+1,j]) * 0.5      vc = (v[i,j] + v[i,j+1]) * 0.5                      (clamp01, face_mean of kernels/cells.h)
 //   SUM_W += w    SUM_WI += w * i    SUM_WJ += w * j    SUM_WU += w * uc    SUM_WV += w * vc    (i, j global indices as doubles)
 // Order, fixed by the geometry and the blob's own box [imin, imax] x [jmin, jmax] alone:
 //   1. the box is cut into row chunks of kBlobRows rows counted from imin and into the column tiles of the grid
@@ -52,7 +52,7 @@
 // most of the domain is spread over (rows / kBlobRows) x tiles waves like any pass over the grid.
 // No contraction (-ffp-contract=off): each term is the bits of the line above.
 #pragma once
-#include "interface.h"
+#include "cells.h"
 
 namespace vof {
 
@@ -92,7 +92,7 @@ __device__ __forceinline__ void blob_unite(int* parent, int a, int b) {
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_blob_init(Geom g, const T* __restrict__ F, int R, int phase, double thr, int* __restrict__ parent) {
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb)) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb)) return;
   const int ny = g.ny, lane = threadIdx.x & 63;
   const int col0 = j0 - 1 - lane * V;   // (0-based column of the tile's first cell, wave-uniform)
   const unsigned long long below = lane ? ~0ull >> (64 - lane) : 0ull;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_blob_init(Geom g, const T* __restrict__
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_blob_merge(Geom g, const T* __restrict__ F, int R, int phase, double thr, int* __restrict__ parent) {
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb)) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb)) return;
   const int ny = g.ny, lane = threadIdx.x & 63;
   size_t o = at(g, ra, j0);
   bool up[V], upl[V];   // membership of (i - 1, j) and of (i - 1, j - 1)
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_blob_merge(Geom g, const T* __restrict_
 template <int V>
 __global__ __launch_bounds__(256) void k_blob_flatten(Geom g, int R, int* __restrict__ parent, int* __restrict__ cnt) {
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb)) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb)) return;
   const int ny = g.ny, lane = threadIdx.x & 63;
   const int tile = (j0 - 1) / (64 * V);
   for (int i = ra; i <= rb; ++i) {
@@ -193,7 +193,7 @@ template <int V>
 __global__ __launch_bounds__(256) void k_blob_number(Geom g, int R, const int* __restrict__ parent, const int* __restrict__ cnt, int* __restrict__ index,
                                                       int* __restrict__ rec) {
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb)) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb)) return;
   const int ny = g.ny;
   const int tile = (j0 - 1) / (64 * V);
   for (int i = ra; i <= rb; ++i) {
@@ -235,7 +235,7 @@ __device__ __forceinline__ void blob_record(int* __restrict__ rec, int label, in
 template <int V>
 __global__ __launch_bounds__(256) void k_blob_label(Geom g, int R, int* __restrict__ parent, const int* __restrict__ index, int* __restrict__ rec) {
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb)) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb)) return;
   const int ny = g.ny, lane = threadIdx.x & 63;
   const int tj0 = j0 - lane * V;   // (the tile's first column, wave-uniform)
   int wl = -1, wc = 0, wi0 = 0, wi1 = 0, wj0 = 0, wj1 = 0;   // the wave's record while it sees one label
@@ -369,13 +369,13 @@ __global__ __launch_bounds__(256) void k_blob_sums(Geom g, const T* __restrict__
       const int j = j0 + q;
       if (j <= ny && labels[rowkey + j - 1] == b) {
         const size_t o = at(g, i, j);
-        const double f = (double)F[o], uw = (double)u[o], ue = (double)u[o + g.pitch], vs = (double)v[o], vn = (double)v[o + 1];
-        const double Fc = __builtin_fmin(__builtin_fmax(f, 0.0), 1.0);
+        const Cell c = {di, (double)j, (double)F[o], (double)u[o], (double)u[o + g.pitch], (double)v[o], (double)v[o + 1]};
+        const double Fc = clamp01(c.f);
         const double w = phase == 0 ? Fc : 1.0 - Fc;
-        const double uc = (uw + ue) * 0.5, vc = (vs + vn) * 0.5;
+        const double uc = face_mean(c.w, c.e), vc = face_mean(c.s, c.n);
         acc[0] += w;
-        acc[1] += w * di;
-        acc[2] += w * (double)j;
+        acc[1] += w * c.i;
+        acc[2] += w * c.j;
         acc[3] += w * uc;
         acc[4] += w * vc;
       }

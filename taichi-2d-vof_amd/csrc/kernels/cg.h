@@ -24,7 +24,7 @@
 // mode); tests/test_solver_bits_gpu.py holds the kernels to it bit for bit.  tests/_cg_np.py restates the METHOD, from the
 // textbook: the independent judge of what a solve converges to, not of these bits.
 #pragma once
-#include "reduce.h"
+#include "cells.h"
 
 namespace vof {
 
@@ -33,19 +33,6 @@ enum : int { CG_SUMB = 0, CG_C, CG_RZ, CG_RZ_OLD, CG_SQ, CG_ALPHA, CG_BETA, CG_M
 // what k_cg_finish does with the sums it has formed
 enum : int { CG_FIN_SUMB = 0, CG_FIN_RESID, CG_FIN_APPLY, CG_FIN_UPDATE };
 constexpr int kCgPart = 3;   // doubles per block in the partials buffer: one sum, two maxima
-
-// wave -> (first column of the lane, rows [ra, rb]); false (wave-uniform) for a wave past the last chunk.  Unlike
-// wave_tile no LANE leaves: lanes right of ny load in-row padding, contribute nothing and store nothing, so that the
-// cross-lane moves and the block reduction below always see 64 live lanes.
-template <int V>
-__device__ __forceinline__ bool cg_tile(const Geom& g, int R, int& j0, int& ra, int& rb) {
-  const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tj = wave % g.ntj, ch = wave / g.ntj;
-  j0 = 1 + tj * 64 * V + (int)(threadIdx.x & 63) * V;
-  ra = g.ilo + ch * R;
-  rb = ra + R - 1 < g.ihi ? ra + R - 1 : g.ihi;
-  return ra <= g.ihi;
-}
 
 // ------------------------------------------------------------------ the block partials -> scalars, alpha, beta
 // ONE block of 256 threads folds the partials (fold_partials of kernels/reduce.h); thread 0 acts on the result.  The launch
@@ -90,7 +77,7 @@ __global__ __launch_bounds__(256) void k_cg_finish(const double* __restrict__ pa
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_cg_sum(Geom g, const T* __restrict__ b, int R, double* __restrict__ part) {
   int j0, ra, rb;
-  const bool active = cg_tile<V>(g, R, j0, ra, rb);
+  const bool active = cell_tile<V>(g, R, j0, ra, rb);
   double acc[kCgPart] = {0.0, 0.0, 0.0};
   if (active) {
     size_t o = at(g, ra, j0);
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256) void k_cg_residual(Geom g, Consts<T> c, const 
                                                       T* __restrict__ r, int R, const double* __restrict__ sc,
                                                       double* __restrict__ part) {
   int j0, ra, rb;
-  const bool active = cg_tile<V>(g, R, j0, ra, rb);
+  const bool active = cell_tile<V>(g, R, j0, ra, rb);
   double acc[kCgPart] = {0.0, 0.0, 0.0};
   if (active) {
     const int nx = g.nx, ny = g.ny;
@@ -173,7 +160,7 @@ __global__ __launch_bounds__(256) void k_cg_apply(Geom g, Consts<T> c, const T* 
                                                    T* __restrict__ s_out, T* __restrict__ qo, int R,
                                                    const double* __restrict__ sc, double* __restrict__ part) {
   int j0, ra, rb;
-  bool active = cg_tile<V>(g, R, j0, ra, rb);
+  bool active = cell_tile<V>(g, R, j0, ra, rb);
   if (sc[CG_STOP] != 0.0) active = false;
   double acc[kCgPart] = {0.0, 0.0, 0.0};
   if (active) {
@@ -240,7 +227,7 @@ __global__ __launch_bounds__(256) void k_cg_update(Geom g, Consts<T> c, T* __res
                                                     T* __restrict__ r, const T* __restrict__ qi, int R,
                                                     const double* __restrict__ sc, double* __restrict__ part) {
   int j0, ra, rb;
-  bool active = cg_tile<V>(g, R, j0, ra, rb);
+  bool active = cell_tile<V>(g, R, j0, ra, rb);
   if (sc[CG_STOP] != 0.0) active = false;
   double acc[kCgPart] = {0.0, 0.0, 0.0};
   if (active) {

@@ -31,7 +31,7 @@
 //   ig = (int)floor(X * dxi) + 1  clamped to [1, nx]      DEPTH = depth_i[ig] * dy      TOP = (double)top[ig]
 // with depth_i and top of the k_depths pass in front of it.
 #pragma once
-#include "cg.h"
+#include "cells.h"
 #include "tracers.h"
 
 namespace vof {
@@ -51,7 +51,7 @@ template <typename T, int V>
 __global__ __launch_bounds__(256) void k_depths(Geom g, const T* __restrict__ F, int R, double* __restrict__ rowpart, double* __restrict__ colpart,
                                                  int* __restrict__ top) {
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb)) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb)) return;
   const int ny = g.ny, ntj = g.ntj, lane = (int)(threadIdx.x & 63);
   const int tj = (j0 - 1) / (64 * V);
   int* const words = top + (g.ihi - g.ilo + 1);

@@ -1,4 +1,4 @@
-// kernels/dye.h -- a marker field carried by the reference's FCT transport (k_dye), and its statistics (k_dye_stats, k_dye_stats_finish)
+// kernels/dye.h -- a marker field carried by the reference's FCT transport (k_dye), and its statistics (k_dye_stats, kDyeRow)
 //
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
@@ -8,7 +8,7 @@
 // place of F on the FINAL u, v of a step: the operator is transport.h's, cell function by cell function.
 #pragma once
 #include "transport.h"
-#include "diag.h"
+#include "cells.h"
 
 namespace vof {
 
@@ -125,8 +125,12 @@ __global__ __launch_bounds__(256) void k_dye(Geom g, Consts<T> c, const T* __res
 // slots of a row (= VOF_DYE_* of include/vof2d.h)
 enum : int { DY_ISTEP = 0, DY_CELLS, DY_SUM_C, DY_SUM_CI, DY_SUM_CJ, DY_SUM_C2, DY_SUM_CF, DY_SUM_CU, DY_SUM_CV, DY_MIN_C, DY_MAX_C, DY_MAX_EXCESS, DY_N = 16 };
 constexpr int kDyeSums = 7, kDyePart = 10;   // doubles per block in the partials buffer: seven sums, then three maxima (-C, C, C - F)
+constexpr RowMap<kDyeSums, kDyePart - kDyeSums> kDyeRow = {DY_N, {{ROW_ISTEP, 0}, {ROW_CELLS, 0}, {ROW_VALUE, 0}, {ROW_VALUE, 1}, {ROW_VALUE, 2}, {ROW_VALUE, 3}, {ROW_VALUE, 4},
+    {ROW_VALUE, 5}, {ROW_VALUE, 6}, {ROW_MINUS, 7}, {ROW_VALUE, 8}, {ROW_VALUE, 9}},
+    {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()}};
+static_assert(DY_CELLS == 1 && DY_SUM_C == 2 && DY_SUM_CV == 8 && DY_MIN_C == 9 && DY_MAX_C == 10 && DY_MAX_EXCESS == 11, "kDyeRow lists the slots in this order");
 
-// One pass over C, F, u, v on the cells i in [g.ilo, g.ihi], j in [1, ny], the shape of k_diag (kernels/diag.h).  Every
+// One pass over C, F, u, v on the cells i in [g.ilo, g.ihi], j in [1, ny], the march of k_diag (reduced_rows of kernels/cells.h) with C as the extra field.  Every
 // operand is converted to double first; then, per cell, in this order (tests/_dye_np.py restates it term for term):
 //   c  = C[i,j]     f = F[i,j]       uw = u[i,j]    ue = u[i+1,j]    vs = v[i,j]    vn = v[i,j+1]
 //   SUM_C  += c
@@ -139,72 +143,24 @@ constexpr int kDyeSums = 7, kDyePart = 10;   // doubles per block in the partial
 //   MIN_C = -max(-c)                 MAX_C = max(c)                  MAX_EXCESS = max(c - f)
 // A NaN operand of a maximum counts as +inf (diag_max of kernels/reduce.h: a NaN C reads MAX_C = +inf, MIN_C = -inf); the
 // sums propagate it.  No contraction (-ffp-contract=off).
-// Order of the sums, fixed: a lane adds its cells row by row, column by column (lane l of tile t holds columns
-// 1 + 64 V t + V l ... + V - 1); from there the reduction of kernels/reduce.h, seven sums and three maxima wide.
+// Order of the sums, fixed: that of k_diag; seven sums and three maxima wide, folded by k_row_finish into the row kDyeRow describes.
 template <typename T, int V>
 __global__ __launch_bounds__(256) void k_dye_stats(Geom g, const T* __restrict__ C, const T* __restrict__ F, const T* __restrict__ u,
                                                     const T* __restrict__ v, int R, double* __restrict__ part) {
-  int j0, ra, rb;
-  const bool active = cg_tile<V>(g, R, j0, ra, rb);
   const double ninf = -__builtin_huge_val();
   double acc[kDyePart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, ninf, ninf, ninf};
-  if (active) {
-    const int ny = g.ny;
-    const int64_t pitch = g.pitch;
-    size_t o = at(g, ra, j0);
-    T uw[V];
-    load_c<T, V>(uw, u + o);
-    for (int i = ra; i <= rb; ++i) {
-      T cc[V], f[V], ue[V];
-      Row<T, V> vr;
-      load_s<T, V>(cc, C + o);
-      load_s<T, V>(f, F + o);
-      load_c<T, V>(ue, u + o + pitch);
-      load_row<T, V>(vr, v + o);
-      const double di = (double)i;
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        if (j0 + q <= ny) {
-          const double cd = (double)cc[q], fd = (double)f[q], w = (double)uw[q], e = (double)ue[q], s = (double)vr.c[q], n = (double)right_of(vr, q);
-          acc[0] += cd;
-          acc[1] += cd * di;
-          acc[2] += cd * (double)(j0 + q);
-          acc[3] += cd * cd;
-          const double Fc = __builtin_fmin(__builtin_fmax(fd, 0.0), 1.0);
-          acc[4] += cd * Fc;
-          const double uc = (w + e) * 0.5, vc = (s + n) * 0.5;
-          acc[5] += cd * uc;
-          acc[6] += cd * vc;
-          acc[7] = diag_max(acc[7], -cd);
-          acc[8] = diag_max(acc[8], cd);
-          acc[9] = diag_max(acc[9], cd - fd);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < V; ++q) uw[q] = ue[q];
-      o += pitch;
-    }
-  }
-  block_publish<kDyeSums, kDyePart - kDyeSums>(acc, part);
-}
-
-// ONE block of 256 threads, the shape of k_diag_finish: fold_partials, then threads 0 .. DY_N - 1 store one slot each
-// (unused slots read 0)
-__global__ __launch_bounds__(256) void k_dye_stats_finish(const double* __restrict__ part, int nblocks, double* __restrict__ row, double istep, double cells) {
-  __shared__ double red[256][kDyePart];
-  const int t = threadIdx.x;
-  const double ninf = -__builtin_huge_val();
-  const double init[kDyePart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, ninf, ninf, ninf};
-  fold_partials<256, kDyeSums, kDyePart - kDyeSums>(part, nblocks, init, red);
-  if (t >= DY_N) return;
-  double x = 0.0;
-  if (t == DY_ISTEP) x = istep;
-  else if (t == DY_CELLS) x = cells;
-  else if (t >= DY_SUM_C && t <= DY_SUM_CV) x = red[0][t - DY_SUM_C];
-  else if (t == DY_MIN_C) x = -red[0][7];
-  else if (t == DY_MAX_C) x = red[0][8];
-  else if (t == DY_MAX_EXCESS) x = red[0][9];
-  row[t] = x;
+  reduced_rows<kDyeSums, kDyePart - kDyeSums, true, T, V>(g, C, F, u, v, R, acc, part, [&](const Cell& c, double cd) {
+    acc[0] += cd;
+    acc[1] += cd * c.i;
+    acc[2] += cd * c.j;
+    acc[3] += cd * cd;
+    acc[4] += cd * clamp01(c.f);
+    acc[5] += cd * face_mean(c.w, c.e);
+    acc[6] += cd * face_mean(c.s, c.n);
+    acc[7] = diag_max(acc[7], -cd);
+    acc[8] = diag_max(acc[8], cd);
+    acc[9] = diag_max(acc[9], cd - c.f);
+  });
 }
 
 }  // namespace vof

@@ -5,13 +5,13 @@
 //
 // Extension, not part of the reference (include/vof2d.h, vof_frame, vof_step_frames).  A whole domain; every
 // operand is converted to double on load (one code path for both dtypes); every product, sum, difference, quotient and root
-// below is rounded on its own: every product goes through fr_mul, whose result no contraction reaches, so the FMA build gives the same bytes.
+// below is rounded on its own: every product goes through mul_rounded (kernels/cells.h), whose result no contraction reaches, so the FMA build gives the same bytes.
 // A NumPy restatement follows it term for term (tests/_frames_np.py).
 //
 //   the cell value q[i,j], i in [1, nx], j in [1, ny]
 //     F, P, DYE   F[i,j], p[i,j], C[i,j], raw
 //     U           uc(i,j) = (u[i,j] + u[i+1,j]) * 0.5
-//     V           vc(i,j) = (v[i,j] + v[i,j+1]) * 0.5                        (the expressions of kernels/diag.h)
+//     V           vc(i,j) = (v[i,j] + v[i,j+1]) * 0.5                        (face_mean of kernels/cells.h, the product rounded on its own)
 //     SPEED       sqrt(uc * uc + vc * vc)
 //     VORT        (vc(i+1,j) - vc(i-1,j)) * hx - (uc(i,j+1) - uc(i,j-1)) * hy     hx = 0.5 dxi, hy = 0.5 dyi, doubles of the host;
 //                 vc(i+-1, j), uc(i, j+-1) are the expressions above at the neighbouring cell, a ghost cell at the walls
@@ -37,7 +37,7 @@
 // no scratch, no floating-point atomics.  Traffic: every field the quantity reads once (u twice at chunk seams), the partials
 // (1 / bx of a field in doubles) once each way.
 #pragma once
-#include "dye.h"
+#include "cells.h"
 
 namespace vof {
 
@@ -58,26 +58,17 @@ __device__ __forceinline__ double frame_unkey(unsigned long long k) {
   return __longlong_as_double((long long)((k >> 63) ? k ^ 0x8000000000000000ull : ~k));
 }
 
-// a * b rounded on its own in either build: the product passes through an empty asm statement, so the compiler cannot fuse it
-// with the addition or subtraction that takes it (-ffp-contract=fast fuses in the backend, whatever a pragma in the source says;
-// the parity build has nothing to fuse).  No instruction is emitted for it.
-__device__ __forceinline__ double fr_mul(double a, double b) {
-  double p = a * b;
-  asm("" : "+v"(p));
-  return p;
-}
-
 // element k in [-1, V] of a row with its neighbours, as a double
 template <typename T, int V>
 __device__ __forceinline__ double fr_at(const Row<T, V>& w, int k) { return (double)(k < 0 ? w.l : (k >= V ? w.r : w.c[k])); }
 // uc at column offset k from the u rows i and i + 1; vc at column offset q in [0, V) from the v row
 template <typename T, int V>
 __device__ __forceinline__ double fr_uc(const Row<T, V>& a, const Row<T, V>& b, int k) {
-  return fr_mul(fr_at<T, V>(a, k) + fr_at<T, V>(b, k), 0.5);
+  return mul_rounded(fr_at<T, V>(a, k) + fr_at<T, V>(b, k), 0.5);
 }
 template <typename T, int V>
 __device__ __forceinline__ double fr_vc(const Row<T, V>& a, int q) {
-  return fr_mul(fr_at<T, V>(a, q) + fr_at<T, V>(a, q + 1), 0.5);
+  return mul_rounded(fr_at<T, V>(a, q) + fr_at<T, V>(a, q + 1), 0.5);
 }
 
 // ------------------------------------------------------------------ the pass over the fields
@@ -89,7 +80,7 @@ __global__ __launch_bounds__(256) void k_frame_cols(Geom g, const T* __restrict_
   constexpr bool NU = Q == FQ_U || Q == FQ_SPEED || Q == FQ_VORT, NV = Q == FQ_V || Q == FQ_SPEED, VORT = Q == FQ_VORT;
   static_assert(Q == FQ_F || NU || NV, "a quantity of the list");
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb)) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb)) return;
   const size_t pitch = (size_t)g.pitch;
   size_t o = at(g, ra, j0);
   // the windows: x, f rows i of s, F; u0, u1 rows i, i + 1 of u; v0 row i of v (V, SPEED); v1 row i + 1 of v with vcm, vc0 = vc of rows i - 1, i (VORT)
@@ -133,10 +124,10 @@ __global__ __launch_bounds__(256) void k_frame_cols(Geom g, const T* __restrict_
       else if constexpr (Q == FQ_V) val = fr_vc<T, V>(v0, q);
       else if constexpr (Q == FQ_SPEED) {
         const double uc = fr_uc<T, V>(u0, u1, q), vc = fr_vc<T, V>(v0, q);
-        val = __builtin_sqrt(fr_mul(uc, uc) + fr_mul(vc, vc));
+        val = __builtin_sqrt(mul_rounded(uc, uc) + mul_rounded(vc, vc));
       } else {
         vcp[q] = fr_vc<T, V>(v1, q);
-        val = fr_mul(vcp[q] - vcm[q], hx) - fr_mul(fr_uc<T, V>(u0, u1, q + 1) - fr_uc<T, V>(u0, u1, q - 1), hy);
+        val = mul_rounded(vcp[q] - vcm[q], hx) - mul_rounded(fr_uc<T, V>(u0, u1, q + 1) - fr_uc<T, V>(u0, u1, q - 1), hy);
       }
       c[q] += val;
       if constexpr (CONTOUR) cf[q] += (double)f[q];
@@ -246,7 +237,7 @@ __global__ __launch_bounds__(256) void k_frame_paint(const double* __restrict__ 
       const double t = (m - lo) / (hi - lo);
       if (hi == lo || !(t > 0.0)) idx = 0;
       else if (t >= 1.0) idx = 255;
-      else idx = (int)(fr_mul(t, 255.0) + 0.5);
+      else idx = (int)(mul_rounded(t, 255.0) + 0.5);
       if (mF) {
         const bool s0 = mF[at_m] >= 0.5;
         if ((a + 1 < pw && s0 != (mF[at_m + ph] >= 0.5)) || (b + 1 < ph && s0 != (mF[at_m + 1] >= 0.5))) {

@@ -42,7 +42,7 @@
 // reduction of kernels/reduce.h, two sums wide: one partial of kIfacePart doubles per block, folded by k_iface_scan (one
 // block of 1024 threads).  The degenerate count travels the same way as a double (exact).
 #pragma once
-#include "cg.h"
+#include "cells.h"
 
 namespace vof {
 
@@ -98,7 +98,7 @@ template <typename T, int V, bool EMIT>
 __global__ __launch_bounds__(256) void k_iface(Geom g, const T* __restrict__ F, int R, IfaceConsts c, int* __restrict__ cnt, double* __restrict__ part,
                                                 double* __restrict__ rows, long long cap) {
   int j0, ra, rb;
-  const bool active = cg_tile<V>(g, R, j0, ra, rb);
+  const bool active = cell_tile<V>(g, R, j0, ra, rb);
   double acc[kIfacePart] = {0.0, 0.0};
   int ndeg = 0;   // the lane's degenerate cells (an integer until the lanes are folded: one register, the same value)
   if (active) {

@@ -4,7 +4,7 @@
 // reference line citations, expression order, one wave = 64*V columns marching along i).
 //
 // Extension, not part of the reference (include/vof2d.h, vof_set_scene).  All geometry is in doubles whatever the
-// field type; every product below goes through fr_mul (kernels/frames.h), whose result no contraction reaches, so the FMA build
+// field type; every product below goes through mul_rounded (kernels/cells.h), whose result no contraction reaches, so the FMA build
 // gives the same bytes.  A NumPy restatement follows it term for term (tests/_scene_np.py).
 //
 //   the cell    (i, j) covers [(i-1) dx, i dx] x [(j-1) dy, j dy] (find_area, 2dvof.py:105-106); a ghost cell is a cell like any
@@ -62,7 +62,7 @@
 //              roundings at |lx| = L, |ly| = M, bounds it: all in if Q(L1, M1) <= t3*t3, all out if Q(L0, M0) > t3*t3
 // Lanes that decide wait for the lanes of their wave that sample; whole waves inside or outside a shape -- most of them -- skip it.
 #pragma once
-#include "stats.h"
+#include "cells.h"
 
 namespace vof {
 
@@ -84,7 +84,7 @@ struct SceneGroups {
 // the coordinate of sample `sub` of cell `cell` along an axis of spacing d
 template <int S>
 __device__ __forceinline__ double scene_coord(int cell, int sub, double d) {
-  return fr_mul((double)(cell - 1) + ((double)sub + 0.5) * (1.0 / S), d);
+  return mul_rounded((double)(cell - 1) + ((double)sub + 0.5) * (1.0 / S), d);
 }
 
 // ------------------------------------------------------------------ the shapes: in(), and decide() over the corners (x0 | x1, y0 | y1)
@@ -93,8 +93,8 @@ struct ScBox {
   double cx, cy, hx, hy, c, s;
   __device__ __forceinline__ void local(double xs, double ys, double& lx, double& ly) const {
     const double px = xs - cx, py = ys - cy;
-    lx = fr_mul(px, c) + fr_mul(py, s);
-    ly = fr_mul(py, c) - fr_mul(px, s);
+    lx = mul_rounded(px, c) + mul_rounded(py, s);
+    ly = mul_rounded(py, c) - mul_rounded(px, s);
   }
   __device__ __forceinline__ bool in(double xs, double ys) const {
     double lx, ly;
@@ -127,12 +127,12 @@ struct ScEllipse {
   ScBox f;      // the frame: cx, cy, hx, hy, c, s
   double rhs;   // t3*t3
   __device__ __forceinline__ explicit ScEllipse(const ScBox& b) : f(b) {
-    const double t3 = fr_mul(b.hx, b.hy);
-    rhs = fr_mul(t3, t3);
+    const double t3 = mul_rounded(b.hx, b.hy);
+    rhs = mul_rounded(t3, t3);
   }
   __device__ __forceinline__ double lhs(double lx, double ly) const {
-    const double t1 = fr_mul(lx, f.hy), t2 = fr_mul(ly, f.hx);
-    return fr_mul(t1, t1) + fr_mul(t2, t2);
+    const double t1 = mul_rounded(lx, f.hy), t2 = mul_rounded(ly, f.hx);
+    return mul_rounded(t1, t1) + mul_rounded(t2, t2);
   }
   __device__ __forceinline__ bool in(double xs, double ys) const {
     double lx, ly;
@@ -164,7 +164,7 @@ struct ScEllipse {
 
 struct ScHalfplane {
   double px0, py0, nx, ny;
-  __device__ __forceinline__ double side(double xs, double ys) const { return fr_mul(xs - px0, nx) + fr_mul(ys - py0, ny); }
+  __device__ __forceinline__ double side(double xs, double ys) const { return mul_rounded(xs - px0, nx) + mul_rounded(ys - py0, ny); }
   __device__ __forceinline__ bool in(double xs, double ys) const { return side(xs, ys) <= 0.0; }
   __device__ __forceinline__ int decide(double x0, double x1, double y0, double y1) const {
     const double v[4] = {side(x0, y0), side(x1, y0), side(x0, y1), side(x1, y1)};
@@ -181,9 +181,9 @@ struct ScHalfplane {
 struct ScTriangle {
   double x0, y0, x1, y1, x2, y2;
   __device__ __forceinline__ void edges(double xs, double ys, double (&e)[3]) const {
-    e[0] = fr_mul(x1 - x0, ys - y0) - fr_mul(y1 - y0, xs - x0);
-    e[1] = fr_mul(x2 - x1, ys - y1) - fr_mul(y2 - y1, xs - x1);
-    e[2] = fr_mul(x0 - x2, ys - y2) - fr_mul(y0 - y2, xs - x2);
+    e[0] = mul_rounded(x1 - x0, ys - y0) - mul_rounded(y1 - y0, xs - x0);
+    e[1] = mul_rounded(x2 - x1, ys - y1) - mul_rounded(y2 - y1, xs - x1);
+    e[2] = mul_rounded(x0 - x2, ys - y2) - mul_rounded(y0 - y2, xs - x2);
   }
   __device__ __forceinline__ bool in(double xs, double ys) const {
     double e[3];
@@ -283,8 +283,8 @@ __global__ __launch_bounds__(256) void k_scene(Geom g, T* __restrict__ F, T* __r
     if (painted) {
       const size_t o = at(g, i, j);
       double acc = (double)n_liq;
-      if (n_keep) acc += fr_mul((double)n_keep, (double)F[o]);
-      const T val = (T)fr_mul(acc, 1.0 / TOTAL);
+      if (n_keep) acc += mul_rounded((double)n_keep, (double)F[o]);
+      const T val = (T)mul_rounded(acc, 1.0 / TOTAL);
       F[o] = val;
       F2[o] = val;
     }

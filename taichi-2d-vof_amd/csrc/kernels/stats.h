@@ -1,4 +1,4 @@
-// kernels/stats.h -- per-cell statistics over a run (k_stats, k_stats_fill, k_stats_summary, k_stats_finish): running sums of F, u, v and their products, envelopes, wet time, arrival step
+// kernels/stats.h -- per-cell statistics over a run (k_stats, k_stats_fill, k_stats_summary, kStatsRow): running sums of F, u, v and their products, envelopes, wet time, arrival step
 //
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
@@ -8,14 +8,14 @@
 // wave tiles (runtime/carve.h, stats_pitch), so that the V columns of a lane are one aligned vector of V doubles in every plane and
 // no lane's vector leaves its row.  One sample is one pass of k_stats over F, u, v on the cells i in [g.ilo, g.ihi], j in [1, ny]:
 // every operand converted to double on load; then, per cell, in this order (tests/_stats_np.py restates it term for term):
-//   f  = F[i,j]    Fc = fmin(fmax(f, 0), 1)    uc = (u[i,j] + u[i+1,j]) * 0.5    vc = (v[i,j] + v[i,j+1]) * 0.5     (Fc, uc, vc of kernels/diag.h)
+//   f  = F[i,j]    Fc = fmin(fmax(f, 0), 1)    uc = (u[i,j] + u[i+1,j]) * 0.5    vc = (v[i,j] + v[i,j+1]) * 0.5     (clamp01, face_mean of kernels/cells.h)
 //   SUM_F += Fc   SUM_F2 += Fc * Fc   SUM_U += uc   SUM_V += vc   SUM_UU += uc * uc   SUM_VV += vc * vc   SUM_UV += uc * vc
 //   SUM_FU += Fc * uc   SUM_FV += Fc * vc                                                                      (group MOMENTS)
 //   s2 = uc * uc + vc * vc    MAX_SPEED2 = diag_max(MAX_SPEED2, s2)    MAX_F = diag_max(MAX_F, Fc)
 //   wet = (Fc >= level)    WET += wet ? 1.0 : 0.0    if (wet && ARRIVAL < 0) ARRIVAL = (double)istep                   (group ENVELOPE)
 // The plain clamp takes a NaN F to Fc = 0 (fmax returns its other operand), as in k_diag: such a cell is dry and its F sums stay finite; a
 // NaN u or v makes the sums it enters NaN and, by diag_max (a NaN operand counts as +inf), MAX_SPEED2 = +inf.  Every product is rounded
-// on its own in either build: it passes through fr_mul of kernels/frames.h, which no contraction reaches.
+// on its own in either build: it passes through mul_rounded of kernels/cells.h, which no contraction reaches.
 //
 // Each cell's accumulation is a sequential chain over the samples: no order of lanes, waves or blocks enters a plane, so the bits
 // depend on the samples alone.  Traffic per sample and cell: F, v once and u once (row i + 1 of one iteration is row i of the next),
@@ -25,7 +25,7 @@
 // planes of a sample are many times the last-level cache), and the field and plane loads of TWO rows are issued before the first of
 // them is computed (650 us against 687 with one row, at 251 VGPRs against 127).
 #pragma once
-#include "frames.h"
+#include "cells.h"
 
 namespace vof {
 
@@ -80,21 +80,20 @@ __device__ __forceinline__ void st_rows(const T* __restrict__ F, const T* __rest
   for (int n = 0; n < N; ++n) {
 #pragma unroll
     for (int q = 0; q < V; ++q) {
-      const double fd = (double)f[n][q], w = (double)(n == 0 ? uw[q] : ue[n > 0 ? n - 1 : 0][q]), e = (double)ue[n][q];
-      const double s = (double)vr[n].c[q], nn = (double)right_of(vr[n], q);
-      const double Fc = __builtin_fmin(__builtin_fmax(fd, 0.0), 1.0);
-      const double uc = (w + e) * 0.5, vc = (s + nn) * 0.5;
-      const double uu = fr_mul(uc, uc), vv = fr_mul(vc, vc);
+      const Cell c = cell_at<T, V>(q, f[n], n == 0 ? uw : ue[n > 0 ? n - 1 : 0], ue[n], vr[n]);
+      const double Fc = clamp01(c.f);
+      const double uc = face_mean(c.w, c.e), vc = face_mean(c.s, c.n);
+      const double uu = mul_rounded(uc, uc), vv = mul_rounded(vc, vc);
       if constexpr ((MASK & STM_MOMENTS) != 0) {
         m[n][ST_SUM_F][q] += Fc;
-        m[n][ST_SUM_F2][q] += fr_mul(Fc, Fc);
+        m[n][ST_SUM_F2][q] += mul_rounded(Fc, Fc);
         m[n][ST_SUM_U][q] += uc;
         m[n][ST_SUM_V][q] += vc;
         m[n][ST_SUM_UU][q] += uu;
         m[n][ST_SUM_VV][q] += vv;
-        m[n][ST_SUM_UV][q] += fr_mul(uc, vc);
-        m[n][ST_SUM_FU][q] += fr_mul(Fc, uc);
-        m[n][ST_SUM_FV][q] += fr_mul(Fc, vc);
+        m[n][ST_SUM_UV][q] += mul_rounded(uc, vc);
+        m[n][ST_SUM_FU][q] += mul_rounded(Fc, uc);
+        m[n][ST_SUM_FV][q] += mul_rounded(Fc, vc);
       }
       if constexpr ((MASK & STM_ENVELOPE) != 0) {
         const double s2 = uu + vv;
@@ -123,7 +122,7 @@ __device__ __forceinline__ void st_rows(const T* __restrict__ F, const T* __rest
 }
 
 // ------------------------------------------------------------------ one sample
-// The march of k_diag (cg_tile: chunks of R rows of [g.ilo, g.ihi]); nothing crosses lanes here, so a lane whose first column lies
+// The march of k_diag (cell_tile: chunks of R rows of [g.ilo, g.ihi]); nothing crosses lanes here, so a lane whose first column lies
 // right of ny leaves.  A lane that holds column ny alone (ny odd) carries column ny + 1 along: the pad of the planes' rows.
 template <typename T, int V, int MASK>
 __global__ __launch_bounds__(256) void k_stats(Geom g, const T* __restrict__ F, const T* __restrict__ u, const T* __restrict__ v, int R, StatsPlanes pl,
@@ -132,7 +131,7 @@ __global__ __launch_bounds__(256) void k_stats(Geom g, const T* __restrict__ F, 
   static_assert(MASK >= 1 && MASK <= 3, "at least one group");
   constexpr int U = kStatsRowsInFlight;
   int j0, ra, rb;
-  if (!cg_tile<V>(g, R, j0, ra, rb) || j0 > g.ny) return;
+  if (!cell_tile<V>(g, R, j0, ra, rb) || j0 > g.ny) return;
   const int64_t pitch = g.pitch;
   size_t o = at(g, ra, j0);
   size_t po = (size_t)(ra - 1) * (size_t)pl.pitch + (size_t)(j0 - 1);
@@ -163,7 +162,7 @@ template <int V>
 __global__ __launch_bounds__(256) void k_stats_summary(Geom g, const double* __restrict__ arrival, const double* __restrict__ speed2, long long ppitch, int R,
                                                         double* __restrict__ part) {
   int j0, ra, rb;
-  const bool active = cg_tile<V>(g, R, j0, ra, rb);
+  const bool active = cell_tile<V>(g, R, j0, ra, rb);
   double acc[kStatsPart] = {0.0, 0.0};
   if (active) {
     size_t po = (size_t)(ra - 1) * (size_t)ppitch + (size_t)(j0 - 1);
@@ -182,12 +181,6 @@ __global__ __launch_bounds__(256) void k_stats_summary(Geom g, const double* __r
   }
   block_publish<1, 1>(acc, part);
 }
-// ONE block of 256 threads, the shape of k_diag_finish: out[0] = EVER_WET, out[1] = MAX_SPEED2
-__global__ __launch_bounds__(256) void k_stats_finish(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
-  __shared__ double red[256][kStatsPart];
-  const double init[kStatsPart] = {0.0, 0.0};
-  fold_partials<256, 1, 1>(part, nblocks, init, red);
-  if (threadIdx.x < kStatsPart) out[threadIdx.x] = red[0][threadIdx.x];
-}
+constexpr RowMap<1, 1> kStatsRow = {kStatsPart, {{ROW_VALUE, 0}, {ROW_VALUE, 1}}, {0.0, 0.0}};   // k_row_finish (kernels/cells.h) folds them into two doubles: EVER_WET, MAX_SPEED2
 
 }  // namespace vof

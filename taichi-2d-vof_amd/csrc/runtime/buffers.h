@@ -47,8 +47,10 @@ struct DevBuf {
   }
 };
 
+struct RowBufs { DevBuf part, rows; };   // a verb that reduces the reported cells to rows (runtime/diag_reduce.h): one partial per block of its pass; the rows recorded on the device
+
 // Every work buffer of a handle: allocated by the first call that needs it (the first two: vof_create), kept until
-// vof_destroy.  Nothing but DevBufs, so that they are released as one flat range: one added here is released too.
+// vof_destroy.  Nothing but DevBufs (a RowBufs is two), so that they are released as one flat range: one added here is released too.
 struct WorkBufs {
   DevBuf courant;      // device counters: [0] courant, [1] max|p_new - p| bits, [2] max|p_new| bits (residual solve), [3] exact-zero cells of F
   DevBuf tbmask;       // work plan of k_jacobi_tb (TbPlan): 2 x TB_BANDS mask words, then the plan (1 + waves entries)
@@ -56,8 +58,7 @@ struct WorkBufs {
   DevBuf cg_part;      // ... one partial per block (kCgPart doubles), then the CG_NSCAL device scalars
   DevBuf mg_arena;     // vof_solve_p_mg (MgCarve): the levels below the grid, the work arrays and scalars of the coarsest-level solve
   DevBuf mg_rec;       // vof_step_mg: the residual record (kernels/mg.h, MGR_*)
-  DevBuf diag_part;    // vof_diagnostics / vof_step_diag (runtime/diag_reduce.h): one partial per block of k_diag
-  DevBuf diag_rows;    // ... the rows recorded on the device, VOF_DIAG_N doubles each, grown on demand
+  RowBufs diag;        // vof_diagnostics / vof_step_diag (runtime/diag_reduce.h): the partials of k_diag, rows of VOF_DIAG_N doubles
   DevBuf iface_work;   // vof_interface (runtime/interface.h, IfaceCarve): the segment counts, turned into offsets in place; the partials; the summary
   DevBuf iface_rows;   // ... the segments, VOF_IFACE_N doubles each, grown on demand
   DevBuf blob_work;    // vof_blobs (runtime/blobs.h, BlobCarve): what the geometry fixes
@@ -74,8 +75,7 @@ struct WorkBufs {
   DevBuf gauge_rows;   // ... the rows of vof_gauges_get (VOF_GAUGE_N doubles each), grown on demand
   DevBuf gauge_recs;   // ... the records vof_step_gauges takes, grown on demand
   DevBuf dye;          // vof_dye_* (runtime/dye.h): the dye and its twin, two arrays in the fields' layout -- state, not scratch: replaced by vof_dye_set alone
-  DevBuf dye_part;     // ... one partial per block of k_dye_stats
-  DevBuf dye_rows;     // ... the rows recorded on the device, VOF_DYE_N doubles each, grown on demand
+  RowBufs dye_stats;   // ... the partials of k_dye_stats, rows of VOF_DYE_N doubles
   DevBuf frame_work;   // vof_frame (runtime/frames.h, FrameCarve): the column partials, the means of F, the words; the means, the summary, the picture
   DevBuf frame_lut;    // ... the colour table, 258 x 3 bytes -- state, not scratch: replaced by vof_frame_set_lut alone
   DevBuf frame_recs;   // ... the pictures vof_step_frames records, their summaries behind them, grown on demand
@@ -88,6 +88,6 @@ struct WorkBufs {
   DevBuf* end() { return begin() + sizeof(WorkBufs) / sizeof(DevBuf); }
   void release() { for (DevBuf* b = begin(); b != end(); ++b) b->release(); }
 };
-static_assert(sizeof(WorkBufs) % sizeof(DevBuf) == 0, "WorkBufs is walked as one array");
+static_assert(sizeof(RowBufs) == 2 * sizeof(DevBuf) && sizeof(WorkBufs) % sizeof(DevBuf) == 0, "WorkBufs is walked as one array");
 
 }  // namespace

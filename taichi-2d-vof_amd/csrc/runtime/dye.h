@@ -1,5 +1,5 @@
 // runtime/dye.h -- vof_dye_set / _get / _advance / _stats and vof_step_dye: the handle's dye arrays, the launches of k_dye (or
-// the two sweeps), k_dye_stats and k_dye_stats_finish, the stepping loop that moves the dye behind every step and records rows
+// the two sweeps), k_dye_stats, the stepping loop that moves the dye behind every step and records rows
 //
 // Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
@@ -83,28 +83,15 @@ int dye_advance(vof2d_ctx* h) {
   return ensure_ok(h);
 }
 
-// ---- the statistics: the partials buffer (once) and room for `rows` rows on the device, before anything is enqueued
-int dye_stats_prepare(vof2d_ctx* h, int64_t rows) {
-  const size_t part = (size_t)reported(h).blocks(diag_chunk(h)) * kDyePart + 1;
-  if (const int rc = h->buf.dye_part.reserve(h, part * sizeof(double), "vof_dye_stats: no memory for the reduction buffer")) return rc;
-  return h->buf.dye_rows.reserve(h, (size_t)(rows < 1 ? 1 : rows) * DY_N * sizeof(double), "vof_step_dye: no memory for the rows");
-}
-template <typename T>
-void dye_stats_launch(vof2d_ctx* h, int64_t slot) {
-  constexpr int V = VecWidth<T>::V;
-  const Reported rep = reported(h);
-  const unsigned nb = rep.blocks(diag_chunk(h));
-  double* const part = h->buf.dye_part.as<double>();
-  if (nb)
-    launch(h, kOther, k_dye_stats<T, V>, dim3(nb), 0, rep.g, (const T*)dye_array<T>(h, h->dye_cur), (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fU),
-           (const T*)F_<T>(h, fV), diag_chunk(h), part);
-  launch(h, kOther, k_dye_stats_finish, dim3(1), 0, (const double*)part, (int)nb, h->buf.dye_rows.as<double>() + slot * DY_N, (double)h->istep, (double)rep.cells());
-}
-// One row of the dye and the fields as vof_get_field would return them now, into slot `slot` of the device rows.  Enqueues only.
+// ---- the statistics: one row of the dye and the fields on the reduced-row path of runtime/diag_reduce.h
+constexpr ReducedVerb<kDyeSums, kDyePart - kDyeSums> kDyeVerb = {&WorkBufs::dye_stats, kDyeRow, "vof_dye_stats: no memory for the reduction buffer",
+                                                                 "vof_step_dye: no memory for the rows"};
 int dye_stats_enqueue(vof2d_ctx* h, int64_t slot) {
-  settle_ghosts(h);
-  DISPATCH_T(h, dye_stats_launch<double>(h, slot), dye_stats_launch<float>(h, slot));
-  return ensure_ok(h);
+  return reduced_enqueue(h, kDyeVerb, slot, [&](auto t, const Geom& g, unsigned nb, int R, double* part) {
+    using T = decltype(t);
+    launch(h, kOther, k_dye_stats<T, VecWidth<T>::V>, dim3(nb), 0, g, (const T*)dye_array<T>(h, h->dye_cur), (const T*)F_<T>(h, fF), (const T*)F_<T>(h, fU),
+           (const T*)F_<T>(h, fV), R, part);
+  });
 }
 
 // step_groups_n (runtime/step.h) in groups of ONE step (the dye needs u, v of every step in memory, so no batch graph) with
@@ -112,13 +99,13 @@ int dye_stats_enqueue(vof2d_ctx* h, int64_t slot) {
 int step_dye_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int criterion, double* out, int64_t* rows_written) {
   const int64_t rows = every > 0 ? nsteps / every : 0;
   int rc;
-  if (rows > 0 && (rc = dye_stats_prepare(h, rows))) return rc;
+  if (rows > 0 && (rc = reduced_prepare(h, kDyeVerb, rows))) return rc;
   rc = step_groups_n(h, nsteps, 1, cycles, criterion, [&](int64_t s) {
     if (const int rc = dye_advance(h)) return rc;
     return every > 0 && (s + 1) % every == 0 ? dye_stats_enqueue(h, (s + 1) / every - 1) : VOF_OK;
   });
   if (rc) return rc;
-  if (rows > 0 && (rc = read_back(h, out, h->buf.dye_rows.p, (size_t)rows * DY_N * sizeof(double)))) return rc;
+  if (rows > 0 && (rc = read_back(h, out, h->buf.dye_stats.rows.p, (size_t)rows * DY_N * sizeof(double)))) return rc;
   if (rows_written) *rows_written = rows;
   return VOF_OK;
 }

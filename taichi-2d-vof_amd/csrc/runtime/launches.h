@@ -457,7 +457,7 @@ struct L {
     int R1, R2; unsigned n1, n2;
   };
   static CgGrid cg_grid(vof2d_ctx* h, const Geom& g, const Consts<T>& c, T* e, const T* f, void* const (&w)[4], double* sc) {
-    const int R1 = pick_rows(h, g.ntj), rows = g.ihi - g.ilo + 1;   // (the rows cg_tile cuts into chunks)
+    const int R1 = pick_rows(h, g.ntj), rows = g.ihi - g.ilo + 1;   // (the rows cell_tile cuts into chunks)
     return {g, c, e, f, w, sc, R1, 2 * R1, blocks_rows(rows, g.ntj, R1), blocks_rows(rows, g.ntj, 2 * R1)};
   }
   static CgGrid cg_own(vof2d_ctx* h) { return cg_grid(h, h->g, C(h), F_<T>(h, fP), (const T*)F_<T>(h, fRHS), h->cg_fld, h->cg_sc); }

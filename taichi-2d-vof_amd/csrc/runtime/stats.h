@@ -1,5 +1,5 @@
 // runtime/stats.h -- vof_stats_begin / _sample / _get / _summary and vof_step_stats: the handle's accumulator planes, the launches of
-// k_stats, k_stats_fill, k_stats_summary and k_stats_finish, the stepping loop that takes a sample behind every group of steps
+// k_stats, k_stats_fill, k_stats_summary and k_row_finish, the stepping loop that takes a sample behind every group of steps
 //
 // Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
@@ -101,7 +101,7 @@ int stats_summary(vof2d_ctx* h, double* out) {
     if (pl.blocks)
       launch(h, kOther, k_stats_summary<2>, dim3(pl.blocks), 0, pl.rep.g, (const double*)w.as<double>(pl.at.plane[ST_ARRIVAL]),
              (const double*)w.as<double>(pl.at.plane[ST_MAX_SPEED2]), (long long)pl.pitch, diag_chunk(h), part);
-    launch(h, kOther, k_stats_finish, dim3(1), 0, (const double*)part, (int)pl.blocks, w.as<double>(pl.at.sum));
+    launch(h, kOther, k_row_finish<1, 1>, dim3(1), 0, (const double*)part, (int)pl.blocks, w.as<double>(pl.at.sum), 0.0, 0.0, kStatsRow);
     if (const int rc = ensure_ok(h)) return rc;
     if (const int rc = read_back(h, red, w.as<double>(pl.at.sum), sizeof(red))) return rc;
   }

@@ -449,10 +449,10 @@ int vof_step_mg(vof2d_handle h, int64_t nsteps, int32_t cycles, int32_t criterio
 // ---- diagnostics on the device (kernels/diag.h, runtime/diag_reduce.h)
 int vof_diagnostics(vof2d_handle h, double* out) {
   if (!h || !out) return VOF_EINVAL;
-  int rc = diag_prepare(h, 1);
+  int rc = reduced_prepare(h, kDiagVerb, 1);
   if (rc) return rc;
   if ((rc = diag_enqueue(h, 0))) return rc;
-  return read_back(h, out, h->buf.diag_rows.p, VOF_DIAG_N * sizeof(double));
+  return read_back(h, out, h->buf.diag.rows.p, VOF_DIAG_N * sizeof(double));
 }
 int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
                   int64_t* rows_written) {
@@ -585,9 +585,9 @@ int vof_dye_stats(vof2d_handle h, double* out) {
   if (!h || !out) return VOF_EINVAL;
   int rc = check_dye_allowed(h, true);
   if (rc) return rc;
-  if ((rc = dye_stats_prepare(h, 1))) return rc;
+  if ((rc = reduced_prepare(h, kDyeVerb, 1))) return rc;
   if ((rc = dye_stats_enqueue(h, 0))) return rc;
-  return read_back(h, out, h->buf.dye_rows.p, VOF_DYE_N * sizeof(double));
+  return read_back(h, out, h->buf.dye_stats.rows.p, VOF_DYE_N * sizeof(double));
 }
 int vof_step_dye(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
                  int64_t* rows_written) {

@@ -17,17 +17,18 @@
 //   jacobi_pair.h  k_jacobi_pair   (two k_jacobi_tb launches as one: pairs of waves, result and rhs rows through LDS)
 //   transport.h  k_fct_x, k_fct_y, k_transport   (update_uv + solve_VOF_rudman + post_process_f)
 //   fused_tm.h   k_tm   (k_transport of one step + k_momentum of the next, rows handed over through LDS)
-//   reduce.h     block_publish, fold_partials   (the fixed-order reduction of the four families below; no kernel of its own)
+//   reduce.h     block_publish, fold_partials   (the fixed-order reduction of the families below; no kernel of its own)
+//   cells.h      cell_tile, mul_rounded, Cell, reduced_rows, k_row_finish   (what the extension kernels share: the tile of the reported cells, the product no contraction reaches, a cell's operands, the pass that ends in one partial per block and the one block that turns the partials into a row)
 //   cg.h         k_cg_apply, k_cg_update, k_cg_residual   (extension: conjugate gradients on the pressure equation)
 //   mg.h         k_mg_smooth, k_mg_restrict, k_mg_prolong, k_mg_coarse_block, k_mg_step_record  (extension: geometric multigrid on the same equation)
-//   diag.h       k_diag, k_diag_finish   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
+//   diag.h       k_diag   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
 //   interface.h  k_iface, k_iface_scan   (extension: the interface as PLIC segments, counted, scanned and emitted in (i, j) order)
 //   blobs.h      k_blob_init, k_blob_merge, k_blob_flatten, k_blob_number, k_blob_label, k_blob_stats, k_blob_summary, k_blob_plan, k_blob_sums, k_blob_rows   (extension: droplets and bubbles labelled by union-find, numbered by first cell, measured in a fixed order)
 //   tracers.h    k_tracer_advance, k_tracer_sample, k_tracer_finish   (extension: passive particles, one per lane: bilinear gather on the staggered grid, midpoint rule, walls)
 //   depths.h     k_depths, k_depths_fold, k_depths_finish, k_gauge_sample   (extension: both marginals of F, the top of the liquid per row and the front in one pass over F; fixed sensors that sample u, v, F, p and read them)
-//   dye.h        k_dye, k_dye_stats, k_dye_stats_finish   (extension: a marker field moved by both FCT sweeps in one pass over C, u, v; its sums and extrema in one fixed-order pass)
+//   dye.h        k_dye, k_dye_stats   (extension: a marker field moved by both FCT sweeps in one pass over C, u, v; its sums and extrema in one fixed-order pass)
 //   frames.h     k_frame_cols, k_frame_fold, k_frame_paint   (extension: a colour-mapped picture of F, u, v, the speed, p, the vorticity or the dye: box averages in a fixed order, a 256-entry colour table, the interface marked on top)
-//   stats.h      k_stats, k_stats_fill, k_stats_summary, k_stats_finish   (extension: per-cell running sums of F, u, v and their products, envelopes, wet time and arrival step over a run: one streaming pass per sample over the fields and planes of doubles)
+//   stats.h      k_stats, k_stats_fill, k_stats_summary   (extension: per-cell running sums of F, u, v and their products, envelopes, wet time and arrival step over a run: one streaming pass per sample over the fields and planes of doubles)
 //   scene.h      k_scene   (extension: an initial state painted from an ordered list of boxes, ellipses, half-planes and triangles, S x S samples a cell as bit masks in registers)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
@@ -40,6 +41,7 @@
 #include "kernels/transport.h"
 #include "kernels/fused_tm.h"
 #include "kernels/reduce.h"
+#include "kernels/cells.h"
 #include "kernels/cg.h"
 #include "kernels/mg.h"
 #include "kernels/diag.h"

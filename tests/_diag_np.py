@@ -72,7 +72,7 @@ def bound_of(t):
 def check(raw, terms, extrema, cells, istep=None, ctx="", say=None, R=None):
     """Hold a raw row (dict keyed by vof2d.diag.NAMES) to the restatement; every figure goes through `say` first.
     R: the rows per wave chunk of the k_diag launch (diag_chunk_rows of tests/_interface_np.py); with it every sum must also
-    equal the fixed-order sum of its terms (k_diag_finish folds with 256 threads)."""
+    equal the fixed-order sum of its terms (k_row_finish folds with 256 threads)."""
     msgs = []
     for k in SUMS:
         t = terms[k].ravel()

@@ -6,7 +6,7 @@
    tests/_diag_np.py (n 2^-52 fsum|t|: any order of summing n doubles errs by at most (n - 1) 2^-53 sum|t| to first order;
    a factor of two for the higher-order terms) and -- where the caller names the chunk length R of the launch -- held bit
    for bit to the order of tests/_reduce_np.py: a lane holds columns 1 + 128 t + 2 l, + 1 of tile t and adds its cells
-   row by row, column by column; k_dye_stats_finish folds with 256 threads.  Extrema, CELLS and ISTEP are compared with ==.
+   row by row, column by column; k_row_finish folds with 256 threads.  Extrema, CELLS and ISTEP are compared with ==.
 
 2. The twin oracle state that judges a transported dye: a NumPy oracle state (oracle/vof_oracle_np.py) whose F is the
    dye, whose u, v and istep are refreshed from the flow before every advance, and which goes through

@@ -49,7 +49,7 @@ static void check_frame(int nx, int ny, int bx, int by) {
   CHECK(f.K == K && f.R == K * ex && f.R % ex == 0 && f.chunks == (f.pw + K - 1) / K, CTX);
   CHECK((long)(f.chunks - 1) * f.R < nx && (long)f.chunks * f.R >= nx, CTX);             // the last chunk has a row, every row a chunk
   CHECK(f.cols_blocks == (unsigned)(((long)f.chunks * ntj + 3) / 4) && (long)f.cols_blocks * 4 >= (long)f.chunks * ntj, CTX);
-  // a wave past the last chunk starts past nx: it returns (cg_tile of kernels/cg.h)
+  // a wave past the last chunk starts past nx: it returns (cell_tile of kernels/cells.h)
   CHECK(1 + (long)f.chunks * f.R > nx, CTX);
   // ---- what k_frame_cols indexes: the pixel row of a chunk's first and last row, the last lane's vector in the padded row
   for (int ch = 0; ch < f.chunks; ch += (f.chunks > 64 ? f.chunks / 7 + 1 : 1)) {

@@ -68,7 +68,7 @@ def test_small_and_rectangular_f64(hip_api, nx, ny, ic, kw):
 
 def test_more_partials_than_folding_threads_f64(hip_api):
     """1100 x 130: the rule gives 2-row chunks, 550 chunks x 2 tiles = 1100 waves = 275 blocks, so threads 0 .. 18 of
-    k_diag_finish fold two partials each; the second tile is ragged (2 of 128 columns).  Sums and extrema with ==."""
+    k_row_finish fold two partials each; the second tile is ragged (2 of 128 columns).  Sums and extrema with ==."""
     nx, ny = 1100, 130
     R = inp.diag_chunk_rows(nx, ny)
     assert R == 2 and rnp.blocks(nx, ny, R) == 275 > 256
@@ -239,6 +239,16 @@ def test_step_diag_on_a_strip_is_refused(hip_api):
     assert s.istep == 0 and all(np.array_equal(s.get(n), before[n]) for n in FIELDS)
     raw = hold_to_restatement(s, "strip rows 0..80 owning 1..60")          # vof_diagnostics works on it
     assert raw["CELLS"] == 60 * 128
+
+
+def test_a_strip_that_owns_nothing(hip_api):
+    """No cell is reported: the pass is not launched and k_row_finish alone forms the row, from the `init` of kDiagRow."""
+    s = engine(hip_api, 64, 64, "f64", "f32", ic=1, rows=(0, 40), own=(2, 1))
+    raw = s.diagnostics()
+    print(raw)
+    want = {k: 0.0 for k in diag.NAMES}
+    want.update(ISTEP=0, CELLS=0, MIN_F=math.inf, MAX_F=-math.inf)
+    assert raw == want
 
 
 # ---------------------------------------------------------------------------- a NaN is reported, not hidden
