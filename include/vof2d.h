@@ -247,6 +247,11 @@ int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycl
  *               alpha = sqrt(2 n1 n2 Fm) if 2 n2 Fm < n1, else n2 Fm + n1 / 2; alpha -> 1 - alpha if F > 0.5; liquid is a xi + b eta < alpha.
  *               One end lies on xi = 0 if b > 0 and alpha <= b, else on eta = 1; the other on eta = 0 if a > 0 and alpha <= a, else on
  *               xi = 1; xi -> 1 - xi if mxsum < 0, eta -> 1 - eta if mysum < 0; x = (i - 1 + xi) dx, y = (j - 1 + eta) dy
+ *   ties        every comparison above is the one written: eps < F and F < 1 - eps are strict (F == eps and F == 1 - eps, the double
+ *               1.0 - eps, are not mixed), 2 n2 Fm < n1 is strict, alpha <= b and alpha <= a take the tie, mxsum < 0 and mysum < 0 leave a
+ *               zero (of either sign) unmirrored, n1 = n2 where a == b and Fm = 0.5 where F == 0.5.  At a == b, F == 0.5 (Fm),
+ *               alpha == a, alpha == b, mxsum == 0 and mysum == 0 both branches give the same row; at F == 0.5 (alpha -> 1 - alpha) and at
+ *               2 n2 Fm == n1 they may differ in the last bits, and the written one holds
  *   a row       VOF_IFACE_N doubles: I, J (global cell indices), (X0, Y0) -> (X1, Y1) ordered so that the liquid lies to the LEFT,
  *               (NX, NY) = (mxsum, mysum) / its Euclidean norm: the unit normal in physical space, liquid -> gas
  * The expression order is stated in csrc/kernels/interface.h.  Rows come in ascending (i, j) order, i first.  At most cap_rows rows are
