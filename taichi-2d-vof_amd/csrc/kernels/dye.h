@@ -7,6 +7,7 @@
 // function in the layout of F, moved by solve_VOF_rudman (2dvof.py:312-318) + post_process_f (:452-455) with C in the
 // place of F on the FINAL u, v of a step: the operator is transport.h's, cell function by cell function.
 #pragma once
+#include "march.h"
 #include "transport.h"
 #include "cells.h"
 
@@ -35,41 +36,25 @@ namespace vof {
 template <typename T, int V, bool YFIRST>
 __global__ __launch_bounds__(256) void k_dye(Geom g, Consts<T> c, const T* __restrict__ C, T* __restrict__ Cn, int nty,
                                               const T* __restrict__ u, const T* __restrict__ v, int R) {
-  constexpr int W = TransportGeom<V>::W, HT = TransportGeom<V>::H, STRIDE = TransportGeom<V>::STRIDE;
-  static_assert(HT >= 4 && HT % V == 0, "the y sweep's +-3 dependency is resolved across lanes");
-  const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int tj = wave % nty, ch = wave / nty;
-  const int c0 = 1 - HT + tj * STRIDE;
-  const int j0 = c0 + lane * V;
+  typedef TransportGeom<V> TG;
+  static_assert(TG::H >= 4 && TG::H % V == 0, "the y sweep's +-3 dependency is resolved across lanes");
   const int ilo = g.ilo, ihi = g.ihi, ny = g.ny;
+  int tj, ch, j0, jlo, jhi;
+  tile_decode<TG, V>(wave_index(), nty, threadIdx.x & 63, ny, tj, ch, j0, jlo, jhi);
   const int ra = ilo + ch * R;
   if (ra > ihi) return;  // padding waves of the last block (wave-uniform)
   const int rb = ra + R - 1 < ihi ? ra + R - 1 : ihi;
-  const int jlo = c0 + HT > 1 ? c0 + HT : 1;
-  const int jhi = c0 + W - HT - 1 < ny ? c0 + W - HT - 1 : ny;
-  auto rowptr = [&](const T* base, int r) {
-    const int rc = r < g.row_lo ? g.row_lo : (r > g.row_hi ? g.row_hi : r);
-    return base + at(g, rc, j0);
-  };
-  auto all_zero = [](const T (&x)[V]) {
-    bool rz = true;
-#pragma unroll
-    for (int q = 0; q < V; ++q) rz = rz && x[q] == (T)0;
-    return (bool)__all(rz);
-  };
   auto swept_row = [&](int r) { return r >= ilo && r <= ihi; };   // rows the y sweep produces; the others keep C
   FctXPipe<T, V> pipe;
   {  // the pipeline's first donor row: C[ra - 3], y-swept where the y sweep runs first and produces that row
     T f1[V];
-    load_c<T, V>(f1, rowptr(C, ra - 3));
+    load_c<T, V>(f1, row_ptr(g, C, ra - 3, j0));
     if (YFIRST && swept_row(ra - 3)) {
       T fs[V];
-#pragma unroll
-      for (int q = 0; q < V; ++q) fs[q] = (T)0;   // (what k_fct_y stores for an all-zero segment)
-      if (!all_zero(f1)) {
+      zero_fill(fs);   // (what k_fct_y stores for an all-zero segment)
+      if (!wave_all_zero(f1)) {
         T v0[V];
-        load_s<T, V>(v0, rowptr(v, ra - 3));
+        load_s<T, V>(v0, row_ptr(g, v, ra - 3, j0));
         fct_y_row<T, V, false>(c, j0, ny, f1, v0, fs);
       }
       pipe.init(fs);
@@ -82,11 +67,11 @@ __global__ __launch_bounds__(256) void k_dye(Geom g, Consts<T> c, const T* __res
   auto v_row = [&](int r) { return YFIRST ? r : r - 3; };
   auto v_wanted = [&](int r) { const int rv = v_row(r); return YFIRST ? swept_row(rv) : (rv >= ra && rv <= rb); };
   T Cnx[V], unx[V], vnx[V];
-  load_c<T, V>(Cnx, rowptr(C, ra - 2));
-  load_s<T, V>(unx, rowptr(u, ra - 2));
+  load_c<T, V>(Cnx, row_ptr(g, C, ra - 2, j0));
+  load_s<T, V>(unx, row_ptr(g, u, ra - 2, j0));
 #pragma unroll
-  for (int q = 0; q < V; ++q) vnx[q] = (T)0;
-  if (v_wanted(ra - 2)) load_s<T, V>(vnx, rowptr(v, v_row(ra - 2)));
+  for (int q = 0; q < V; ++q) vnx[q] = (T)0;   // (mirrors zero_fill of march.h)
+  if (v_wanted(ra - 2)) load_s<T, V>(vnx, row_ptr(g, v, v_row(ra - 2), j0));
   for (int r = ra - 2; r <= rb + 3; ++r) {
     T Cr[V], ur[V], vr[V];
 #pragma unroll
@@ -94,13 +79,13 @@ __global__ __launch_bounds__(256) void k_dye(Geom g, Consts<T> c, const T* __res
       Cr[q] = Cnx[q]; ur[q] = unx[q]; vr[q] = vnx[q];
     }
     if (r < rb + 3) {
-      load_c<T, V>(Cnx, rowptr(C, r + 1));
-      load_s<T, V>(unx, rowptr(u, r + 1));
-      if (v_wanted(r + 1)) load_s<T, V>(vnx, rowptr(v, v_row(r + 1)));
+      load_c<T, V>(Cnx, row_ptr(g, C, r + 1, j0));
+      load_s<T, V>(unx, row_ptr(g, u, r + 1, j0));
+      if (v_wanted(r + 1)) load_s<T, V>(vnx, row_ptr(g, v, v_row(r + 1), j0));
     }
     T out[V];
     const int io = r - 3;
-    const bool zr = all_zero(Cr);
+    const bool zr = wave_all_zero(Cr);
     if (YFIRST) {
       T Cp[V];
       if (!swept_row(r) || zr) {
@@ -113,9 +98,8 @@ __global__ __launch_bounds__(256) void k_dye(Geom g, Consts<T> c, const T* __res
     } else {
       T Cp[V];
       pipe.template push<false>(c, r, ilo, ihi, Cr, ur, Cp, zr);   // C'[r - 3]
-#pragma unroll
-      for (int q = 0; q < V; ++q) out[q] = (T)0;
-      if (io >= ra && io <= rb && !all_zero(Cp)) fct_y_row<T, V, true>(c, j0, ny, Cp, vr, out);
+      zero_fill(out);
+      if (io >= ra && io <= rb && !wave_all_zero(Cp)) fct_y_row<T, V, true>(c, j0, ny, Cp, vr, out);
     }
     if (io >= ra && io <= rb) store_s<T, V>(Cn + at(g, io, j0), out, j0, jlo, jhi);
   }

@@ -24,11 +24,13 @@
 // Virtual ghosts (the steady-state fused step) only; on a strip the rows beyond its stored rows are the clamped edge rows (the invalid fringe).
 // The two marches below are k_transport's and k_momentum's row loops with the source / sink of F'', u, v exchanged (LDS
 // instead of memory) and the chunk bounds of the pair.  The arithmetic of a row is ONE source shared with the stand-alone
-// kernels (round 6): MomentumWindow::step (kernels/momentum.h), TransportRow (kernels/transport.h).
+// kernels (round 6): MomentumWindow::step (kernels/momentum.h), TransportWindow::step (kernels/transport.h);
+// the tile columns, the row pointer, the Courant count and the u, v store around them are kernels/march.h's.
 #pragma once
+#include "march.h"
 #include "momentum.h"
 #include "transport.h"
-#include "tm_segments.h"
+#include "row_segments.h"
 
 namespace vof {
 
@@ -71,17 +73,13 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
   // the transport wave is the one the momentum wave waits for: priority 1 (4096^2 fp64: 314 -> 299 us y first, 327 -> 305 x first;
   // the momentum wave instead: 314 / 333).  ABL_PRIO0 of the diagnostic build = without it.
   if constexpr ((ABL & ABL_PRIO0) == 0) __builtin_amdgcn_s_setprio(1);
-  const int j0 = c0 + lane * V;
+  const int j0 = c0 + lane * V;   // (j0, jlo, jhi: mirror tile_columns<TmGeom<V>, V, IN> of march.h)
   const int ilo = g.ilo, ihi = g.ihi, nx = g.nx, ny = g.ny;
   const int jlo = IN ? c0 + HF : (c0 + HF > 1 ? c0 + HF : 1);
   const int jhi = IN ? c0 + W - HF - 1 : (c0 + W - HF - 1 < ny ? c0 + W - HF - 1 : ny);
   const int t_lo = ma - 5, t_hi = mb + 8;   // lockstep steps of the pair
   const int64_t pitch = g.pitch;
-  auto rowptr = [&](const T* base, int r) {
-    if constexpr ((ABL & ABL_FIXED_ROW) != 0) r = ma;
-    const int rc = IN ? r : (r < g.row_lo ? g.row_lo : (r > g.row_hi ? g.row_hi : r));
-    return base + at(g, rc, j0);
-  };
+  auto rowptr = [&](const T* base, int r) { return row_ptr<IN>(g, base, (ABL & ABL_FIXED_ROW) != 0 ? ma : r, j0); };
   const int tra = ma - 3, trb = mb + 3;
   // the register window and the arithmetic of an iteration are k_transport's (TransportWindow, kernels/transport.h): what differs
   // here is where u, v and F'' go -- the pair's ring in LDS (and memory where somebody reads them) -- and the chunk bounds of the pair
@@ -95,7 +93,7 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
       load_s<T, V>(v0, rowptr(vs, tra - 3));
     } else {
 #pragma unroll
-      for (int q = 0; q < V; ++q) v0[q] = (T)0;
+      for (int q = 0; q < V; ++q) v0[q] = (T)0;   // (mirrors zero_fill of march.h)
     }
     win.template init<YFIRST, IN>(c, j0, ny, f1, pr1, v0, swept);
   }
@@ -137,7 +135,7 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
       T out[V];
       const bool own = r >= ma && r <= mb;
       win.template step<YFIRST, IN>(c, r, ilo, ihi, nx, j0, ny, Fr, ur, vr, pr, out, tra, trb, [&](bool urow) {
-        if (own && (IN || (r >= g.own_lo && r <= g.own_hi))) {
+        if (own && (IN || (r >= g.own_lo && r <= g.own_hi))) {   // (mirrors courant_count<IN> of march.h)
 #pragma unroll
           for (int q = 0; q < V; ++q) {
             const int j = j0 + q;
@@ -154,7 +152,7 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
           const int so = own ? (int)((int64_t)(r - g.row_lo) * pitch * (int64_t)sizeof(T)) : 0;
           store_buf_nt<T, V>(Uo + (int64_t)(g.col0 + c0), own ? voff_st : kBufSkip, so, ur);
           store_buf_nt<T, V>(Vo + (int64_t)(g.col0 + c0), own ? voff_st : kBufSkip, so, vr);
-        } else if (STORE_UV && own && !(ABL & ABL_NO_STORE)) {
+        } else if (STORE_UV && own && !(ABL & ABL_NO_STORE)) {   // (mirrors store_uv_row of march.h)
           store_s<T, V>(Uo + at(g, r, j0), ur, j0, jlo, jhi);
           store_s<T, V>(Vo + at(g, r, j0), vr, j0, jlo, jhi == ny ? ny + 1 : jhi);
           if (r == nx) {
@@ -178,7 +176,7 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
     }
     wt_.barrier();
   }
-  if (__any(viol != 0)) {
+  if (__any(viol != 0)) {   // (mirrors courant_publish of march.h)
     unsigned int tot = viol;
 #pragma unroll
     for (int sft = 32; sft > 0; sft >>= 1) tot += __shfl_down(tot, sft, 64);
@@ -198,7 +196,7 @@ __device__ __forceinline__ void tm_momentum_march(const Geom& g, const Consts<T>
     for (int t = t_lo; t <= t_hi; ++t) wt_.barrier();
     return;
   }
-  const int j0 = c0 + lane * V;
+  const int j0 = c0 + lane * V;   // (j0, jlo, jhi: mirror tile_columns<TmGeom<V>, V, IN> of march.h)
   const int ilo = g.ilo, ihi = g.ihi, nx = g.nx, ny = g.ny;
   const int jlo = IN ? c0 + HF : (c0 + HF > 1 ? c0 + HF : 1);
   const int jhi = IN ? c0 + W - HF - 1 : (c0 + W - HF - 1 < ny ? c0 + W - HF - 1 : ny);
@@ -278,11 +276,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void k
                                             const T* __restrict__ us, const T* __restrict__ vs, const T* __restrict__ p,
                                             T* __restrict__ Uo, T* __restrict__ Vo, T* __restrict__ us_out,
                                             T* __restrict__ vs_out, T* __restrict__ rhs,
-                                            unsigned long long* __restrict__ courant, TbPlan tp, TmSegments rows) {
-  // rows: up to four row ranges, each cut in chunks of its own length and handed out in order (tm_segments.h) -- the body and the
+                                            unsigned long long* __restrict__ courant, TbPlan tp, RowSegments rows) {
+  // rows: up to four row ranges, each cut in chunks of its own length and handed out in order (row_segments.h) -- the body and the
   // shorter chunks of a full domain's tail, or the two edge bands of a strip in one launch
-  constexpr int W = TmGeom<V>::W, HF = TmGeom<V>::H, STRIDE = TmGeom<V>::STRIDE;
-  static_assert(HF >= 4 + 3 && HF % V == 0, "momentum's inputs must lie inside the transport march's valid columns");
+  constexpr int W = TmGeom<V>::W;
+  static_assert(TmGeom<V>::H >= 4 + 3 && TmGeom<V>::H % V == 0, "momentum's inputs must lie inside the transport march's valid columns");
   static_assert(sizeof(TbPlanShared) <= sizeof(TmRing<double, 2>) / 2, "the planner block borrows the ring's LDS");
   __shared__ __attribute__((aligned(16))) char smem[sizeof(TmRing<T, V>) > sizeof(TbPlanShared) ? sizeof(TmRing<T, V>) : sizeof(TbPlanShared)];
   const int plan_blocks = tp.masks != nullptr ? 1 : 0;
@@ -303,9 +301,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void k
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // 0: transport, 1: momentum
   const int lane = threadIdx.x & 63;
   const int tj = pair % ntf, ch = pair / ntf;
-  const int c0 = 1 - HF + tj * STRIDE;
+  const int c0 = tile_c0<TmGeom<V>>(tj);
   int ma = 1, mb = 0;
-  if (!tm_chunk_rows_of(rows, ch, ma, mb)) return;   // (block-uniform) both waves leave
+  if (!row_chunk_rows_of(rows, ch, ma, mb)) return;   // (block-uniform) both waves leave
   // interior pair, stated as what the IN marches fold to constants: every row the pair loads, forms or tests (ma - 8 .. mb + 7: the
   // x pipeline's "row strictly inside [ilo, ihi]" tests reach ma - 7 and mb + 6) lies inside the computable rows [ilo, ihi] -- on a
   // full domain [1, nx], on a strip also inside the stored rows, whose addresses the interior marches do not clamp --, every row it

@@ -3,7 +3,7 @@
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
 #pragma once
-#include "common.h"
+#include "march.h"
 #include "plan.h"
 
 namespace vof {
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void k_jacobi_tb(Geom g, Consts<T> c, const T*
   rb = __builtin_amdgcn_readfirstlane(rb);
   if (planned && rb < ra) return;   // an unused wave of the plan
   if (planned && ra < first) ra = first;   // (a launch on part of the rows takes its part of every planned chunk)
-  const int c0 = 1 - H + tj * STRIDE;
+  const int c0 = 1 - H + tj * STRIDE;   // (c0, j0, jlo, jhi: mirror tile_c0 and tile_columns of march.h)
   const int j0 = c0 + lane * V;
   if (ra > last) return;  // wave-uniform
   if (rb > last) rb = last;
@@ -203,10 +203,6 @@ __global__ __launch_bounds__(256) void k_jacobi_tb(Geom g, Consts<T> c, const T*
     yI[q] = (T)1 / apI[q];
     if (SQ && (j < 1 || j > ny)) yI[q] = (T)0;  // out-of-domain columns: every sweep yields the value 0
   }
-  auto rowptr = [&](const T* base, int r) {
-    const int rc = r < g.row_lo ? g.row_lo : (r > g.row_hi ? g.row_hi : r);
-    return base + (size_t)(rc - g.row_lo) * (size_t)pitch + (size_t)(g.col0 + j0);
-  };
 
   // ring[s][k]: input rows of stage s+1 (s = 0: values of p from memory; s > 0: the previous
   // stage's output, as products when SQ).  In the sub-iteration with phase U (t = tb + U):
@@ -234,11 +230,11 @@ __global__ __launch_bounds__(256) void k_jacobi_tb(Geom g, Consts<T> c, const T*
   const int t0 = ra - TS + 2, t1 = rb + TS;
   // phase 0 at t = t0: rows t0-2, t0-1, t0 of p in ring[0][0..2]; rhs row t0-1 in rq slot 0
   // (stage s at phase U reads rhs row t-s -> slot (U+1-s) mod 6)
-  load_c<T, V>(ring[0][0], rowptr(p, t0 - 2));
+  load_c<T, V>(ring[0][0], row_ptr(g, p, t0 - 2, j0));
   {
-    const T* q1 = rowptr(p, t0 - 1);
+    const T* q1 = row_ptr(g, p, t0 - 1, j0);
     load_c<T, V>(ring[0][1], q1);
-    const T* q2 = rowptr(p, t0);
+    const T* q2 = row_ptr(g, p, t0, j0);
     load_c<T, V>(ring[0][2], q2);
     if constexpr (!SQ) {
       sideL[0] = sideR[0] = (T)0;
@@ -248,7 +244,7 @@ __global__ __launch_bounds__(256) void k_jacobi_tb(Geom g, Consts<T> c, const T*
       sideR[2] = q2[V];
     }
   }
-  load_s<T, V>(rq[0], rowptr(rhs, t0 - 1));
+  load_s<T, V>(rq[0], row_ptr(g, rhs, t0 - 1, j0));
 
   const T* const pn_tile = pn + (int64_t)(g.col0 + c0);   // BS: (wave-uniform) the tile's first column of stored row row_lo
   const int voff_st = (j0 >= jlo && j0 + V - 1 <= jhi) ? lane * (int)(V * sizeof(T)) : kBufSkip;
@@ -320,13 +316,13 @@ __global__ __launch_bounds__(256) void k_jacobi_tb(Geom g, Consts<T> c, const T*
       }
       if (s == 1 && (BS || t < t1)) {
         // ring[0][kM] (row t-2) is dead now: prefetch row t+1 into it; rhs row t into the free slot
-        const T* qn = rowptr(p, t + 1);
+        const T* qn = row_ptr(g, p, t + 1, j0);
         load_c<T, V>(ring[0][kM], qn);
         if constexpr (!SQ) {
           sideL[kM] = qn[-1];
           sideR[kM] = qn[V];
         }
-        load_s<T, V>(rq[(U + 1) % 6], rowptr(rhs, t));
+        load_s<T, V>(rq[(U + 1) % 6], row_ptr(g, rhs, t, j0));
       }
     }
     const int io = t - TS;

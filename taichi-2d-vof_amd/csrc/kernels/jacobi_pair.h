@@ -17,6 +17,7 @@
 //     result row t + 1 (written at step t + TS + 1) and rhs row t (written at step t + 1); ring slot = row & 7.
 // Square cells only (the product-carrying pipeline); the caller keeps k_jacobi_tb for everything else.
 #pragma once
+#include "march.h"
 #include "jacobi.h"
 
 namespace vof {
@@ -51,11 +52,9 @@ __device__ __forceinline__ void jacobi_pair_march(const Geom& g, const Consts<T>
   // LDS): it runs at priority 1 -- 4096^2 fp64: 146 -> 135 us per launch inside the front, 149 -> 141 behind it
   // (tools/probes/pair_bound.py; the other way round: 142 / 148).  ABL_PRIO0 of the diagnostic build = without it.
   if constexpr ((ROLE == 0 && !(ABL & ABL_PRIO0)) || (ROLE == 1 && (ABL & ABL_PRIO1))) __builtin_amdgcn_s_setprio(1);
-  constexpr int W = JacobiPairGeom<V, TS>::W, H = JacobiPairGeom<V, TS>::H;
-  const int j0 = c0 + lane * V;
   const int nx = g.nx, ny = g.ny;
-  const int jlo = c0 + H > 1 ? c0 + H : 1;
-  const int jhi = c0 + W - H - 1 < ny ? c0 + W - H - 1 : ny;
+  int j0, jlo, jhi;
+  tile_columns<JacobiPairGeom<V, TS>, V>(c0, lane, ny, j0, jlo, jhi);
   const int64_t pitch = g.pitch;
   // Every stage takes PRODUCTS coef * p, the first one too: a row that arrives (from memory / from the first march) is
   // multiplied once by the coefficient it carries in the equations of all its four neighbours -- dxi2 (= dyi2: square
@@ -71,11 +70,7 @@ __device__ __forceinline__ void jacobi_pair_march(const Geom& g, const Consts<T>
     yI[q] = (T)1 / apI[q];
     if (j < 1 || j > ny) yI[q] = (T)0;  // out-of-domain columns: every sweep yields the value 0
   }
-  auto rowptr = [&](const T* base, int r) {
-    if constexpr ((ABL & ABL_FIXED_ROW) != 0) r = ra;
-    const int rc = r < g.row_lo ? g.row_lo : (r > g.row_hi ? g.row_hi : r);
-    return base + (size_t)(rc - g.row_lo) * (size_t)pitch + (size_t)(g.col0 + j0);
-  };
+  auto rowptr = [&](const T* base, int r) { return row_ptr(g, base, (ABL & ABL_FIXED_ROW) != 0 ? ra : r, j0); };
   auto to_products = [&](T (&row)[V], int r) {
     const bool rowok = r >= 1 && r <= nx;
 #pragma unroll
@@ -264,7 +259,6 @@ template <typename T, int V, int TS, bool BS, int ABL = 0>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void k_jacobi_pair(Geom g, Consts<T> c, const T* __restrict__ p,
                                                      const T* __restrict__ rhs, T* __restrict__ pn, int R, int ntt,
                                                      TbPlan tp, int first, int last) {
-  constexpr int H = JacobiPairGeom<V, TS>::H, STRIDE = JacobiPairGeom<V, TS>::STRIDE;
   __shared__ __attribute__((aligned(16))) JpRing<T, V> lds;
   WaveTimer wt_(WT_JACOBI_PAIR);
   if (last < first) { first = g.ilo; last = g.ihi; }
@@ -294,7 +288,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4))) void k
   if (ra > last) return;
   if (rb > last) rb = last;
   if (rb < ra) return;
-  const int c0 = 1 - H + tj * STRIDE;
+  const int c0 = tile_c0<JacobiPairGeom<V, TS>>(tj);
   if (threadIdx.x == 0) lds.hit = 0;   // (the first barrier comes before the second wave's first sub-iteration, and the first wave's rows are rows again)
   __syncthreads();
   if (role == 0) {

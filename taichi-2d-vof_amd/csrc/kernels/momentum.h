@@ -3,7 +3,7 @@
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
 #pragma once
-#include "common.h"
+#include "march.h"
 #include "plan.h"
 
 namespace vof {
@@ -32,30 +32,6 @@ __device__ __forceinline__ T div_or_zero(T t, T d) {
   T r = t;
   if (t != (T)0) r = t / d;
   return r;
-}
-
-template <typename T>
-__device__ __forceinline__ void normals_cell(const Consts<T>& c, T Fmm, T Fm0, T Fmp, T F0m, T F00, T F0p, T Fpm,
-                                             T Fp0, T Fpp, T& ox, T& oy) {
-  const T cxn = c.nrm_x, cyn = c.nrm_y;
-  T mx1 = cxn * (Fpp + Fp0 - F0p - F00);
-  T my1 = cyn * (Fpp - Fp0 + F0p - F00);
-  T mx2 = cxn * (Fp0 + Fpm - F00 - F0m);
-  T my2 = cyn * (Fp0 - Fpm + F00 - F0m);
-  T mx3 = cxn * (F00 + F0m - Fm0 - Fmm);
-  T my3 = cyn * (F00 - F0m + Fm0 - Fmm);
-  T mx4 = cxn * (F0p + F00 - Fmp - Fm0);
-  T my4 = cyn * (F0p - F00 + Fmp - Fm0);
-  T mxsum = (mx1 + mx2 + mx3 + mx4) / (T)4;
-  T mysum = (my1 + my2 + my3 + my4) / (T)4;
-  if (dabs<T>(mxsum) < c.tiny && dabs<T>(mysum) < c.tiny) {
-    ox = mxsum;
-    oy = mysum;
-  } else {
-    T magnitude = dsqrt<T>(mxsum * mxsum + mysum * mysum);
-    ox = mxsum / magnitude;
-    oy = mysum / magnitude;
-  }
 }
 
 // all V+2 values of a lane's row window are equal
@@ -315,7 +291,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
   WaveTimer wt_(WT_MOMENTUM);
   const int wave = ((int)blockIdx.x - plan_blocks) * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const int tj = wave % ntt, ch = wave / ntt;
+  const int tj = wave % ntt, ch = wave / ntt;   // (from here to jhi: mirrors tile_decode of march.h; c0 is used below)
   const int c0 = 1 - H + tj * STRIDE;
   const int j0 = c0 + lane * V;
   const int ra = first + ch * R;
@@ -328,18 +304,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 #pragma unroll
   for (int q = 0; q < V; ++q) dom[q] = (j0 + q) >= 1 && (j0 + q) <= ny;
   const bool vlo = virt && g.wall_lo, vhi = virt && g.wall_hi;
-  auto rowptr = [&](const T* base, int r) {
-    const int rc = r < g.row_lo ? g.row_lo : (r > g.row_hi ? g.row_hi : r);
-    return base + (size_t)(rc - g.row_lo) * (size_t)g.pitch + (size_t)(g.col0 + j0);
-  };
   // ghost rows 0 / nx+1 of F and v mirror rows 1 / nx (:176-189); u's are stored (u[nx+1] = 0)
   auto mirrow = [&](int r) { return (vlo && r == 0) ? 1 : ((vhi && r == g.nx + 1) ? g.nx : r); };
   const bool edge_cols = virt && (c0 - 1 <= 0 || c0 + W >= ny + 1);   // wave-uniform: the tile holds a ghost column
   // (the ghost columns are mirrored when a row is taken into use, not when it is loaded: the
   // prefetched rows stay in flight for a whole iteration)
-  auto load_F = [&](Row<T, V>& w, int r) { load_row<T, V>(w, rowptr(F, mirrow(r))); };
-  auto load_u = [&](Row<T, V>& w, int r) { load_row<T, V>(w, rowptr(u, r)); };
-  auto load_v = [&](Row<T, V>& w, int r) { load_row<T, V>(w, rowptr(v, mirrow(r))); };
+  auto load_F = [&](Row<T, V>& w, int r) { load_row<T, V>(w, row_ptr(g, F, mirrow(r), j0)); };
+  auto load_u = [&](Row<T, V>& w, int r) { load_row<T, V>(w, row_ptr(g, u, r, j0)); };
+  auto load_v = [&](Row<T, V>& w, int r) { load_row<T, V>(w, row_ptr(g, v, mirrow(r), j0)); };
   // the register window and the arithmetic of an iteration: MomentumWindow (shared with k_tm)
   MomentumWindow<T, V> win;
   win.init(c);

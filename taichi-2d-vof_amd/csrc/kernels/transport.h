@@ -3,7 +3,8 @@
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
 #pragma once
-#include "common.h"
+#include "march.h"
+#include "row_segments.h"
 
 namespace vof {
 
@@ -71,15 +72,6 @@ __device__ __forceinline__ T fct_clamp(T ftd) {
 // F, writes Fn (the twin); the host swaps the two pointers afterwards.
 // Zero-ghost semantics (S5): Ftd, rp, rm outside [ilo, ihi] and cx at face
 // ilo read as 0, exactly what the never-written ghost entries hold.
-// update_uv (2dvof.py:269-280) for one cell, shared by k_correct's fused forms below: the same
-// expressions in the same order.  rho_c / rho_m: density of the cell and of its lower neighbour in
-// the component's direction; pc / pm likewise for p.
-template <typename T>
-__device__ __forceinline__ T corrected_velocity(const Consts<T>& c, T star, T rho_c, T rho_m, T pc, T pm, T di) {
-  const T r = (rho_c + rho_m) * (T)0.5;
-  return star - c.dt / r * (pc - pm) * di;
-}
-
 // fct_y_sweep for one row segment: a wave's 64*V consecutive cells, valid for the inner columns
 // [c0+4, c0+W-5] (the j+-3 dependency is resolved across lanes; tiles overlap by 8 columns)
 // IN: every column the wave holds lies in [2, ny] (an interior tile of a pair kernel): the column tests are constants
@@ -284,7 +276,7 @@ struct TransportWindow {
     // update_uv's r = (rho + rho') / 2 is that density and dt / r the host's correctly rounded dt / rho.
     int cls = 2;
     {
-      bool rz = true, ro = true;
+      bool rz = true, ro = true;   // (rz: mirrors wave_all_zero of march.h -- with the call, here and below, k_transport's y-first form ran 3 % slower)
 #pragma unroll
       for (int q = 0; q < V; ++q) rz = rz && Fr[q] == (T)0;
       if (__all(rz)) {
@@ -384,30 +376,26 @@ __global__ __launch_bounds__(256) void k_fct_x(Geom g, Consts<T> c, const T* __r
   if (!wave_tile<V>(g, rfirst, rlast, R, j0, ra, rb)) return;
   const int ilo = g.ilo, ihi = g.ihi;
   FctXPipe<T, V> pipe;  // face -> Ftd -> rp/rm -> cx -> F' along i
-  auto rowptr = [&](const T* base, int r) {
-    int rc = r < g.row_lo ? g.row_lo : (r > g.row_hi ? g.row_hi : r);
-    return base + at(g, rc, j0);
-  };
   T F1[V];  // F[r-1]: the pipeline's first donor row, and update_uv's i-1 density
-  load_c<T, V>(F1, rowptr(F, ra - 3));
+  load_c<T, V>(F1, row_ptr(g, F, ra - 3, j0));
   pipe.init(F1);
   T Fnx[V], unx[V];  // rows r of F and u (CORR: u*), prefetched one iteration ahead
-  load_c<T, V>(Fnx, rowptr(F, ra - 2));
-  load_c<T, V>(unx, rowptr(CORR ? us : u, ra - 2));
+  load_c<T, V>(Fnx, row_ptr(g, F, ra - 2, j0));
+  load_c<T, V>(unx, row_ptr(g, CORR ? us : u, ra - 2, j0));
   // CORR state: p and rho of row r-1, prefetched p / v* / left neighbours of row r
   T p1[V], rho1[V];
   Row<T, V> pnx;
   T vsnx[V], Flnx = (T)0;
   unsigned int viol = 0;
   if (CORR) {
-    load_c<T, V>(p1, rowptr(p, ra - 3));
+    load_c<T, V>(p1, row_ptr(g, p, ra - 3, j0));
 #pragma unroll
     for (int q = 0; q < V; ++q) rho1[q] = rho_of(c, F1[q]);
-    const T* pr0 = rowptr(p, ra - 2);
+    const T* pr0 = row_ptr(g, p, ra - 2, j0);
     load_c<T, V>(pnx.c, pr0);
     pnx.l = pr0[-1];
-    load_s<T, V>(vsnx, rowptr(vs, ra - 2));
-    Flnx = rowptr(F, ra - 2)[-1];
+    load_s<T, V>(vsnx, row_ptr(g, vs, ra - 2, j0));
+    Flnx = row_ptr(g, F, ra - 2, j0)[-1];
   }
   for (int r = ra - 2; r <= rb + 3; ++r) {
     T Fr[V], ur[V];
@@ -424,14 +412,14 @@ __global__ __launch_bounds__(256) void k_fct_x(Geom g, Consts<T> c, const T* __r
       for (int q = 0; q < V; ++q) vsr[q] = vsnx[q];
     }
     if (r < rb + 3) {
-      load_c<T, V>(Fnx, rowptr(F, r + 1));
-      load_c<T, V>(unx, rowptr(CORR ? us : u, r + 1));
+      load_c<T, V>(Fnx, row_ptr(g, F, r + 1, j0));
+      load_c<T, V>(unx, row_ptr(g, CORR ? us : u, r + 1, j0));
       if (CORR) {
-        const T* prn = rowptr(p, r + 1);
+        const T* prn = row_ptr(g, p, r + 1, j0);
         load_c<T, V>(pnx.c, prn);
         pnx.l = prn[-1];
-        load_s<T, V>(vsnx, rowptr(vs, r + 1));
-        Flnx = rowptr(F, r + 1)[-1];
+        load_s<T, V>(vsnx, row_ptr(g, vs, r + 1, j0));
+        Flnx = row_ptr(g, F, r + 1, j0)[-1];
       }
     }
     if (CORR) {  // update_uv for row r (:269-280): ur currently holds u*[r]
@@ -449,7 +437,7 @@ __global__ __launch_bounds__(256) void k_fct_x(Geom g, Consts<T> c, const T* __r
         const T pl = q == 0 ? pr.l : pr.c[q - 1];
         const T vn = corrected_velocity<T>(c, vsr[q], rhor[q], rl, pr.c[q], pl, c.dyi);
         ov[q] = (j >= 2 && j <= g.ny) ? vn : (T)0;   // v exists on j in [2, ny]
-        if (own && j <= g.ny && r >= g.own_lo && r <= g.own_hi) {
+        if (own && j <= g.ny && r >= g.own_lo && r <= g.own_hi) {   // (mirrors courant_count of march.h, inside the cell loop)
           if (urow && ur[q] * c.dt > c.cfl_x) viol++;
           if (j >= 2 && ov[q] * c.dt > c.cfl_y) viol++;
         }
@@ -462,8 +450,7 @@ __global__ __launch_bounds__(256) void k_fct_x(Geom g, Consts<T> c, const T* __r
         if (j0 + V > g.ny) Vo[at(g, r, g.ny + 1)] = (T)0;
         if (r == g.nx) {
           T zero[V];
-#pragma unroll
-          for (int q = 0; q < V; ++q) zero[q] = (T)0;
+          zero_fill(zero);
           store_c<T, V>(Uo + at(g, r + 1, j0), zero, j0, 1, g.ny);
         }
       }
@@ -477,19 +464,11 @@ __global__ __launch_bounds__(256) void k_fct_x(Geom g, Consts<T> c, const T* __r
     // F are exact zeros: the pipeline bypasses itself once the wave's whole 7-row dependency window
     // is zero (FctXPipe::push).
     T out[V];
-    bool rz = true;
-#pragma unroll
-    for (int q = 0; q < V; ++q) rz = rz && Fr[q] == (T)0;
-    pipe.template push<POST>(c, r, ilo, ihi, Fr, ur, out, __all(rz));
+    pipe.template push<POST>(c, r, ilo, ihi, Fr, ur, out, wave_all_zero(Fr));
     const int io = r - 3;
     if (io >= ra && io <= rb) store_s<T, V>(Fn + at(g, io, j0), out, j0, 1, g.ny);
   }
-  if (CORR && __any(viol != 0)) {
-    unsigned int tot = viol;
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) tot += __shfl_down(tot, sft, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(courant, (unsigned long long)tot);
-  }
+  if (CORR) courant_publish(viol, courant);
 }
 // 2dvof.py:385-448 fct_y_sweep, fused like k_fct_x.  The sweep direction is
 // the contiguous one, so the +-3-cell dependency is resolved across lanes with
@@ -507,7 +486,7 @@ __global__ __launch_bounds__(256) void k_fct_y(Geom g, Consts<T> c, const T* __r
   WaveTimer wt_(WT_FCT_Y);
   const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // SGPR: rows are wave-uniform
   const int lane = threadIdx.x & 63;
-  const int tj = wave % nty, ch = wave / nty;
+  const int tj = wave % nty, ch = wave / nty;   // (from here to jhi: mirrors tile_decode of march.h)
   const int c0 = 1 - HT + tj * STRIDE;
   const int j0 = c0 + lane * V;
   const int ra = rfirst + ch * R;
@@ -565,46 +544,26 @@ __global__ __launch_bounds__(256) void k_fct_y(Geom g, Consts<T> c, const T* __r
         const T vn = corrected_velocity<T>(c, vz[q], rhoz[q], q == 0 ? rhol : rhoz[q - 1], pz[q],
                                            q == 0 ? pl : pz[q - 1], c.dyi);
         vz[q] = (j >= 2 && j <= ny) ? vn : (T)0;   // v exists on j in [2, ny]; j = 1, ny+1 keep set_BC's 0
-        if (own && j >= jlo && j <= jhi) {
+        if (own && j >= jlo && j <= jhi) {   // (mirrors courant_count of march.h, inside the cell loop)
           if (i >= 2 && ou[q] * c.dt > c.cfl_x) viol++;
           if (j >= 2 && vz[q] * c.dt > c.cfl_y) viol++;
         }
         p1[q] = pz[q];
         rho1[q] = rhoz[q];
       }
-      // wall faces included (set_BC's zeros, :525): the x sweep reads u[1], u[nx+1] before the
-      // u, v boundary kernel runs on a full domain
-      store_s<T, V>(Uo + o, ou, j0, jlo, jhi);
-      store_s<T, V>(Vo + o, vz, j0, jlo, jhi == ny ? ny + 1 : jhi);
-      if (i == g.nx) {
-        T zero[V];
-#pragma unroll
-        for (int q = 0; q < V; ++q) zero[q] = (T)0;
-        store_c<T, V>(Uo + o + g.pitch, zero, j0, jlo, jhi);
-      }
+      store_uv_row<T, V>(Uo + o, Vo + o, Uo + o + g.pitch, i == g.nx, ou, vz, j0, jlo, jhi, ny);
     }
-    {  // F identically 0 over the wave's whole row segment: every output of the segment is 0
-      bool rz = true;
-#pragma unroll
-      for (int q = 0; q < V; ++q) rz = rz && Fz[q] == (T)0;
-      if (__all(rz)) {
-        T zero[V];
-#pragma unroll
-        for (int q = 0; q < V; ++q) zero[q] = (T)0;
-        store_s<T, V>(Fn + o, zero, j0, jlo, jhi);
-        continue;
-      }
+    if (wave_all_zero(Fz)) {   // F identically 0 over the wave's whole row segment: every output of the segment is 0
+      T zero[V];
+      zero_fill(zero);
+      store_s<T, V>(Fn + o, zero, j0, jlo, jhi);
+      continue;
     }
     T out[V];
     fct_y_row<T, V, POST>(c, j0, ny, Fz, vz, out);
     store_s<T, V>(Fn + o, out, j0, jlo, jhi);
   }
-  if (CORR && __any(viol != 0)) {
-    unsigned int tot = viol;
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) tot += __shfl_down(tot, sft, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(courant, (unsigned long long)tot);
-  }
+  if (CORR) courant_publish(viol, courant);
 }
 
 // ------------------------------------------------------------------ fused transport
@@ -622,55 +581,32 @@ __global__ __launch_bounds__(256) void k_fct_y(Geom g, Consts<T> c, const T* __r
 // [ilo, ihi] enter the x pipeline unswept (YFIRST), and F' in the ghost columns only ever meets the
 // zero wall velocity v[:,1] = v[:,ny+1] = 0 (x first).
 
-// Up to three row ranges a launch produces, in this order, each cut in chunks of its own length
-// (an empty range has last < first): e.g. the two edge bands of a strip in short chunks.
-struct RowRanges {
-  int first[3], last[3], R[3];
-};
-
 template <typename T, int V, bool YFIRST>
 __global__ __launch_bounds__(256) void k_transport(Geom g, Consts<T> c, const T* __restrict__ F, T* __restrict__ Fn,
                                                     int nty, const T* __restrict__ us,
                                                     const T* __restrict__ vs, const T* __restrict__ p,
                                                     T* __restrict__ Uo, T* __restrict__ Vo,
-                                                    unsigned long long* __restrict__ courant, RowRanges rr) {
-  // rr: all computable rows of a full domain; on a strip the owned rows -- as one range, or the two
+                                                    unsigned long long* __restrict__ courant, RowSegments rows) {
+  // rows (row_segments.h): all computable rows of a full domain; on a strip the owned rows -- as one segment, or the two
   // edge bands (what the neighbours wait for) first and then the rest, in one launch or in two.
   // The sweeps' domain stays [ilo, ihi].
-  constexpr int W = TransportGeom<V>::W, HT = TransportGeom<V>::H, STRIDE = TransportGeom<V>::STRIDE;
-  static_assert(HT >= 4 && HT % V == 0, "the y sweep's +-3 dependency is resolved across lanes");
+  typedef TransportGeom<V> TG;
+  static_assert(TG::H >= 4 && TG::H % V == 0, "the y sweep's +-3 dependency is resolved across lanes");
   WaveTimer wt_(WT_TRANSPORT);
-  const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int tj = wave % nty, ch = wave / nty;
-  const int c0 = 1 - HT + tj * STRIDE;
-  const int j0 = c0 + lane * V;
   const int ilo = g.ilo, ihi = g.ihi, nx = g.nx, ny = g.ny;
-  int k = 0, cbase = 0;   // range of this chunk (wave-uniform)
-  for (; k < 3; ++k) {
-    const int n = rr.last[k] >= rr.first[k] ? (rr.last[k] - rr.first[k] + rr.R[k]) / rr.R[k] : 0;
-    if (ch < cbase + n) break;
-    cbase += n;
-  }
-  if (k == 3) return;  // padding waves of the last block
-  const int R = rr.R[k], hi = rr.last[k];
-  const int ra = rr.first[k] + (ch - cbase) * R;
-  const int rb = ra + R - 1 < hi ? ra + R - 1 : hi;
-  const int jlo = c0 + HT > 1 ? c0 + HT : 1;
-  const int jhi = c0 + W - HT - 1 < ny ? c0 + W - HT - 1 : ny;
-  auto rowptr = [&](const T* base, int r) {
-    const int rc = r < g.row_lo ? g.row_lo : (r > g.row_hi ? g.row_hi : r);
-    return base + at(g, rc, j0);
-  };
+  int tj, ch, j0, jlo, jhi;
+  tile_decode<TG, V>(wave_index(), nty, threadIdx.x & 63, ny, tj, ch, j0, jlo, jhi);
+  int ra = 1, rb = 0;   // the chunk's rows (wave-uniform)
+  if (!row_chunk_rows_of(rows, ch, ra, rb)) return;  // padding waves of the last block
   // the register window and the arithmetic of an iteration: TransportWindow (shared with k_tm)
   TransportWindow<T, V> win;
   {
     T f1[V], pr1[V], v0[V];
-    load_c<T, V>(f1, rowptr(F, ra - 3));
-    load_c<T, V>(pr1, rowptr(p, ra - 3));
+    load_c<T, V>(f1, row_ptr(g, F, ra - 3, j0));
+    load_c<T, V>(pr1, row_ptr(g, p, ra - 3, j0));
     const bool swept = YFIRST && ra - 3 >= ilo;
     if (swept) {
-      load_s<T, V>(v0, rowptr(vs, ra - 3));
+      load_s<T, V>(v0, row_ptr(g, vs, ra - 3, j0));
     } else {
 #pragma unroll
       for (int q = 0; q < V; ++q) v0[q] = (T)0;
@@ -678,15 +614,15 @@ __global__ __launch_bounds__(256) void k_transport(Geom g, Consts<T> c, const T*
     win.template init<YFIRST, false>(c, j0, ny, f1, pr1, v0, swept);
   }
   T Fnx[V], usnx[V], vsnx[V], pnx[V];  // row r, prefetched one iteration ahead
-  load_c<T, V>(Fnx, rowptr(F, ra - 2));
-  load_s<T, V>(usnx, rowptr(us, ra - 2));
+  load_c<T, V>(Fnx, row_ptr(g, F, ra - 2, j0));
+  load_s<T, V>(usnx, row_ptr(g, us, ra - 2, j0));
   if (YFIRST) {
-    load_s<T, V>(vsnx, rowptr(vs, ra - 2));
+    load_s<T, V>(vsnx, row_ptr(g, vs, ra - 2, j0));
   } else {
 #pragma unroll
     for (int q = 0; q < V; ++q) vsnx[q] = (T)0;
   }
-  load_c<T, V>(pnx, rowptr(p, ra - 2));
+  load_c<T, V>(pnx, row_ptr(g, p, ra - 2, j0));
   unsigned int viol = 0;
   for (int r = ra - 2; r <= rb + 3; ++r) {
     T Fr[V], ur[V], vr[V], pr[V];
@@ -695,46 +631,23 @@ __global__ __launch_bounds__(256) void k_transport(Geom g, Consts<T> c, const T*
       Fr[q] = Fnx[q]; ur[q] = usnx[q]; vr[q] = vsnx[q]; pr[q] = pnx[q];
     }
     if (r < rb + 3) {
-      load_c<T, V>(Fnx, rowptr(F, r + 1));
-      load_s<T, V>(usnx, rowptr(us, r + 1));
+      load_c<T, V>(Fnx, row_ptr(g, F, r + 1, j0));
+      load_s<T, V>(usnx, row_ptr(g, us, r + 1, j0));
       // x first: the y sweep trails the pipeline and only touches the chunk's own rows, so v* of the
       // lead-in / lead-out rows is never used (the stored v of a row is written by the chunk that owns it)
-      if (YFIRST || (r + 1 >= ra && r + 1 <= rb)) load_s<T, V>(vsnx, rowptr(vs, r + 1));
-      load_c<T, V>(pnx, rowptr(p, r + 1));
+      if (YFIRST || (r + 1 >= ra && r + 1 <= rb)) load_s<T, V>(vsnx, row_ptr(g, vs, r + 1, j0));
+      load_c<T, V>(pnx, row_ptr(g, p, r + 1, j0));
     }
     T out[V];
     const bool own = r >= ra && r <= rb;     // rows this chunk stores (and counts)
     win.template step<YFIRST, false>(c, r, ilo, ihi, nx, j0, ny, Fr, ur, vr, pr, out, ra, rb, [&](bool urow) {
-      if (own && r >= g.own_lo && r <= g.own_hi) {
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          const int j = j0 + q;
-          if (j >= jlo && j <= jhi) {
-            if (urow && ur[q] * c.dt > c.cfl_x) viol++;
-            if (j >= 2 && vr[q] * c.dt > c.cfl_y) viol++;
-          }
-        }
-      }
-      if (own) {
-        store_s<T, V>(Uo + at(g, r, j0), ur, j0, jlo, jhi);
-        store_s<T, V>(Vo + at(g, r, j0), vr, j0, jlo, jhi == ny ? ny + 1 : jhi);
-        if (r == nx) {
-          T zero[V];
-#pragma unroll
-          for (int q = 0; q < V; ++q) zero[q] = (T)0;
-          store_c<T, V>(Uo + at(g, r + 1, j0), zero, j0, jlo, jhi);
-        }
-      }
+      if (own && r >= g.own_lo && r <= g.own_hi) courant_count(c, ur, vr, urow, j0, jlo, jhi, viol);
+      if (own) store_uv_row<T, V>(Uo + at(g, r, j0), Vo + at(g, r, j0), Uo + at(g, r + 1, j0), r == nx, ur, vr, j0, jlo, jhi, ny);
     });
     const int io = r - 3;
     if (io >= ra && io <= rb) store_s<T, V>(Fn + at(g, io, j0), out, j0, jlo, jhi);
   }
-  if (__any(viol != 0)) {
-    unsigned int tot = viol;
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) tot += __shfl_down(tot, sft, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(courant, (unsigned long long)tot);
-  }
+  courant_publish(viol, courant);
 }
 
 }  // namespace vof

@@ -3,7 +3,7 @@
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
 #pragma once
-#include "common.h"
+#include "march.h"
 
 namespace vof {
 
@@ -240,6 +240,7 @@ __global__ __launch_bounds__(256) void k_normals(Geom g, Consts<T> c, const T* _
     T ox[V], oy[V];
 #pragma unroll
     for (int q = 0; q < V; ++q) {
+      // (mirrors normals_cell of march.h: with the call the fp32 form stores its columns one by one)
       const T Fmm = left_of(m, q), Fm0 = m.c[q], Fmp = right_of(m, q);
       const T F0m = left_of(z, q), F00 = z.c[q], F0p = right_of(z, q);
       const T Fpm = left_of(p, q), Fp0 = p.c[q], Fpp = right_of(p, q);
@@ -298,6 +299,9 @@ __global__ __launch_bounds__(256) void k_kappa(Geom g, Consts<T> c, const T* __r
 
 // ------------------------------------------------------------------ predictor
 // 2dvof.py:206-233 advect_upwind: u*, v* from u, v, kappa, F (rho, nu).
+// k_predictor and k_rhs are the literal left-to-right statement of 2dvof.py:206-241 and stay written out: what the fused kernels
+// do instead (upwind_diff's operand selection, the constant-division tiers of MomentumWindow::step) is tested against these two
+// in tests/test_parity_gpu.py::test_each_verb_matches_oracle, so they share no arithmetic with it.
 // STORED: read the rho / nu arrays written by cal_nu_rho (verb semantics);
 // otherwise recompute them from F per cell (identical values: rho[i,j] is a
 // pure function of F[i,j] and F is unchanged since cal_nu_rho, 2dvof.py:513-517).
@@ -450,12 +454,10 @@ __global__ __launch_bounds__(256) void k_correct(Geom g, Consts<T> c, const T* _
     const bool own = i >= g.own_lo && i <= g.own_hi;
 #pragma unroll
     for (int q = 0; q < V; ++q) {
-      T r = (rz.c[q] + rm_[q]) * (T)0.5;
-      ou[q] = usz[q] - c.dt / r * (pz.c[q] - pm[q]) * c.dxi;
-      T r2 = (rz.c[q] + left_of(rz, q)) * (T)0.5;
-      ov[q] = vsz[q] - c.dt / r2 * (pz.c[q] - left_of(pz, q)) * c.dyi;
+      ou[q] = corrected_velocity<T>(c, usz[q], rz.c[q], rm_[q], pz.c[q], pm[q], c.dxi);
+      ov[q] = corrected_velocity<T>(c, vsz[q], rz.c[q], left_of(rz, q), pz.c[q], left_of(pz, q), c.dyi);
       const int j = j0 + q;
-      if (own && j <= g.ny) {
+      if (own && j <= g.ny) {   // (mirrors courant_count of march.h, inside the cell loop)
         if (i >= 2 && ou[q] * c.dt > c.cfl_x) viol++;
         if (j >= 2 && ov[q] * c.dt > c.cfl_y) viol++;
       }
@@ -468,12 +470,7 @@ __global__ __launch_bounds__(256) void k_correct(Geom g, Consts<T> c, const T* _
       rm_[q] = rz.c[q];
     }
   }
-  if (__any(viol != 0)) {
-    unsigned int tot = viol;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) tot += __shfl_down(tot, s, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(courant, (unsigned long long)tot);
-  }
+  courant_publish(viol, courant);
 }
 
 // cells of the computable rows whose F is an exact zero (the batch-form rule of vof_step: one look at the state per handle)
@@ -482,8 +479,7 @@ __global__ __launch_bounds__(256) void k_gas_cells(Geom g, const T* __restrict__
   unsigned int n = 0;
   for (int i = g.ilo + (int)blockIdx.x; i <= g.ihi; i += (int)gridDim.x)
     for (int j = 1 + (int)threadIdx.x; j <= g.ny; j += 256) n += F[at(g, i, j)] == (T)0 ? 1u : 0u;
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) n += __shfl_down(n, sft, 64);
+  n = wave_sum(n);
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, (unsigned long long)n);
 }
 

@@ -21,10 +21,10 @@ template <bool YFIRST, int ABL>
 void dbg_tm(vof2d_ctx* h) {
   typedef double T; constexpr int V = VecWidth<T>::V;
   const int ntf = TmGeom<V>::tiles(h->g.ny), first = h->g.ilo, last = h->g.ihi;
-  const TmSegments rows = L<T>::tm_chunk_rows(h, first, last, ntf, resident(h, k_tm<T, V, YFIRST, false, true, ABL>, 128));
+  const RowSegments rows = L<T>::tm_chunk_rows(h, first, last, ntf, resident(h, k_tm<T, V, YFIRST, false, true, ABL>, 128));
   const TbPlan tp{nullptr, nullptr, 0, 0, 0, 0, 0};
-  const unsigned pairs = (unsigned)(tm_chunks(rows) * ntf);
-  h->tm_segments_last = tm_used_segments(rows);
+  const unsigned pairs = (unsigned)(row_chunks(rows) * ntf);
+  h->tm_segments_last = row_used_segments(rows);
   launch_block(h, kTM, k_tm<T, V, YFIRST, false, true, ABL>, dim3(pairs), 128u, 0, h->g, L<T>::C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
                (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
                F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, fRHS), h->d_courant + 3, tp, rows);

@@ -366,7 +366,7 @@ struct L {
     const long R = (rows + chunks - 1) / chunks;
     return (int)(R < 16 ? 16 : (R > 96 ? 96 : R));
   }
-  // The rows [first, last] of one launch as segments (kernels/tm_segments.h): the body in chunks of tm_body_rows and, behind it, up to
+  // The rows [first, last] of one launch as segments (kernels/row_segments.h): the body in chunks of tm_body_rows and, behind it, up to
   // three tail segments of shorter chunks.  The hardware hands the pairs out in index order, so the chunks of the last rows are the
   // ones that start last, and a launch ended with whole 52-row gas chunks (87 us each) at falling occupancy: Sum durations / (span x
   // slots) = 0.735.  Shorter chunks there fill the slots the body's pairs leave (0.82-0.85) at the price of their 14 lead-in steps.
@@ -386,7 +386,7 @@ struct L {
   // launches and forced chunk lengths (tm_rows) keep one segment.
   struct TmTaperRule { int div[3]; int share[3]; int floor_rows; int min_body_rows; };   // tail segment j: chunks of R / div[j] rows (>= floor_rows), share[j] % of the resident pairs
   static constexpr TmTaperRule kTmTaper{{2, 4, 6}, {30, 40, 20}, 8, 28};
-  static TmSegments tm_chunk_rows(const vof2d_ctx* h, int first, int last, int ntf, long cap) {
+  static RowSegments tm_chunk_rows(const vof2d_ctx* h, int first, int last, int ntf, long cap) {
     const int R = tm_body_rows(h, last - first + 1, ntf, cap);
     int at[3] = {last + 1, last + 1, last + 1}, len[3] = {1, 1, 1};
     if (h->tm_taper > 0) {
@@ -399,16 +399,16 @@ struct L {
         lo = at[j];
       }
     } else if (h->tm_taper < 0 && h->tm_rows <= 0 && h->g.wall_lo && h->g.wall_hi && first == h->g.ilo && last == h->g.ihi &&
-               (long)tm_seg_chunks(first, last, R) * ntf > cap && (R >= kTmTaper.min_body_rows || h->tm_taper == -2)) {
+               (long)row_seg_chunks(first, last, R) * ntf > cap && (R >= kTmTaper.min_body_rows || h->tm_taper == -2)) {
       int lo = last + 1;
       for (int j = 2; j >= 0; --j) {
         len[j] = R / kTmTaper.div[j] > kTmTaper.floor_rows ? R / kTmTaper.div[j] : kTmTaper.floor_rows;
         lo -= (int)((kTmTaper.share[j] * cap + 50L * ntf) / (100L * ntf)) * len[j];   // (chunk rows of the segment) * (their length)
         at[j] = lo;
       }
-      if (at[0] < first + R) return tm_segments(tm_seg(first, last, R));
+      if (at[0] < first + R) return row_segments(row_seg(first, last, R));
     }
-    return tm_segments(tm_seg(first, at[0] - 1, R), tm_seg(at[0], at[1] - 1, len[0]), tm_seg(at[1], at[2] - 1, len[1]), tm_seg(at[2], last, len[2]));
+    return row_segments(row_seg(first, at[0] - 1, R), row_seg(at[0], at[1] - 1, len[0]), row_seg(at[1], at[2] - 1, len[1]), row_seg(at[2], last, len[2]));
   }
   // rows [first, last] and, in the same launch, [first2, last2] (a strip's two edge bands: two segments of rows_forced-row chunks);
   // store_uv: the last k_tm of a batch; rhs_id: the array the next step's rhs goes to (fRHS, or fKAPPA where the caller alternates
@@ -423,10 +423,10 @@ struct L {
     // (2.5 rounds) 261 / 281 (inside / behind the front), 48 252 / 282, 52 253 / 280, 54 256 / 277, 56 257 / 284,
     // 100 376 / 381 (tools/probes/pair_bound.py --rows)
     dispatch([&](auto YF, auto UV, auto BS) {
-      const TmSegments rows = rows_forced > 0 ? tm_segments(tm_seg(first, last, rows_forced), tm_seg(first2, last2, rows_forced))
+      const RowSegments rows = rows_forced > 0 ? row_segments(row_seg(first, last, rows_forced), row_seg(first2, last2, rows_forced))
                                               : tm_chunk_rows(h, first, last, ntf, resident(h, k_tm<T, V, YF(), UV(), true>, 128));
-      const unsigned pairs = (unsigned)(tm_chunks(rows) * ntf) + (tp.masks ? 1u : 0u);
-      h->tm_segments_last = tm_used_segments(rows);
+      const unsigned pairs = (unsigned)(row_chunks(rows) * ntf) + (tp.masks ? 1u : 0u);
+      h->tm_segments_last = row_used_segments(rows);
       launch_block(h, UV() ? kTMUV : kTM, k_tm<T, V, YF(), UV(), BS()>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
                    (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
                    F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, rhs_id), h->d_courant, tp, rows);
@@ -537,16 +537,10 @@ struct L {
   static int transport_rows(const vof2d_ctx* h) {
     return h->fctx_corr_rows > 0 ? h->fctx_corr_rows : chunk_rows(h, h->nty, 4, 16);
   }
-  static long range_chunks(const RowRanges& rr) {
-    long n = 0;
-    for (int k = 0; k < 3; ++k)
-      if (rr.last[k] >= rr.first[k]) n += (rr.last[k] - rr.first[k] + rr.R[k]) / rr.R[k];
-    return n;
-  }
-  // the rows of rr (all computable rows by default)
-  static void transport(vof2d_ctx* h, bool y_first, const RowRanges* ranges = nullptr) {
-    const RowRanges rr = ranges ? *ranges : RowRanges{{h->g.ilo, 1, 1}, {h->g.ihi, 0, 0}, {transport_rows(h), 1, 1}};
-    const unsigned tr_blocks = (unsigned)((range_chunks(rr) * h->nty + 3) / 4);
+  // the rows of `segments` (kernels/row_segments.h; all computable rows by default)
+  static void transport(vof2d_ctx* h, bool y_first, const RowSegments* segments = nullptr) {
+    const RowSegments rr = segments ? *segments : row_segments(row_seg(h->g.ilo, h->g.ihi, transport_rows(h)));
+    const unsigned tr_blocks = (unsigned)(((long)row_chunks(rr) * h->nty + 3) / 4);
     dispatch([&](auto YF) {
       launch(h, kTransport, k_transport<T, V, YF()>, dim3(tr_blocks), 0, h->g, C(h),
              (const T*)F_<T>(h, fF), F_<T>(h, fF2), h->nty, (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS),

@@ -37,7 +37,9 @@ void transport_part(vof2d_ctx* h, bool y_first, int part) {
   // the bands are few rows: short chunks, so that they are many short-lived waves (2 x 16 rows of an
   // 8192-wide strip: 31 us with 16-row chunks, 15-18 us with 4-row chunks)
   const int Rb = h->band_rows, R = L<T>::transport_rows(h);
-  const RowRanges rr{{pr.band_lo.first, pr.band_hi.first, pr.body.first}, {pr.band_lo.last, pr.band_hi.last, pr.body.last}, {Rb, Rb, R}};
+  // (the bands first, as ever: the neighbours wait for them)
+  const RowSegments rr = row_segments(row_seg(pr.band_lo.first, pr.band_lo.last, Rb), row_seg(pr.band_hi.first, pr.band_hi.last, Rb),
+                                      row_seg(pr.body.first, pr.body.last, R));
   L<T>::transport(h, y_first, &rr);
 }
 
@@ -304,7 +306,7 @@ bool enqueue_steps_halves(vof2d_ctx* h, int64_t first_step, int K) {
     n_lastjac = n - 1;
     ok = ok && hipEventRecord(ev_plan[k], st[P - 1]) == hipSuccess;
     all([&](int a, int b, bool) {
-      const RowRanges rr{{a, 1, 1}, {b, 0, 0}, {L<T>::transport_rows(h), 1, 1}};
+      const RowSegments rr = row_segments(row_seg(a, b, L<T>::transport_rows(h)));
       L<T>::transport(h, istep % 2 == 0, &rr);
     });
     swap_F(h);

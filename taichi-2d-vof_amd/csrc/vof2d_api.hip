@@ -868,7 +868,7 @@ int vof_get_counter(vof2d_handle h, const char* name, int64_t* value) {
     *value = h->pair_launches;
     return VOF_OK;
   }
-  if (!strcmp(name, "tm_segments")) {   // row segments of the last k_tm launch enqueued (1: no tail; kernels/tm_segments.h)
+  if (!strcmp(name, "tm_segments")) {   // row segments of the last k_tm launch enqueued (1: no tail; kernels/row_segments.h)
     *value = h->tm_segments_last;
     return VOF_OK;
   }

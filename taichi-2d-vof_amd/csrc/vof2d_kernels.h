@@ -10,6 +10,8 @@
 //
 // The kernels live in kernels/, one file per family:
 //   common.h     tile rows, streaming loads / stores, DPP neighbours, exact division
+//   march.h      wave_index, tile_c0, tile_columns, tile_decode, row_ptr, zero_fill, wave_all_zero, wave_sum, courant_count, courant_publish, store_uv_row, normals_cell, corrected_velocity   (what the marching kernels share around the arithmetic of a row)
+//   row_segments.h  the rows of a k_tm or k_transport launch as up to four segments of chunks, for host and device
 //   verbs.h      one kernel per reference verb (the literal main loop, 2dvof.py:513-528)
 //   plan.h       the equal-cost work plan of the fused Jacobi launches
 //   momentum.h   k_momentum      (cal_nu_rho + get_normal_young + advect_upwind + rhs)
@@ -33,6 +35,7 @@
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
+#include "kernels/march.h"
 #include "kernels/verbs.h"
 #include "kernels/plan.h"
 #include "kernels/momentum.h"

@@ -1,4 +1,4 @@
-"""k_tm's rows as segments (kernels/tm_segments.h, L::tm_chunk_rows): a launch cuts its rows into a body and up to three tail
+"""k_tm's rows as segments (kernels/row_segments.h, L::tm_chunk_rows): a launch cuts its rows into a body and up to three tail
 segments of shorter chunks, handed out in order.  Which rows a pair takes never changes a value -- every cell is computed from
 the same operands whatever the chunking --, so what can break is the bookkeeping: the pair -> (segment, chunk, rows) mapping, the
 pair count, ragged last chunks, chunks shorter than the marches' pipeline (12 transport rows around a chunk, the momentum wave
