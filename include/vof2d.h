@@ -280,6 +280,54 @@ int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycl
 #define VOF_IFACE_SUM_ISTEP 3
 #define VOF_IFACE_SUM_N 4
 int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary /* VOF_IFACE_SUM_N */);
+/* Extension: how curved the interface is, by height functions, and how far the solver's own curvature (the CSF kappa = -div of Youngs'
+ * normals, 2dvof.py:283-309) is from that.  One row per mixed cell with an orientation, the cells and the order of vof_interface at the
+ * same eps (the I, J columns are equal row for row).  Whole-domain handles only (the stencil reaches three rows: a strip returns
+ * VOF_ESTATE, as does a phased step in progress).  Every operand is converted to double first; ghost cells a fused step left virtual
+ * are settled first; f(ii, jj) = F[clamp(ii, 0, nx + 1), clamp(jj, 0, ny + 1)].
+ *   mixed, degenerate, mxsum, mysum   as vof_interface
+ *   AXIS        |mxsum| dx > |mysum| dy ? 1 : 0 -- 1: the heights are summed along i, 0 (and the tie): along j
+ *   heights     H[d], d = -1, 0, 1: the sum over t = -3 .. 3 of the raw f(i + d, j + t) (AXIS 0) or f(i + t, j + d) (AXIS 1)
+ *   VALID       1.0 if in all three columns the end cell on the liquid side (t = -3 if the normal component along the axis is >= 0,
+ *               else t = 3) is >= 1 - eps and the end cell on the gas side is <= eps (a NaN fails); else 0.0
+ *   KAPPA, HP   with (hs, ht) = (dy, dx) for AXIS 0, (dx, dy) for AXIS 1: hp = (H[1] - H[-1]) hs / (2 ht),
+ *               hpp = (H[1] - 2 H[0] + H[-1]) hs / ht^2, KAPPA = hpp / (1 + hp^2)^(3/2), HP = hp; both 0 where VALID is 0.
+ *               The solver's sign: -1/R for a drop, +1/R for a bubble
+ *   KAPPA_CSF   the solver's own curvature at the cell, evaluated in double: on an f64 handle, bit for bit, kappa[i, j] directly after
+ *               vof_get_normal_young on the same F (normals of cells outside [1, nx] x [1, ny] are 0, as the reference leaves them)
+ *   a row       VOF_CURV_N doubles: I, J, KAPPA, VALID, AXIS, KAPPA_CSF, HP, F
+ * The expression order is stated in csrc/kernels/curvature.h.  Rows come in ascending (i, j) order, i first.  At most cap_rows rows are
+ * written and nothing behind min(ROWS, cap_rows) rows is touched; `summary` always describes ALL rows, so rows = NULL with cap_rows = 0
+ * sizes a buffer.  The summary, VOF_CURV_SUM_N doubles (unused slots read 0), sums in double in the fixed order that file states:
+ *   SUM_ROWS (may exceed cap_rows), SUM_DEGENERATE, SUM_VALID; SUM_K, SUM_K2, MIN_K, MAX_K of KAPPA over the VALID rows; SUM_CSF,
+ *   SUM_CSF2, MIN_CSF, MAX_CSF of KAPPA_CSF over all rows; ISTEP.  A NaN operand makes a maximum +inf and a minimum -inf; with no
+ *   operand a sum reads 0, a maximum -inf and a minimum +inf.
+ * No atomics anywhere: the same state and call give the same bytes.  No field, istep, counter or cached graph changes, and a vof_step*
+ * that follows gives the bits it would have given without the call.  rows == NULL with cap_rows > 0, cap_rows < 0, summary == NULL, a
+ * bad eps (the rule of vof_interface), more than 2^31 - 1 cells: VOF_EINVAL, the handle untouched.  Synchronises and copies out. */
+#define VOF_CURV_I 0          /* global cell indices, as doubles */
+#define VOF_CURV_J 1
+#define VOF_CURV_KAPPA 2      /* height-function curvature (0 where VALID is 0) */
+#define VOF_CURV_VALID 3      /* 1.0: the three columns span the interface */
+#define VOF_CURV_AXIS 4       /* 1.0: heights summed along i; 0.0: along j */
+#define VOF_CURV_KAPPA_CSF 5  /* the solver's own curvature at the cell */
+#define VOF_CURV_HP 6         /* the slope of the height function (0 where VALID is 0) */
+#define VOF_CURV_F 7
+#define VOF_CURV_N 8
+#define VOF_CURV_SUM_ROWS 0       /* slots of `summary`: rows that exist (may exceed cap_rows) */
+#define VOF_CURV_SUM_DEGENERATE 1 /* mixed cells with no orientation: counted, no row */
+#define VOF_CURV_SUM_VALID 2      /* rows whose VALID is 1 */
+#define VOF_CURV_SUM_K 3          /* KAPPA over the VALID rows: sum, sum of squares, minimum, maximum */
+#define VOF_CURV_SUM_K2 4
+#define VOF_CURV_SUM_MIN_K 5
+#define VOF_CURV_SUM_MAX_K 6
+#define VOF_CURV_SUM_CSF 7        /* KAPPA_CSF over all rows: sum, sum of squares, minimum, maximum */
+#define VOF_CURV_SUM_CSF2 8
+#define VOF_CURV_SUM_MIN_CSF 9
+#define VOF_CURV_SUM_MAX_CSF 10
+#define VOF_CURV_SUM_ISTEP 11
+#define VOF_CURV_SUM_N 16
+int vof_curvature(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary /* VOF_CURV_SUM_N */);
 /* Extension: how many pieces the liquid (or the gas) is in, and what each piece is doing: connected-component labelling and per-blob
  * sums on the device instead of copying F, u, v to the host.  Cells: the handle's owned interior cells, i in [max(own_lo, 1), min(own_hi, nx)],
  * j in [1, ny]; ghost cells are never members; every operand is converted to double first (one code path for both dtypes).

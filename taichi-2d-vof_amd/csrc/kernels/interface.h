@@ -1,4 +1,4 @@
-// kernels/interface.h -- PLIC interface segments extracted on the device (k_iface, k_iface_scan): Youngs' normal, the line in the cell, an ordered compaction
+// kernels/interface.h -- PLIC interface segments extracted on the device (k_iface, k_iface_scan; scan_counts): Youngs' normal, the line in the cell, an ordered compaction
 //
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
@@ -174,16 +174,13 @@ __global__ __launch_bounds__(256) void k_iface(Geom g, const T* __restrict__ F, 
 }
 
 // ------------------------------------------------------------------ counts -> exclusive offsets, block partials -> summary
-// ONE block of kIfaceScanThreads threads.  Thread t owns the entries [t * run, (t + 1) * run) of cnt (run = ceil(n / threads)):
-// it adds them up, the block scans the threads' totals (waves by __shfl_up, the 16 wave totals by thread 0 through LDS), and
-// the thread writes its entries' exclusive offsets back.  Then the partials (fold_partials of kernels/reduce.h), and
-// threads 0 .. IFS_N - 1 store one slot of the summary each.  The launch boundary in front of it is what makes the counts
-// and partials of every block visible.
-__global__ __launch_bounds__(kIfaceScanThreads) void k_iface_scan(int* __restrict__ cnt, long long n, const double* __restrict__ part, int nblocks,
-                                                                   double* __restrict__ summary, double istep) {
-  constexpr int NT = kIfaceScanThreads, NW = NT / 64;
-  __shared__ long long wsum[NW + 1];
-  __shared__ double red[NT][kIfacePart];
+// Every thread of a ONE-block kernel of NT threads calls it (k_iface_scan, k_curv_scan of kernels/curvature.h).  Thread t owns the entries
+// [t * run, (t + 1) * run) of cnt (run = ceil(n / threads)): it adds them up, the block scans the threads' totals (waves by __shfl_up,
+// the NT / 64 wave totals by thread 0 through LDS), and the thread writes its entries' exclusive offsets back.  Returns the total of all
+// entries to every thread.  wsum: NT / 64 + 1 words of LDS.
+template <int NT>
+__device__ __forceinline__ long long scan_counts(int* __restrict__ cnt, long long n, long long* wsum) {
+  constexpr int NW = NT / 64;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const long long run = (n + NT - 1) / NT;
   const long long e0 = (long long)t * run, e1 = e0 + run < n ? e0 + run : n;
@@ -208,7 +205,19 @@ __global__ __launch_bounds__(kIfaceScanThreads) void k_iface_scan(int* __restric
     cnt[e] = (int)off;
     off += k;
   }
-  const double segments = (double)wsum[NW];
+  return wsum[NW];
+}
+
+// ONE block of kIfaceScanThreads threads: scan_counts, then the partials (fold_partials of kernels/reduce.h), and threads
+// 0 .. IFS_N - 1 store one slot of the summary each.  The launch boundary in front of it is what makes the counts and partials of
+// every block visible.
+__global__ __launch_bounds__(kIfaceScanThreads) void k_iface_scan(int* __restrict__ cnt, long long n, const double* __restrict__ part, int nblocks,
+                                                                   double* __restrict__ summary, double istep) {
+  constexpr int NT = kIfaceScanThreads;
+  __shared__ long long wsum[NT / 64 + 1];
+  __shared__ double red[NT][kIfacePart];
+  const int t = threadIdx.x;
+  const double segments = (double)scan_counts<NT>(cnt, n, wsum);
   const double zero[kIfacePart] = {0.0, 0.0};
   fold_partials<NT, kIfacePart, 0>(part, nblocks, zero, red);
   if (t >= IFS_N) return;

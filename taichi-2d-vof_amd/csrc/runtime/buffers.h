@@ -61,6 +61,8 @@ struct WorkBufs {
   RowBufs diag;        // vof_diagnostics / vof_step_diag (runtime/diag_reduce.h): the partials of k_diag, rows of VOF_DIAG_N doubles
   DevBuf iface_work;   // vof_interface (runtime/interface.h, IfaceCarve): the segment counts, turned into offsets in place; the partials; the summary
   DevBuf iface_rows;   // ... the segments, VOF_IFACE_N doubles each, grown on demand
+  DevBuf curv_work;    // vof_curvature (runtime/curvature.h, CurvCarve): the row counts, turned into offsets in place; the partials; the summary
+  DevBuf curv_rows;    // ... the rows, VOF_CURV_N doubles each, grown on demand
   DevBuf blob_work;    // vof_blobs (runtime/blobs.h, BlobCarve): what the geometry fixes
   DevBuf blob_rec;     // ... grown on demand: the integer records of the blobs (kBlobRec ints each),
   DevBuf blob_off;     // the wave offsets and

@@ -54,6 +54,14 @@ inline IfaceCarve carve_iface(size_t entries, size_t doubles) {
   return {cnt, part, a.total};
 }
 
+// vof_curvature: the count of every (row, column tile) and one spare int; the block partials; the summary
+struct CurvCarve { size_t cnt, part, sum, total; };
+inline CurvCarve carve_curv(size_t entries, size_t part_doubles, size_t summary_doubles) {
+  Carve a;
+  const size_t cnt = a.ints(entries + 1), part = a.doubles(part_doubles), sum = a.doubles(summary_doubles);
+  return {cnt, part, sum, a.total};
+}
+
 // vof_blobs: parent, then label, of every cell; the blob index of every root; the root count of every (row, column tile),
 // two ints of k_blob_stats and one spare; 8 doubles (the summary, the total of a scan)
 struct BlobCarve { size_t lab, idx, cnt, sum, total; };

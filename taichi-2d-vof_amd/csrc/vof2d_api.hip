@@ -20,6 +20,7 @@
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
 //   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
 //   runtime/interface.h  the buffers, launches and copies of vof_interface
+//   runtime/curvature.h  the buffers, launches and copies of vof_curvature
 //   runtime/blobs.h      the buffers, launches and copies of vof_blobs
 //   runtime/tracers.h    the buffers, launches and copies of vof_tracers_*, the loop of vof_step_tracers
 //   runtime/depths.h     the buffers, launches and copies of vof_depths and vof_gauges_*, the loop of vof_step_gauges
@@ -38,6 +39,7 @@
 #include "runtime/step.h"
 #include "runtime/diag_reduce.h"
 #include "runtime/interface.h"
+#include "runtime/curvature.h"
 #include "runtime/blobs.h"
 #include "runtime/tracers.h"
 #include "runtime/depths.h"
@@ -472,6 +474,16 @@ int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, do
   if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
   if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_interface keeps 32-bit offsets: at most 2^31 - 1 cells");
   return iface_run(h, eps, rows, cap_rows, summary);
+}
+
+// ---- height-function curvature beside the solver's own (kernels/curvature.h, runtime/curvature.h)
+int vof_curvature(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary) {
+  if (!h || !summary) return VOF_EINVAL;
+  if (!(eps >= 0.0 && eps < 0.5)) return fail(h, VOF_EINVAL, "eps must lie in [0, 0.5)");
+  if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
+  if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_curvature keeps 32-bit offsets: at most 2^31 - 1 cells");
+  if (const int rc = check_verb_allowed(h, "vof_curvature needs the whole domain in one handle (curvature over row strips is not built)")) return rc;
+  return curv_run(h, eps, rows, cap_rows, summary);
 }
 
 // ---- droplets and bubbles, labelled and measured (kernels/blobs.h, runtime/blobs.h)

@@ -72,6 +72,11 @@ def build_parser():
                      help='every N steps write data/interface_NNNNNN.npy -- the interface as one PLIC segment per mixed cell, '
                           'rows of i, j, x0, y0, x1, y1, nx, ny extracted on the device (vof_interface) -- and append istep, '
                           'segments, degenerate, length to data/interface.csv; with -s the VOF frame draws the segments')
+    ext.add_argument('--curvature-every', type=int, default=None, metavar='N',
+                     help='every N steps write data/curvature_NNNNNN.npy -- one row per mixed cell, in the order of --interface-every: '
+                          'i, j, kappa (height functions), valid, axis, kappa_csf (the solver\'s own), hp, f, computed on the device '
+                          '(vof_curvature) -- and append istep, rows, degenerate, valid, the valid share, mean, rms, min and max of both '
+                          'curvatures to data/curvature.csv; one GPU')
     ext.add_argument('--blobs-every', type=int, default=None, metavar='N',
                      help='every N steps append one line per blob to data/blobs.csv -- istep, blob, cells, volume, xc, yc, uc, vc, '
                           'imin, imax, jmin, jmax of every connected piece of the phase, labelled and measured on the device (vof_blobs)')
@@ -223,7 +228,9 @@ def parse_args(argv=None):
         for opt in options:
             if getattr(args, opt + "_every") is not None and getattr(args, opt + "_every") < 1:
                 parser.error("--%s-every needs N >= 1" % opt)
-    at_least_1("diag", "interface", "blobs")
+    at_least_1("diag", "interface", "blobs", "curvature")
+    if args.curvature_every is not None and args.gpus > 1:
+        parser.error("--curvature-every runs on one GPU (curvature over row strips is not built): drop --gpus")
     if not 0.0 < args.blobs_threshold < 1.0:
         parser.error("--blobs-threshold needs 0 < T < 1")
     if args.tracers < 0:

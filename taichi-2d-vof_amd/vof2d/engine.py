@@ -235,6 +235,18 @@ class Engine:
                                 lambda ptr, cap: self.api.interface(self._h, float(eps), ptr, cap, summ))
         return rows, interface.summary_of(list(summ))
 
+    def curvature(self, eps=1e-6):
+        """vof_curvature: one row per mixed cell with an orientation -- the cells and the order of interface() at the same eps --
+        holding the height-function curvature, whether its three columns span the interface, the axis, the solver's own CSF
+        curvature at the cell, the slope and F; whole-domain handles only.  Returns (rows, summary): an (n, VOF_CURV_N) float64
+        array (the slots: vof2d/curvature.py) and the summary as a dict keyed by curvature.SUMMARY.  One call with the capacity
+        the last call needed (plus a margin); a second one if the list has outgrown it."""
+        from . import curvature
+        summ = (C.c_double * _abi.VOF_CURV_SUM_N)()
+        rows = self._sized_rows("_curv_cap", 0, _abi.VOF_CURV_N, summ, _abi.VOF_CURV_SUM_ROWS, "curvature",
+                                lambda ptr, cap: self.api.curvature(self._h, float(eps), ptr, cap, summ))
+        return rows, curvature.summary_of(list(summ))
+
     def blobs(self, phase="liquid", threshold=0.5, labels=False):
         """vof_blobs: the connected pieces of the liquid (F >= threshold) or of the gas (F < threshold) on the owned interior
         rows, labelled and measured on the device; returns (rows, summary[, labels]): an (n, VOF_BLOB_N) float64 array in

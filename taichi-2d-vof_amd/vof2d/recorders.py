@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from . import blobs, cli, diag, dye, frames, gauges, stats, tracers
+from . import blobs, cli, curvature, diag, dye, frames, gauges, stats, tracers
 
 NSTEP = 100  # Interval to update output                       (2dvof.py:497)
 
@@ -98,6 +98,22 @@ class Interface(Recorder):
                 seg, summ = self.run.iface_last
                 np.save('data/interface_%06d.npy' % i, seg)
                 append(self.path, ['%d,%d,%d,%r' % (i, summ["SEGMENTS"], summ["DEGENERATE"], float(summ["LENGTH"]))])
+
+
+class Curvature(Recorder):
+    """--curvature-every: the curvature rows (vof_curvature) are read between calls, like the interface; one GPU."""
+    path, header = 'data/curvature.csv', curvature.CSV_HEADER
+
+    def setup(self, run):
+        if not hasattr(run.api, "curvature"):
+            raise SystemExit("--curvature-every needs the curvature verb of the HIP library (vof_curvature): this backend has none")
+        super().setup(run)
+
+    def after(self, i):
+        if due(i, self.every):
+            rows, summ = self.run.eng.curvature()
+            np.save('data/curvature_%06d.npy' % i, rows)
+            append(self.path, [curvature.csv_line(summ)])
 
 
 class Blobs(Recorder):
@@ -340,11 +356,11 @@ class Display(Recorder):
 
 
 def recorders_of(args, drv, world):
-    """The recorders the options ask for, in the order they act at a stop.  Tracers, gauges, frames and statistics run on one GPU;
+    """The recorders the options ask for, in the order they act at a stop.  The curvature, tracers, gauges, frames and statistics run on one GPU;
     strips get the rest (the dye refuses them)."""
     opt = lambda name: getattr(args, name, None) or 0
     one = world == 1
-    every = [Diag(drv.diag_every, stop=not drv.diag_in_advance), Interface(opt("interface_every")), Blobs(opt("blobs_every")),
+    every = [Diag(drv.diag_every, stop=not drv.diag_in_advance), Interface(opt("interface_every")), Curvature(opt("curvature_every") if one else 0), Blobs(opt("blobs_every")),
              Tracers(save=opt("tracers_save_every"), on=one and opt("tracers")),
              Gauges(opt("gauges_every"), stop=not getattr(drv, "gauges_in_advance", False), on=one and (opt("gauge") or opt("gauges_file") or opt("gauges_every"))),
              Depths(opt("depths_every")),

@@ -143,6 +143,10 @@ class VOF2D:
         """The interface as PLIC segments, extracted on the device (vof_interface): (rows, summary), vof2d/interface.py."""
         return self.eng.interface(eps)
 
+    def curvature(self, eps=1e-6):
+        """Height-function curvature of every mixed cell beside the solver's own, on the device (vof_curvature): (rows, summary), vof2d/curvature.py."""
+        return self.eng.curvature(eps)
+
     def blobs(self, phase="liquid", threshold=0.5, labels=False):
         """Droplets or bubbles labelled and measured on the device (vof_blobs): (rows, summary[, labels]), vof2d/blobs.py."""
         return self.eng.blobs(phase, threshold, labels)
