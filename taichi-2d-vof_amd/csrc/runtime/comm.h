@@ -64,7 +64,7 @@ Rccl* rccl_bind(Rccl& r) {
 void comm_teardown(vof2d_ctx* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->cstream) (void)hipStreamSynchronize(h->cstream);
-  h->graphs.clear_exchange();  // captured send/recv nodes hold the communicator: they go first
+  h->graphs.clear_if([](const GraphKey& k) { return k.kind >= gXchg; });  // captured send/recv nodes hold the communicator: they go first
   if (h->comm && rccl()) (void)rccl()->CommDestroy(h->comm);
   h->comm = nullptr;
   if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
@@ -148,7 +148,7 @@ int enqueue_transport_exchange(vof2d_ctx* h) {
   transport_part<T>(h, y_first, kEdgeBands);
   if ((rc = comm_post(h, VOF_XCHG_P | VOF_XCHG_F | VOF_XCHG_U | VOF_XCHG_V, /*f_in_twin=*/true, 1))) return rc;
   transport_part<T>(h, y_first, kRest);
-  swap_F(h);
+  h->views.swap_F();
   if ((rc = comm_join(h))) return rc;
   if (!h->virtual_ghosts) L<T>::template set_bc<BC_ALL>(h);
   return VOF_OK;
@@ -223,8 +223,8 @@ int enqueue_mid_step5(vof2d_ctx* h) {
   { StreamScope on(h, h->cstream); tm5_tm<T>(h, h->istep, 1); }
   if ((rc = comm_post(h, VOF_XCHG_F | VOF_XCHG_US | VOF_XCHG_VS | VOF_XCHG_RHS | VOF_XCHG_P, /*f_in_twin=*/true, 1, /*s_in_alt=*/true, /*on_cstream=*/true, /*shallow=*/true))) return rc;
   tm5_tm<T>(h, h->istep, 2);
-  swap_F(h);
-  swap_S(h);
+  h->views.swap_F();
+  h->views.swap_S();
   return comm_join(h);
 }
 // the last step of a call: mode 4's step without its k_momentum (u, v reach memory here)
@@ -312,7 +312,7 @@ int step_exchange_mode5(vof2d_ctx* h, int64_t nsteps) {
   auto eager_mid = [&] { h->xchg_steps += 1; return mid_step(); };
   if (mid & 1) { if ((rc = eager_mid())) return rc; mid -= 1; }
   while (mid > 0) {
-    hipGraphExec_t& exec = h->graphs.xchg5[xchg5_key(h)];
+    hipGraphExec_t& exec = h->graphs.slot(graph_key(h, gXchg5, (int)((h->istep + 1) & 1)));
     if (want_graph && h->xchg5_graph && !exec &&
         (rc = capture_exchange_or_switch_off(h, &exec, &h->xchg5_graph, "two middle steps of mode 5", "eager", [&] { const int r2 = mid_step(); return r2 ? r2 : mid_step(); })))
       return rc;
@@ -338,7 +338,7 @@ int step_exchange_mode5(vof2d_ctx* h, int64_t nsteps) {
 // nsteps steps of overlap mode 0, 1, 3 or 4, each with its exchanges
 int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
   const bool want_graph = !(h->d.flags & VOF_FLAG_NO_GRAPH);
-  GraphCache& G = h->graphs;
+  auto& G = h->graphs;
   auto one_step = [&]() -> int {
     int r2 = VOF_OK;
     DISPATCH_T(h, r2 = enqueue_step_exchange<double>(h, overlap), r2 = enqueue_step_exchange<float>(h, overlap));
@@ -350,7 +350,8 @@ int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
     const StepPlan p = strip_step_plan(h, want_graph && h->xchg_graph && h->xchg_steps > 0);
     if (!p.virt) settle_ghosts(h);
     h->istep += 1;   // (behind settle_ghosts here, in front of it in step_loop: settle_ghosts does not look at istep)
-    const int par = (int)(h->istep & 1), ori = ori_F(h);
+    const int par = (int)(h->istep & 1);
+    const GraphKey one = graph_key(h, gXchg, overlap * 2 + par), next = {gXchg, one.views ^ FieldViews::kF, one.variant ^ 1};   // this step's graph, and (mode 4) the next step's
     int rc;
     // The first step of a communicator runs eagerly: RCCL sets its peer connections up on first
     // use, which must not happen inside a capture.  After that the whole step -- kernels on the
@@ -360,16 +361,17 @@ int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
     // Two mode-4 steps per graph launch (a graph launch leaves ~9 us of idle queue behind it, see step.h):
     // only once both single-step graphs of this handle exist, i.e. this RCCL has shown that it can be
     // captured; two steps return the F / twin pair and the parity to where they were.
-    if (p.captured && overlap == 4 && h->xchg_pair && p.virt && nsteps - s >= 2 && G.xchg[par][4][ori] && G.xchg[par ^ 1][4][ori ^ 1]) {
-      if (!G.xchg2[par][ori] &&
-          (rc = capture_exchange_or_switch_off(h, &G.xchg2[par][ori], &h->xchg_pair, "two steps + exchanges", "one step per launch (those graphs are known to work)", [&] {
+    if (p.captured && overlap == 4 && h->xchg_pair && p.virt && nsteps - s >= 2 && G.find(one) && G.find(next)) {
+      hipGraphExec_t& two = G.slot(graph_key(h, gXchg2, par));
+      if (!two &&
+          (rc = capture_exchange_or_switch_off(h, &two, &h->xchg_pair, "two steps + exchanges", "one step per launch (those graphs are known to work)", [&] {
              const int r2 = one_step();
              h->istep += 1;
              return r2 ? r2 : one_step();
            })))
         return rc;
-      if (G.xchg2[par][ori]) {
-        HIPCHK(h, hipGraphLaunch(G.xchg2[par][ori], h->stream));
+      if (two) {
+        HIPCHK(h, hipGraphLaunch(two, h->stream));
         h->istep += 1;
         s += 1;
         h->xchg_steps += 2;
@@ -379,11 +381,11 @@ int step_exchange(vof2d_ctx* h, int64_t nsteps, int overlap) {
       }
     }
     if (p.captured) {
-      hipGraphExec_t& exec = G.xchg[par][overlap][ori];
+      hipGraphExec_t& exec = G.slot(one);
       if (!exec && (rc = capture_exchange_or_switch_off(h, &exec, &h->xchg_graph, "step + exchanges", "eager", one_step))) return rc;
       if (exec) {
         HIPCHK(h, hipGraphLaunch(exec, h->stream));
-        if (overlap == 4) swap_F(h);   // the fused transport swaps the F / twin pair once per step
+        if (overlap == 4) h->views.swap_F();   // the fused transport swaps the F / twin pair once per step
         h->xchg_steps += 1;
         h->xchg_graph_steps += 1;
         finish_step(h->state, p);

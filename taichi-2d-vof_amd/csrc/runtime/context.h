@@ -19,6 +19,7 @@
 #include "../../../include/vof2d.h"
 #include "../vof2d_kernels.h"
 #include "state.h"
+#include "views.h"
 #include "buffers.h"
 
 using namespace vof;
@@ -126,35 +127,13 @@ bool divisors_ok(const ConstsD& s) {
 
 }  // namespace
 
-// Every captured graph of a handle (runtime/graphs.h captures them; ori: ori_F).  Nothing but exec handles, so the whole
-// cache, and the part of it whose graphs captured send / recv nodes, are flat ranges of them.
-struct GraphCache {
-  static constexpr int kStepBatches = 3;
-  hipGraphExec_t step[2][2] = {};                      // whole step, [istep parity][ori]
-  // several consecutive steady-state steps of a full domain as ONE graph (step_batch[b] steps, an even number: the
-  // F / twin pair and the step parity are back where they started): a graph launch leaves ~9 us of idle queue
-  // behind it, which one launch per step pays every step (step.h)
-  hipGraphExec_t batch[2][kStepBatches][2][2] = {};    // [form: 0 chains or the plain sequence, 1 k_tm][batch size][parity of the first step][ori]
-  hipGraphExec_t phase[5] = {};                        // phase 0, then phases 1, 2 x istep parity (slot 2 * phase - 1 + parity)
-  hipGraphExec_t mg = nullptr;                         // one V-cycle of vof_solve_p_mg (runtime/multigrid.h keeps what it was captured for)
-  hipGraphExec_t step_mg[2][2] = {};                   // whole step of vof_step_mg, [istep parity][ori] (runtime/step.h keeps what they were captured for)
-  // ---- from here on: with the exchanges of a strip (they hold the communicator: clear_exchange)
-  hipGraphExec_t xchg[2][5][2] = {};                   // whole step + exchanges, [istep parity][overlap mode][ori]
-  hipGraphExec_t xchg2[2][2] = {};                     // TWO mode-4 steps + exchanges per launch, [parity of the first][ori] (comm.h)
-  hipGraphExec_t xchg5[16] = {};                       // TWO middle steps of mode 5 per launch, [xchg5_key]
-
-  hipGraphExec_t* begin() { return &step[0][0]; }
-  hipGraphExec_t* end() { return xchg5 + 16; }
-  static bool any(hipGraphExec_t* a, hipGraphExec_t* b) { while (a != b && !*a) ++a; return a != b; }
-  static void clear(hipGraphExec_t* a, hipGraphExec_t* b) {
-    for (; a != b; ++a)
-      if (*a) { (void)hipGraphExecDestroy(*a); *a = nullptr; }
-  }
-  bool any() { return any(begin(), end()); }
-  void clear() { clear(begin(), end()); }
-  void clear_exchange() { clear(&xchg[0][0][0], end()); }
+// How a captured graph leaves the handle's store (GraphStore, runtime/views.h; the keys: runtime/graphs.h)
+struct vof2d_ctx;
+struct GraphDestroy {
+  vof2d_ctx* h;
+  void quiesce() const;   // waits for the streams of the handle a graph may still be replaying on (below the handle)
+  void operator()(hipGraphExec_t e) const { (void)hipGraphExecDestroy(e); }
 };
-static_assert(sizeof(GraphCache) == (4 + 4 * GraphCache::kStepBatches * 2 + 5 + 1 + 4 + 20 + 4 + 16) * sizeof(hipGraphExec_t), "GraphCache is walked as one array");
 
 // knob "fuse_tm" = -2 (exploration): both forms of the batch graphs timed on the handle's own data (tune_next_is_timed, step.h);
 // `choice` and `decided` also carry what the rule of fuse_tm = -1 found (decide_batch_form_by_rule)
@@ -191,7 +170,8 @@ struct vof2d_ctx {
   int nty;        // y-sweep tiles
   size_t field_elems;
   char* arena = nullptr;
-  void* fld[NFIELDS];
+  FieldViews views;                              // which buffer each field id names, and the four swaps (runtime/views.h)
+  const FieldViews::Table& fld = views.table();  // ... read as h->fld[id]
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int device = 0;
@@ -211,11 +191,7 @@ struct vof2d_ctx {
   int mg_nu = 2;                // knob "mg_nu": sweeps before and after the coarser levels
   int mg_levels = -1;           // knob "mg_levels": cap on the depth of a cycle (-1: none)
   int mg_graph = 1;             // knob "mg_graph": 0 launches every kernel of a cycle itself instead of replaying the captured cycle
-  void* mg_key[3] = {nullptr, nullptr, nullptr};   // p, pt, rhs the cached cycle was captured with
   int mg_coarse_block = 0;      // knob "mg_coarse_block": the coarsest-level solve as one launch of one workgroup (k_mg_coarse_block) where the level is small enough
-  // vof_step_mg (runtime/step.h): what the step graphs were captured for
-  void* step_mg_key[NFIELDS] = {};   // the field views (F and its twin apart: the graphs are keyed by the orientation)
-  int step_mg_cycles = 0, step_mg_crit = 0;
   double* iface_part = nullptr;   // vof_interface (runtime/interface.h): the block partials, then the summary, behind the counts in buf.iface_work
   // vof_blobs (runtime/blobs.h): the blob index of every root, the root counts, the 8 doubles behind the labels in buf.blob_work
   int* blob_idx = nullptr;
@@ -257,12 +233,11 @@ struct vof2d_ctx {
   int band_rows = 4;       // rows per wave chunk of the edge-band launch of the fused transport (strips)
   int buf_stores = 7;      // range-checked buffer stores where the grid allows (buffer_stores_ok): bit 0 k_momentum, bit 1 k_jacobi_tb, bit 2 k_tm's momentum wave
   int virtual_ghosts = 1;  // ... without the step's set_BC launch (k_momentum forms the ghost cells it reads)
-  void* f_home = nullptr;  // the buffer fld[fF] pointed to at creation (orientation of the F / twin pair)
-  void* us_home = nullptr; // ... fld[fUS] (the u*, v* pair alternates with mx, my in the k_tm forms) and fld[fP] (k_jacobi_pair alternates p / pt)
-  void* p_home = nullptr;
-  int phase_graph_ori = 0; // orientation the phase graphs were captured in
-  GraphCache graphs;
-  static constexpr int kStepBatches = GraphCache::kStepBatches;
+  GraphStore<hipGraphExec_t, GraphDestroy> graphs{GraphDestroy{this}};   // every captured graph of the handle
+  // several consecutive steady-state steps of a full domain as ONE graph (step_batch[b] steps, an even number: the
+  // F / twin pair and the step parity are back where they started): a graph launch leaves ~9 us of idle queue
+  // behind it, which one launch per step pays every step (step.h)
+  static constexpr int kStepBatches = 3;
   static constexpr int kTuneBatch = 1;     // the batch size the two forms are timed with (fuse_tm = -2)
   // (the k_tm form has one plain k_momentum and one plain k_transport per batch: 4096^2 0.5256 ms/step in batches of 8, 0.5193 of 16,
   // 0.5178 of 32, 0.5346 of 4; knob "batch_steps" sets the first)
@@ -327,6 +302,11 @@ struct vof2d_ctx {
   int peer_lo = -1, peer_hi = -1;  // ranks owning the rows below own_lo / above own_hi (-1: wall)
   char err[512];
 };
+
+inline void GraphDestroy::quiesce() const {
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->cstream) (void)hipStreamSynchronize(h->cstream);   // (the chains of a batch graph join the handle's stream inside it)
+}
 
 namespace {
 

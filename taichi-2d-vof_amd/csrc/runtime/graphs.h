@@ -1,4 +1,4 @@
-// runtime/graphs.h -- the keys of the graph cache (GraphCache, context.h) and the one way a graph is captured
+// runtime/graphs.h -- the keys of the handle's graph store (GraphStore, views.h) and the one way a graph is captured
 //
 // Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
@@ -6,13 +6,16 @@
 
 namespace {
 
-// Graphs bake the field pointers in, so they are keyed by which buffer of a pair the host's view calls the first:
-// 0 where F is in the buffer it had at creation, 1 where it is in its twin
-inline int ori_F(const vof2d_ctx* h) { return h->fld[fF] == h->f_home ? 0 : 1; }
-// the middle steps of mode 5 move all three pairs: parity of the first step | F / twin << 1 | (u*, v*) / (mx, my) << 2 | p / pt << 3
-inline int xchg5_key(const vof2d_ctx* h) {
-  return (int)((h->istep + 1) & 1) | (ori_F(h) << 1) | ((h->fld[fUS] == h->us_home ? 0 : 1) << 2) | ((h->fld[fP] == h->p_home ? 0 : 1) << 3);
-}
+// Graphs bake the field pointers in: every key carries the handle's current views (runtime/views.h).  variant is what the
+// kind bakes in besides them, and nothing else:
+//   gStep    parity of the step                gPhase   0 for phase 0, else 2 * phase - 1 + parity
+//   gBatch   batch_variant (below)             gMg      0
+//   gStepMg  (cycles * 2 + criterion) * 2 + parity
+//   gXchg    overlap mode * 2 + parity         gXchg2, gXchg5   parity of the first step
+inline GraphKey graph_key(const vof2d_ctx* h, int kind, int variant = 0) { return {kind, h->views.bits(), variant}; }
+// form: 0 chains or the plain sequence, 1 k_tm; b: the batch size step_batch[b]; first: the batch's first step
+inline int batch_variant(int form, int b, int64_t first) { return (form * vof2d_ctx::kStepBatches + b) * 2 + (int)(first & 1); }
+inline int batch_form_of(const GraphKey& k) { return k.variant / (2 * vof2d_ctx::kStepBatches); }
 
 // Captures what `enqueue` launches on h->stream (it returns false if something could not be enqueued) and instantiates
 // it into *exec.  A capture enqueues nothing, but enqueueing runs the host-side swaps of the field views and may move
@@ -24,8 +27,7 @@ inline int xchg5_key(const vof2d_ctx* h) {
 template <typename Enqueue>
 hipError_t capture_graph(vof2d_ctx* h, hipStreamCaptureMode mode, bool upload, hipGraphExec_t* exec, Enqueue&& enqueue) {
   *exec = nullptr;
-  void* keep[NFIELDS];
-  memcpy(keep, h->fld, sizeof(keep));
+  const FieldViews views = h->views;
   const int64_t istep = h->istep;
   hipStream_t const stream = h->stream;
   hipError_t e = hipStreamBeginCapture(stream, mode);
@@ -33,7 +35,7 @@ hipError_t capture_graph(vof2d_ctx* h, hipStreamCaptureMode mode, bool upload, h
   const bool enqueued = enqueue();
   hipGraph_t graph = nullptr;
   e = hipStreamEndCapture(stream, &graph);
-  memcpy(h->fld, keep, sizeof(keep));
+  h->views = views;
   h->istep = istep;
   if (e == hipSuccess && !(enqueued && graph)) e = hipErrorUnknown;
   if (e == hipSuccess) e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);

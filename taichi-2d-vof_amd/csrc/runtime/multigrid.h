@@ -148,15 +148,11 @@ int mg_cycles(vof2d_ctx* h, int n) {
     for (int k = 0; k < n; ++k) DISPATCH_T(h, mg_enqueue_cycle<double>(h), mg_enqueue_cycle<float>(h));
     return ensure_ok(h);
   }
-  void* const key[3] = {h->fld[fP], h->fld[fPT], h->fld[fRHS]};   // a graph bakes its pointers in, and the views move
-  if (h->graphs.mg && memcmp(key, h->mg_key, sizeof(key)) != 0) GraphCache::clear(&h->graphs.mg, &h->graphs.mg + 1);
-  if (!h->graphs.mg) {
-    const int rc = capture_or_fail(h, true, &h->graphs.mg, "the multigrid cycle",
-                                   [&] { DISPATCH_T(h, mg_enqueue_cycle<double>(h), mg_enqueue_cycle<float>(h)); });
-    if (rc) return rc;
-    memcpy(h->mg_key, key, sizeof(key));
-  }
-  for (int k = 0; k < n; ++k) HIPCHK(h, hipGraphLaunch(h->graphs.mg, h->stream));
+  hipGraphExec_t& exec = h->graphs.slot(graph_key(h, gMg));   // (a graph bakes its pointers in, and the views move: the key)
+  int rc;
+  if (!exec && (rc = capture_or_fail(h, true, &exec, "the multigrid cycle", [&] { DISPATCH_T(h, mg_enqueue_cycle<double>(h), mg_enqueue_cycle<float>(h)); })))
+    return rc;
+  for (int k = 0; k < n; ++k) HIPCHK(h, hipGraphLaunch(exec, h->stream));
   return VOF_OK;
 }
 

@@ -7,16 +7,10 @@
 
 namespace {
 
-void swap_F(vof2d_ctx* h) {
-  void* t = h->fld[fF];
-  h->fld[fF] = h->fld[fF2];
-  h->fld[fF2] = t;
-}
-
 template <typename T, bool POST, bool CORR = false>
-void sweep_x(vof2d_ctx* h) { L<T>::template fct_x<POST, CORR>(h); swap_F(h); }
+void sweep_x(vof2d_ctx* h) { L<T>::template fct_x<POST, CORR>(h); h->views.swap_F(); }
 template <typename T, bool POST, bool CORR = false>
-void sweep_y(vof2d_ctx* h) { L<T>::template fct_y<POST, CORR>(h); swap_F(h); }
+void sweep_y(vof2d_ctx* h) { L<T>::template fct_y<POST, CORR>(h); h->views.swap_F(); }
 inline StripRows strip_rows(const vof2d_ctx* h) {
   return vof::strip_rows(h->d.row_lo, h->d.row_hi, h->d.own_lo, h->d.own_hi, h->d.nx, h->d.jacobi_iters);
 }
@@ -143,7 +137,7 @@ void enqueue_phase(vof2d_ctx* h, int phase, int64_t istep, bool merge_bc = false
     if (!merge_bc && !lean) L<T>::template set_bc<BC_UV>(h);  // u, v part of :525
   } else {
     final_sweep<T>(h, /*along_x=*/y_first);  // second sweep, :527 fused, on the owned rows
-    swap_F(h);
+    h->views.swap_F();
     if (lean) return;                       // the caller's single set_bc<u,v,F,p> follows
     // F part of :528 on the rows this handle produced; a strip's halo rows arrive with the
     // sender's ghost columns (and may be arriving right now)
@@ -166,7 +160,7 @@ void enqueue_step(vof2d_ctx* h, int64_t istep, bool lean = false, bool virt = fa
     if (mg) mg_enqueue_step_solve<T>(h, mg->cycles, mg->criterion);
     else jacobi_n<T>(h, h->d.jacobi_iters, false, (int)(istep & 1));
     L<T>::transport(h, istep % 2 == 0);
-    swap_F(h);
+    h->views.swap_F();
     if (!virt) L<T>::template set_bc<BC_ALL>(h);
     return;
   }
@@ -190,16 +184,6 @@ constexpr int kHalvesDrift = 8;
 // Measured (tools/probes/halves_sweep.py, ms/step off -> on): 4096^2 fp64 dam-break 0.579 -> 0.560 (late) / 0.592 -> 0.562
 // (front), bubble 0.694 -> 0.622, 4096^2 fp32 0.367 -> 0.339, 8192^2 2.30 -> 2.24, 3072^2 0.353 -> 0.344, 2560^2 0.261 -> 0.251;
 // 2048^2 fp64 0.172 -> 0.190 and 1024^2 0.087 -> 0.097 (half launches too small to fill the chip): on from 6 M cells and 1024 rows per chain.
-inline void swap_S(vof2d_ctx* h) {
-  void* t = h->fld[fUS]; h->fld[fUS] = h->fld[fMX]; h->fld[fMX] = t;
-  t = h->fld[fVS]; h->fld[fVS] = h->fld[fMY]; h->fld[fMY] = t;
-}
-// ... and rhs with the (otherwise verb-only) kappa array: the chained k_tm batches, whose every launch leaves the
-// previous step's u*, v*, rhs intact beside the next step's (enqueue_steps_tm)
-inline void swap_SR(vof2d_ctx* h) {
-  swap_S(h);
-  void* t = h->fld[fRHS]; h->fld[fRHS] = h->fld[fKAPPA]; h->fld[fKAPPA] = t;
-}
 inline bool tm_eligible(const vof2d_ctx* h) {
   return h->fuse_tm != 0 && h->g.wall_lo && h->g.wall_hi && h->fuse_transport && h->tb >= 5 && h->d.jacobi_iters % 5 == 0 &&
          h->d.jacobi_iters / 5 % 2 == 0 && h->g.nx >= 16;
@@ -309,7 +293,7 @@ bool enqueue_steps_halves(vof2d_ctx* h, int64_t first_step, int K) {
       const RowSegments rr = row_segments(row_seg(a, b, L<T>::transport_rows(h)));
       L<T>::transport(h, istep % 2 == 0, &rr);
     });
-    swap_F(h);
+    h->views.swap_F();
   }
   for (int p = 1; p < P; ++p)
     ok = ok && hipEventRecord(ev_join[p - 1], st[p]) == hipSuccess && hipStreamWaitEvent(st[0], ev_join[p - 1], 0) == hipSuccess;
@@ -324,18 +308,17 @@ bool enqueue_steps_halves(vof2d_ctx* h, int64_t first_step, int K) {
 // arrays -- (mx, my, kappa), verb-only otherwise -- and the host's view of the sets alternates: after an even number of
 // steps the view is where it was, holding step K + 1's predictor, and the other set still holds step K's -- what the
 // reference's u_star, v_star, rhs hold after K steps (settle_ahead copies it over when somebody asks).
-inline void swap_P(vof2d_ctx* h) { void* t = h->fld[fP]; h->fld[fP] = h->fld[fPT]; h->fld[fPT] = t; }
 // the step's Jacobi sweeps inside a batch: pairs of five-sweep launches as k_jacobi_pair where the handle allows (each
 // leaves its result in the other array of the p / pt pair: the host's view is swapped along, an even number of times
 // per batch of an even number of steps; an odd count per step -- the middle steps of a strip in overlap mode 5 -- leaves it
-// swapped: the exchange graphs are keyed by it), else the k_jacobi_tb launches of jacobi_n, ending in fld[fP], on the work plan
+// swapped: every graph is keyed by it), else the k_jacobi_tb launches of jacobi_n, ending in fld[fP], on the work plan
 // of parity tb_par (-1: uniform chunks)
 template <typename T>
 void batch_jacobi(vof2d_ctx* h, int par, int tb_par) {
   if (!L<T>::jacobi_pair_ok(h)) return jacobi_n<T>(h, h->d.jacobi_iters, false, tb_par);
   for (int j = 0; j < h->d.jacobi_iters / 10; ++j) {
     L<T>::jacobi_pair(h, fP, fPT, par);
-    swap_P(h);
+    h->views.swap_P();
   }
 }
 template <typename T>
@@ -346,10 +329,10 @@ void enqueue_steps_tm(vof2d_ctx* h, int64_t first_step, int K) {
     const int par = (int)(istep & 1);
     batch_jacobi<T>(h, par, par);
     L<T>::tm(h, istep % 2 == 0, /*store_uv=*/k == K - 1, par ^ 1, plan_for, /*rhs_id=*/fKAPPA);   // (swap_SR alternates rhs with the kappa array)
-    swap_SR(h);
-    swap_F(h);
+    h->views.swap_SR();
+    h->views.swap_F();
   }
-  if (plan_for == PlanFor::kJacobiPair && ((K * (h->d.jacobi_iters / 10)) & 1)) swap_P(h);   // (never: K is even)
+  if (plan_for == PlanFor::kJacobiPair && ((K * (h->d.jacobi_iters / 10)) & 1)) h->views.swap_P();   // (never: K is even)
   // (K swaps, an even number: the host's view of the pairs is back where it was)
 }
 // the one k_momentum launch in front of the first batch of a chain (its planner block plans the geometry of the Jacobi
@@ -433,25 +416,11 @@ void destroy_graphs(vof2d_ctx* h) {
   for (int b = 0; b < vof2d_ctx::kStepBatches; ++b) h->halves_captured[b] = false;
   h->batching = true;   // (a parameter change may be what a capture tripped over: try again)
 }
-// A single sweep swaps F with its twin, so field pointers baked into captured graphs go stale: drop the graphs.
+// A single sweep swaps F with its twin.  Every graph is keyed by the views, so none of them could be replayed against the
+// swapped pair; they are dropped all the same, as they always were: with them goes the batch form the rule chose, which is
+// decided again on the F the sweeps have moved (destroy_graphs).
 void sweep_swapped(vof2d_ctx* h) {
-  if (!h->graphs.any()) return;
-  (void)hipStreamSynchronize(h->stream);
-  destroy_graphs(h);
-}
-// The phase graphs bake the F / twin pointers in and assume the pair returns to the same orientation
-// after every step (two swaps).  The fused transport swaps once per step, so a handle that mixes
-// the entry points may arrive here with the pair the other way round: drop those graphs then
-// (they are re-captured on use).  The step and exchange graphs are keyed by the orientation.
-int match_phase_graph_orientation(vof2d_ctx* h) {
-  GraphCache& G = h->graphs;
-  if (ori_F(h) == h->phase_graph_ori) return VOF_OK;
-  if (GraphCache::any(G.phase, G.phase + 5)) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    GraphCache::clear(G.phase, G.phase + 5);
-  }
-  h->phase_graph_ori = ori_F(h);
-  return VOF_OK;
+  if (h->graphs.any()) destroy_graphs(h);
 }
 
 }  // namespace

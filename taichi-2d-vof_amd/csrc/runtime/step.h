@@ -99,13 +99,12 @@ int batch_steps(const vof2d_ctx* h, int variant, int b) {
 // failure on the way switches the form off for the handle and leaves the other form, the single-step graphs (or eager
 // launches) to carry on: never an error of vof_step.
 void build_step_batches(vof2d_ctx* h, int variant) {
-  auto& GB = h->graphs.batch[variant];
   bool ok = true;
   for (int c = 0; c < 2 && ok; ++c) {
-    if (c) swap_F(h);                                   // the pair as the NEXT step will find it
+    if (c) h->views.swap_F();                                   // the pair as the NEXT step will find it
     const int64_t first = h->istep + c;
     for (int b = 0; b < vof2d_ctx::kStepBatches && ok; ++b) {
-      hipGraphExec_t& slot = GB[b][(int)(first & 1)][ori_F(h)];
+      hipGraphExec_t& slot = h->graphs.slot(graph_key(h, gBatch, batch_variant(variant, b, first)));
       if (slot) continue;
       const int K = batch_steps(h, variant, b);
       const bool chains = !variant && halves_eligible(h, K) && halves_prepare(h, K);
@@ -121,11 +120,11 @@ void build_step_batches(vof2d_ctx* h, int variant) {
         return enq;
       }) == hipSuccess;
     }
-    if (c) swap_F(h);
+    if (c) h->views.swap_F();
   }
   if (!ok) {
     (void)hipGetLastError();
-    GraphCache::clear(&GB[0][0][0], &GB[0][0][0] + vof2d_ctx::kStepBatches * 4);
+    h->graphs.clear_if([variant](const GraphKey& k) { return k.kind == gBatch && batch_form_of(k) == variant; });
     // the k_tm form failing leaves the other form's batch graphs in use; only when those fail is it one graph launch per step
     if (variant) h->tm_broken = true; else h->batching = false;
     if (getenv("VOF2D_DEBUG")) fprintf(stderr, "[vof2d] step batches (%s) could not be captured: %s\n", variant ? "k_tm form" : "chains / plain",
@@ -141,21 +140,22 @@ void build_step_batches(vof2d_ctx* h, int variant) {
 // *ran: the steps the launch ran, 0 if no batch fits (or batching is off): the step is then run on its own.
 int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
   *ran = 0;
-  const int par = (int)(h->istep & 1), ori = ori_F(h);
+  const int par = (int)(h->istep & 1);
   bool timed = false;
   int variant = batch_form(h, true, remaining, &timed);
-  if (h->batching && !h->graphs.batch[variant][0][par][ori]) {
+  auto batch = [&](int form, int b) { return h->graphs.find(graph_key(h, gBatch, batch_variant(form, b, h->istep))); };
+  if (h->batching && !batch(variant, 0)) {
     build_step_batches(h, variant);
     if (variant && h->tm_broken) {
       variant = 0; timed = false;
-      if (h->batching && !h->graphs.batch[0][0][par][ori]) build_step_batches(h, 0);
+      if (h->batching && !batch(0, 0)) build_step_batches(h, 0);
     }
   }
-  auto& GB = h->graphs.batch[variant];
   TuneState& t = h->tune;
   for (int b = timed ? vof2d_ctx::kTuneBatch : 0; b < vof2d_ctx::kStepBatches; ++b) {   // (while the forms are being timed: batches of the timed size)
     const int K = batch_steps(h, variant, b);
-    if (remaining < K || !GB[b][par][ori]) continue;
+    hipGraphExec_t const exec = batch(variant, b);
+    if (remaining < K || !exec) continue;
     const bool time_it = timed && b == vof2d_ctx::kTuneBatch && h->batching;
     if (time_it) {
       for (int k = 0; k < 2; ++k)
@@ -169,7 +169,7 @@ int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
       else DISPATCH_T(h, enqueue_tm_head<double>(h, par), enqueue_tm_head<float>(h, par));
       h->state.ahead = true;
     } else h->state.ahead = false;
-    if (hipGraphLaunch(GB[b][par][ori], h->stream) != hipSuccess) return fail(h, VOF_EHIP, "hipGraphLaunch of a step batch");
+    if (hipGraphLaunch(exec, h->stream) != hipSuccess) return fail(h, VOF_EHIP, "hipGraphLaunch of a step batch");
     if (time_it) {
       if (hipEventRecord(t.ev[2 * t.n + 1], h->stream) == hipSuccess) t.n += 1;
       else (void)hipGetLastError();   // (the batch ran: this timing is lost, the steps are not)
@@ -182,18 +182,18 @@ int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
   }
   return VOF_OK;
 }
-// 2. From the step's own graph, captured on first use.  Graphs bake the field pointers in: one per (parity, which buffer
-// of the F / twin pair holds F).  The two-kernel transport swaps the pair twice per step, the fused one once.
+// 2. From the step's own graph, captured on first use.  Graphs bake the field pointers in: one per (parity, field
+// views: graph_key).  The two-kernel transport swaps the pair twice per step, the fused one once.
 int run_step_graph(vof2d_ctx* h, bool virt) {
   h->state.ahead = false;   // (this step forms its own predictor, into the host's view of u*, v*, rhs)
-  hipGraphExec_t& exec = h->graphs.step[(int)(h->istep & 1)][ori_F(h)];
+  hipGraphExec_t& exec = h->graphs.slot(graph_key(h, gStep, (int)(h->istep & 1)));
   int rc;
   if (!exec && (rc = capture_or_fail(h, /*upload=*/true, &exec, "the step graph", [&] {
         DISPATCH_T(h, enqueue_step<double>(h, h->istep, true, virt), enqueue_step<float>(h, h->istep, true, virt));
       })))
     return rc;
   HIPCHK(h, hipGraphLaunch(exec, h->stream));
-  if (h->g.wall_lo && h->g.wall_hi && h->fuse_transport) swap_F(h);     // keep the host's view in step with what the replayed kernels did
+  if (h->g.wall_lo && h->g.wall_hi && h->fuse_transport) h->views.swap_F();     // keep the host's view in step with what the replayed kernels did
   return VOF_OK;
 }
 // 3. Eagerly, launch by launch: the first step after set_init_F / from_numpy / a single verb (lean = false: the schedule with
@@ -235,32 +235,18 @@ int step_n(vof2d_ctx* h, int64_t nsteps) {
 }
 
 // ---- vof_step_mg: the same three ways minus the batches, the step's sweeps replaced by `cycles` V-cycles (enqueue_step
-// with a StepMg).  The step graphs bake in every field view, the cycle count and the criterion of the record: they are
-// dropped when one of those changes (F and its twin apart: the slots are keyed by the orientation), and with every
-// other graph when a knob does (destroy_graphs).
+// with a StepMg).  The step graphs bake in the cycle count and the criterion of the record beside the views: both are in
+// the key (at most GraphStore::kCap of them stay), and the graphs go with every other when a knob changes (destroy_graphs).
 int run_step_mg_graph(vof2d_ctx* h, bool virt, const StepMg& mg) {
   h->state.ahead = false;   // (see run_step_graph; settled in front of the loop: step_mg_n)
-  GraphCache& G = h->graphs;
-  void* key[NFIELDS];
-  memcpy(key, h->fld, sizeof(key));
-  key[fF] = key[fF2] = nullptr;
-  if (GraphCache::any(&G.step_mg[0][0], &G.step_mg[0][0] + 4) &&
-      (memcmp(key, h->step_mg_key, sizeof(key)) != 0 || h->step_mg_cycles != mg.cycles || h->step_mg_crit != mg.criterion)) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    GraphCache::clear(&G.step_mg[0][0], &G.step_mg[0][0] + 4);
-  }
-  hipGraphExec_t& exec = G.step_mg[(int)(h->istep & 1)][ori_F(h)];
+  hipGraphExec_t& exec = h->graphs.slot(graph_key(h, gStepMg, (mg.cycles * 2 + mg.criterion) * 2 + (int)(h->istep & 1)));
   int rc;
-  if (!exec) {
-    if ((rc = capture_or_fail(h, /*upload=*/true, &exec, "the multigrid step graph", [&] {
-          DISPATCH_T(h, enqueue_step<double>(h, h->istep, true, virt, &mg), enqueue_step<float>(h, h->istep, true, virt, &mg));
-        })))
-      return rc;
-    memcpy(h->step_mg_key, key, sizeof(key));
-    h->step_mg_cycles = mg.cycles; h->step_mg_crit = mg.criterion;
-  }
+  if (!exec && (rc = capture_or_fail(h, /*upload=*/true, &exec, "the multigrid step graph", [&] {
+        DISPATCH_T(h, enqueue_step<double>(h, h->istep, true, virt, &mg), enqueue_step<float>(h, h->istep, true, virt, &mg));
+      })))
+    return rc;
   HIPCHK(h, hipGraphLaunch(exec, h->stream));
-  if (h->fuse_transport) swap_F(h);     // (a full domain: see run_step_graph)
+  if (h->fuse_transport) h->views.swap_F();     // (a full domain: see run_step_graph)
   return VOF_OK;
 }
 // nsteps steps; the record of the call into whichever of the three pointers are given (one 32-byte read-back at the end;
@@ -309,14 +295,14 @@ int step_phase(vof2d_ctx* h, int phase) {
     DISPATCH_T(h, enqueue_phase<double>(h, phase, h->istep), enqueue_phase<float>(h, phase, h->istep));
     return ensure_ok(h);
   }
-  hipGraphExec_t& exec = h->graphs.phase[phase == 0 ? 0 : 2 * phase - 1 + (int)(h->istep & 1)];
+  hipGraphExec_t& exec = h->graphs.slot(graph_key(h, gPhase, phase == 0 ? 0 : 2 * phase - 1 + (int)(h->istep & 1)));
   int rc;
   if (!exec && (rc = capture_or_fail(h, /*upload=*/false, &exec, "a phase graph", [&] {
         DISPATCH_T(h, enqueue_phase<double>(h, phase, h->istep), enqueue_phase<float>(h, phase, h->istep));
       })))
     return rc;
   HIPCHK(h, hipGraphLaunch(exec, h->stream));
-  if (phase == 1 || phase == 2) swap_F(h);   // keep the host's view of the F / twin buffers in step with what the replayed kernels did
+  if (phase == 1 || phase == 2) h->views.swap_F();   // keep the host's view of the F / twin buffers in step with what the replayed kernels did
   return VOF_OK;
 }
 

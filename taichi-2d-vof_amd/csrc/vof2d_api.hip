@@ -9,11 +9,12 @@
 // call into the runtime, what the call did to the handle's state (a call into runtime/state.h).  The runtime behind them:
 // They are included once, in the order of the #include lines below (each names the one before it; the diagnostic build adds
 // runtime/diag.h at the end):
-//   runtime/context.h    the handle (with its graph cache), constants, read_back
+//   runtime/context.h    the handle (with its field views and its graph store), constants, read_back
 //   runtime/buffers.h    DevBuf, the owner of a device allocation, and the handle's list of them; with runtime/carve.h, plain C++: the arenas cut into ranges
 //   runtime/state.h      plain C++: what the fields and ghost cells hold (FieldState), a field written from outside, the prologue and epilogue of a step, the phase order
+//   runtime/views.h      plain C++: which buffer each field id names and the four swaps that change it; the graphs captured against a view, kept by {kind, views, variant}
 //   runtime/launches.h   chunk-length heuristics, one launch wrapper per kernel (tile counts from the geometry in vof2d_device.h)
-//   runtime/graphs.h     the keys of the graph cache, the one capture helper
+//   runtime/graphs.h     what each kind of graph puts into its key, the one capture helper
 //   runtime/rows.h       plain C++: the owned rows of a strip, its edge bands, the rest; what a launch of one part gets; the cells a handle reports
 //   runtime/schedule.h   the per-step schedule, ghost-cell bookkeeping, dropping graphs
 //   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop of both
@@ -188,10 +189,7 @@ int vof_create(const vof2d_desc* d, void* stream, vof2d_handle* out) {
     const size_t bytes = h->field_elems * h->esz * NFIELDS;
     if (hipMalloc(reinterpret_cast<void**>(&h->arena), bytes) != hipSuccess) { rc = VOF_ENOMEM; break; }
     if (hipMemsetAsync(h->arena, 0, bytes, h->stream) != hipSuccess) { rc = VOF_EHIP; break; }
-    for (int k = 0; k < NFIELDS; ++k) h->fld[k] = h->arena + (size_t)k * h->field_elems * h->esz;
-    h->f_home = h->fld[fF];
-    h->us_home = h->fld[fUS];
-    h->p_home = h->fld[fP];
+    h->views = FieldViews(h->arena, h->field_elems * h->esz);
     if ((rc = h->buf.courant.reserve(h, 4 * sizeof(unsigned long long), "vof_create: no memory for the counters", true))) break;
     const size_t tbmask_bytes = (2 * TB_BANDS * (TB_COLS / 64) + 1 + kTbPlanWaves) * sizeof(unsigned long long);   // the mask words, then the plan
     if ((rc = h->buf.tbmask.reserve(h, tbmask_bytes, "vof_create: no memory for the work plan", true))) break;
@@ -344,8 +342,6 @@ int vof_step_phase(vof2d_handle h, int32_t phase) {
   if (!phase_is_next(h->state, phase)) return fail(h, VOF_ESTATE, "vof_step_phase must be called in the order 0, 1, 2");
   if (phase == 0) {
     settle_ghosts(h);
-    int rc = match_phase_graph_orientation(h);
-    if (rc) return rc;
     h->istep += 1;
   }
   phase_taken(h->state, phase);
@@ -1048,14 +1044,14 @@ int vof_step_tm_piece(vof2d_handle h, int32_t piece) {
   } else if (piece == 1) {
     h->istep += 1;
     DISPATCH_T(h, (tm5_jacobi<double>(h, (int)(h->istep & 1)), tm5_tm<double>(h, h->istep, 0)), (tm5_jacobi<float>(h, (int)(h->istep & 1)), tm5_tm<float>(h, h->istep, 0)));
-    swap_F(h);
-    swap_S(h);
+    h->views.swap_F();
+    h->views.swap_S();
   } else {
     h->istep += 1;
     const bool y_first = (h->istep % 2 == 0);
     DISPATCH_T(h, (jacobi_n<double>(h, h->d.jacobi_iters, false, -1), transport_part<double>(h, y_first, kAllOwned)),
                (jacobi_n<float>(h, h->d.jacobi_iters, false, -1), transport_part<float>(h, y_first, kAllOwned)));
-    swap_F(h);
+    h->views.swap_F();
     if (!h->virtual_ghosts) DISPATCH_T(h, L<double>::set_bc<BC_ALL>(h), L<float>::set_bc<BC_ALL>(h));
   }
   finish_step(h->state, strip_step_plan(h, true));   // (nothing was dirty: refused above)
