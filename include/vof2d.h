@@ -779,7 +779,9 @@ int vof_get_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, void*
 int vof_set_rows(vof2d_handle h, const char* name, int32_t g0, int32_t g1, const void* src,
                  size_t nbytes);
 /* device view for zero-copy halo exchange: element (i, j) lives at
- * base + ((i - row_lo) * pitch + col0 + j) * elem_size */
+ * base + ((i - row_lo) * pitch + col0 + j) * elem_size.  A write through the pointer is not seen by
+ * the handle: after a view of "F" or "F2" the handle keeps no zero maps for k_tm (knob
+ * f_zero_map has no effect on it any more), so that such a write is honoured as before. */
 int vof_field_view(vof2d_handle h, const char* name, void** base, int64_t* pitch, int64_t* col0,
                    int64_t* nrows);
 /* device-to-device copy of rows [g0, g1] of `name` from src into dst (same

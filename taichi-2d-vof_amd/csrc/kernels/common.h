@@ -196,6 +196,24 @@ __device__ __forceinline__ void load_buf(T (&c)[V], const T* base, int lane_off_
 #pragma unroll
   for (int q = 0; q < V; ++q) c[q] = k[q];
 }
+// the bit pattern of a cell, folded to one word that is 0 for +0.0 alone (a -0.0 is not)
+__device__ __forceinline__ unsigned bits_of(double x) { return (unsigned)__double2hiint(x) | (unsigned)__double2loint(x); }
+__device__ __forceinline__ unsigned bits_of(float x) { return __float_as_uint(x); }
+// One 32-bit word per lane through the same window (k_tm's zero map, kernels/fused_tm.h): the lanes' byte offsets in a VGPR -- kBufSkip
+// drops a lane's store and makes its load return 0 --, the row's byte offset wave-uniform.  As in store_buf_nt the row offset of a
+// store travels in the lane offsets.
+__device__ __forceinline__ unsigned load_buf_word(const unsigned* base, int lane_off_bytes, int row_off_bytes) {
+  row_off_bytes = __builtin_amdgcn_readfirstlane(row_off_bytes);
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(wave_uniform(const_cast<unsigned*>(base)), 0, kBufSkip, 0x00020000);
+  return __builtin_amdgcn_raw_buffer_load_b32(r, lane_off_bytes, row_off_bytes, 0);
+}
+__device__ __forceinline__ void store_buf_word(unsigned* base, int lane_off_bytes, int row_off_bytes, unsigned word) {
+  row_off_bytes = __builtin_amdgcn_readfirstlane(row_off_bytes);
+  lane_off_bytes += row_off_bytes;
+  asm volatile("" : "+v"(lane_off_bytes));
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(wave_uniform(base), 0, kBufSkip, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b32(word, r, lane_off_bytes, 0, 0);
+}
 template <typename T, int V>
 __device__ __forceinline__ T left_of(const Row<T, V>& w, int q) { return q == 0 ? w.l : w.c[q - 1]; }
 template <typename T, int V>

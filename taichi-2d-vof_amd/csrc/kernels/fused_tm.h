@@ -63,13 +63,15 @@ __device__ __forceinline__ void ring_get(Row<T, V>& w, const T (&row)[64 * V], i
 // waves issue one instruction at a time and wait for each other at every row); 93 % of the pairs of a 4096^2 grid.
 
 // ------------------------------------------------------------------ transport march (k_transport's, rows tra .. trb)
-template <typename T, int V, bool YFIRST, bool STORE_UV, bool BS, bool IN, int ABL>
+template <typename T, int V, bool YFIRST, bool STORE_UV, bool BS, bool IN, int ABL, bool ZMAP = false>
 __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T>& c, TmRing<T, V>& ring, const T* __restrict__ F,
                                                    T* __restrict__ Fn, const T* __restrict__ us, const T* __restrict__ vs,
                                                    const T* __restrict__ p, T* __restrict__ Uo, T* __restrict__ Vo,
                                                    unsigned long long* __restrict__ courant, int c0, int lane, int ma, int mb,
-                                                   WaveTimer& wt_) {
+                                                   WaveTimer& wt_, const ZeroMaps zm = ZeroMaps{nullptr, 0, 0, 0}, int tj = 0) {
   constexpr int W = TmGeom<V>::W, HF = TmGeom<V>::H;
+  static_assert(!ZMAP || (BS && ABL == 0), "the zero map goes with the buffer-store form of the product build");
+  constexpr bool ZSKIP = ZMAP && IN;   // the march that reads flags and drops loads and stores; every march of a ZMAP launch writes them
   // the transport wave is the one the momentum wave waits for: priority 1 (4096^2 fp64: 314 -> 299 us y first, 327 -> 305 x first;
   // the momentum wave instead: 314 / 333).  ABL_PRIO0 of the diagnostic build = without it.
   if constexpr ((ABL & ABL_PRIO0) == 0) __builtin_amdgcn_s_setprio(1);
@@ -107,6 +109,22 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
   // exact count that leaves the store in flight
   const T* const Fn_tile = Fn + (int64_t)(g.col0 + c0);
   const int voff_st = (j0 >= jlo && j0 + V - 1 <= jhi) ? lane * (int)(V * sizeof(T)) : kBufSkip;
+  // ZMAP (see ZeroMaps): the words of row i lie at byte (i - 1) * zm.stride * 4 of a map, tile tj's at + (tj + 1) * 4; both maps
+  // lie behind one base, so ONE load per row brings every word the next iteration looks at -- lanes 0, 1, 2: the source words of
+  // tiles tj - 1, tj, tj + 1 of the row it requests; every further lane: the destination word of the row it stores, four rows
+  // behind (the lanes' offsets differ by that constant; four rows of padding in front of the maps keep them from going negative).  Requested at the head of an iteration, in front of its row loads, and
+  // looked at behind its arithmetic: the two decisions are scalars by the next head.
+  const int zrow = ZMAP ? zm.stride * (int)sizeof(unsigned) : 0;
+  const int zoff_own = ZMAP ? zm.dst + (tj + 1) * (int)sizeof(unsigned) : 0;
+  const int zoff_ld = ZMAP ? (ZSKIP && lane < 3 ? zm.src + (tj + lane) * (int)sizeof(unsigned) : zoff_own - 4 * zrow) : 0;
+  const T* const F_tile = F + (int64_t)(g.col0 + c0);
+  unsigned zf = 0;
+  bool zskip_next = false, zdst_next = false;
+  if constexpr (ZSKIP) {
+    zf = load_buf_word(zm.base, zoff_ld, (t_lo + 1 - 1) * zrow);
+    zskip_next = __all(lane >= 3 || zf == 1u);
+        zdst_next = __builtin_amdgcn_readlane((int)zf, 3) == 1;
+  }
   unsigned int viol = 0;
   for (int t = t_lo; t <= t_hi; ++t) {
     if (t <= trb + 3) {
@@ -116,7 +134,17 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
       for (int q = 0; q < V; ++q) {
         Fr[q] = Fnx[q]; ur[q] = usnx[q]; vr[q] = vsnx[q]; pr[q] = pnx[q];
       }
-      if (BS || r < trb + 3) {
+      bool zdst_set = false;
+      if constexpr (ZSKIP) {
+        // row r + 1 of F is all +0 bits in every column the tile loads: the load touches no memory and returns those zeros
+        const bool zrow_src = zskip_next;
+        zdst_set = zdst_next;
+        zf = load_buf_word(zm.base, zoff_ld, (r + 2 - 1) * zrow);
+        load_buf<T, V>(Fnx, F_tile, zrow_src ? kBufSkip : lane * (int)(V * sizeof(T)), (int)((int64_t)(r + 1 - g.row_lo) * pitch * (int64_t)sizeof(T)), false);
+        load_s<T, V>(usnx, rowptr(us, r + 1));
+        load_s<T, V>(vsnx, rowptr(vs, r + 1));
+        load_c<T, V>(pnx, rowptr(p, r + 1));
+      } else if (BS || r < trb + 3) {
         load_c<T, V>(Fnx, rowptr(F, r + 1));
         load_s<T, V>(usnx, rowptr(us, r + 1));
         load_s<T, V>(vsnx, rowptr(vs, r + 1));
@@ -168,10 +196,26 @@ __device__ __forceinline__ void tm_transport_march(const Geom& g, const Consts<T
       const bool st = io >= ma && io <= mb;
       if constexpr ((ABL & ABL_NO_STORE) != 0) {
         asm volatile("" :: "v"(out[0]), "v"(out[V - 1]));
+      } else if constexpr (ZMAP) {
+        // the segment's flag in the destination map, by lane 0 of the wave that stores the segment: 1 where every stored cell
+        // is +0 bit for bit, else 0 ("unknown").  Where the interior march finds the flag already standing over such a
+        // segment, memory holds these zeros: the store is dropped.
+        unsigned nz = 0;
+#pragma unroll
+        for (int q = 0; q < V; ++q) nz |= bits_of(out[q]);
+        const bool zout = __all(voff_st == kBufSkip || nz == 0);   // (over the lanes that store)
+        // (lane 3 stores: its offset is the destination word's four rows behind, (io - 1) + 4 = r rows on)
+        store_buf_word(zm.base, (st && lane == 3) ? zoff_ld : kBufSkip, st ? r * zrow : 0, zout ? 1u : 0u);
+        const bool wr = st && !(zout && zdst_set);
+        store_buf_nt<T, V>(Fn_tile, wr ? voff_st : kBufSkip, st ? (int)((int64_t)(io - g.row_lo) * pitch * (int64_t)sizeof(T)) : 0, out);
       } else if constexpr (BS) {
         store_buf_nt<T, V>(Fn_tile, st ? voff_st : kBufSkip, st ? (int)((int64_t)(io - g.row_lo) * pitch * (int64_t)sizeof(T)) : 0, out);
       } else if (st) {
         store_s<T, V>(Fn + at(g, io, j0), out, j0, jlo, jhi);
+      }
+      if constexpr (ZSKIP) {
+        zskip_next = __all(lane >= 3 || zf == 1u);
+        zdst_next = __builtin_amdgcn_readlane((int)zf, 3) == 1;
       }
     }
     wt_.barrier();
@@ -271,12 +315,12 @@ __device__ __forceinline__ void tm_momentum_march(const Geom& g, const Consts<T>
 }
 
 // (three waves per SIMD: <= 168 VGPRs in every instantiation -- the forms with exec-masked global stores would take 171)
-template <typename T, int V, bool YFIRST, bool STORE_UV, bool BS, int ABL = 0>
+template <typename T, int V, bool YFIRST, bool STORE_UV, bool BS, int ABL = 0, bool ZMAP = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void k_tm(Geom g, Consts<T> c, const T* __restrict__ F, T* __restrict__ Fn, int ntf,
                                             const T* __restrict__ us, const T* __restrict__ vs, const T* __restrict__ p,
                                             T* __restrict__ Uo, T* __restrict__ Vo, T* __restrict__ us_out,
                                             T* __restrict__ vs_out, T* __restrict__ rhs,
-                                            unsigned long long* __restrict__ courant, TbPlan tp, RowSegments rows) {
+                                            unsigned long long* __restrict__ courant, TbPlan tp, RowSegments rows, ZeroMaps zm) {
   // rows: up to four row ranges, each cut in chunks of its own length and handed out in order (row_segments.h) -- the body and the
   // shorter chunks of a full domain's tail, or the two edge bands of a strip in one launch
   constexpr int W = TmGeom<V>::W;
@@ -310,12 +354,30 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3))) void k
   // counts Courant violations on is an owned row, columns c0 - 1 .. c0 + W lie in [1, ny + 1] with every lane's columns in [2, ny]
   const bool interior = ma - 8 >= g.ilo && mb + 7 <= g.ihi && ma >= g.own_lo && mb <= g.own_hi && c0 >= 2 && c0 + W - 1 <= g.ny;
   if (role == 0) {
-    if (interior) tm_transport_march<T, V, YFIRST, STORE_UV, BS, true, ABL>(g, c, ring, F, Fn, us, vs, p, Uo, Vo, courant, c0, lane, ma, mb, wt_);
-    else tm_transport_march<T, V, YFIRST, STORE_UV, BS, false, ABL>(g, c, ring, F, Fn, us, vs, p, Uo, Vo, courant, c0, lane, ma, mb, wt_);
+    if (interior) tm_transport_march<T, V, YFIRST, STORE_UV, BS, true, ABL, ZMAP>(g, c, ring, F, Fn, us, vs, p, Uo, Vo, courant, c0, lane, ma, mb, wt_, zm, tj);
+    else tm_transport_march<T, V, YFIRST, STORE_UV, BS, false, ABL, ZMAP>(g, c, ring, F, Fn, us, vs, p, Uo, Vo, courant, c0, lane, ma, mb, wt_, zm, tj);
   } else {
     if (interior) tm_momentum_march<T, V, BS, true, ABL>(g, c, ring, us_out, vs_out, rhs, c0, lane, ma, mb, wt_);
     else tm_momentum_march<T, V, BS, false, ABL>(g, c, ring, us_out, vs_out, rhs, c0, lane, ma, mb, wt_);
   }
+}
+
+// The zero map of F against F itself, on demand (counters "fzmap_flagged", "fzmap_wrong"): one thread per (row, tile) word; a flagged
+// segment is wrong if one of the cells the tile stores in that row is not +0 bit for bit.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void k_fzmap_check(Geom g, const T* __restrict__ F, int ntf, const unsigned* __restrict__ map,
+                                                     unsigned long long* __restrict__ counts) {
+  const long w = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= (long)g.nx * ntf) return;
+  const int i = 1 + (int)(w / ntf), tj = (int)(w % ntf);
+  if (map[(size_t)(i - 1) * (ntf + 2) + tj + 1] != 1u) return;
+  const int c0 = tile_c0<TmGeom<V>>(tj);
+  int j0, jlo, jhi;
+  tile_columns<TmGeom<V>, V>(c0, 0, g.ny, j0, jlo, jhi);
+  unsigned nz = 0;
+  for (int j = jlo; j <= jhi; ++j) nz |= bits_of(F[at(g, i, j)]);
+  atomicAdd(&counts[0], 1ull);
+  if (nz) atomicAdd(&counts[1], 1ull);
 }
 
 }  // namespace vof

@@ -85,6 +85,8 @@ struct WorkBufs {
   DevBuf scene;        // vof_set_scene (runtime/scene.h): the shape list as k_scene reads it (room for VOF_SCENE_MAX_SHAPES records), the slots of the two counters behind it
   DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
   DevBuf red;          // device scalar of vof_comm_allreduce_max
+  DevBuf fzmap;        // k_tm's zero maps (kernels/fused_tm.h): one word per (interior row, k_tm tile column) of the F array and, behind it, of its twin -- one allocation: one buffer descriptor in the march --, reserved zeroed
+  DevBuf fzmap_cnt;    // ... the two words of the counters "fzmap_flagged", "fzmap_wrong"
 
   DevBuf* begin() { return &courant; }
   DevBuf* end() { return begin() + sizeof(WorkBufs) / sizeof(DevBuf); }

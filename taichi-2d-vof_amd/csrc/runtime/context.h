@@ -272,6 +272,9 @@ struct vof2d_ctx {
   // shorter chunks for the rows k_tm hands out last (L::tm_chunk_rows): -1 by the rule, -2 the rule whatever the body's chunk length, 0 never, 1 as tm_tail_at / tm_tail_rows say
   int tm_taper = -1;
   int tm_tail_at[3] = {0, 0, 0}, tm_tail_rows[3] = {0, 0, 0};   // first row and chunk length of tail segment 1..3 (0: none)
+  int f_zero_map = -1;       // knob "f_zero_map": k_tm keeps a map of the all-zero row segments of F and moves no bytes for them (fzmap_allowed, runtime/launches.h)
+  bool f_view_given = false; // vof_field_view handed out a pointer to F or its twin: the caller may write through it at any time, the handle keeps no zero maps from then on
+  bool fzmap_active = false; // the k_tm batches of the handle keep and use the zero maps: what its batch graphs were captured with (fzmap_prepare, runtime/schedule.h)
   int tm_segments_last = 0;  // row segments of the last k_tm launch enqueued (counter "tm_segments")
   int halves = -1;   // -1: where it pays (halves_eligible), 0: never, 1: wherever the schedule allows
   std::vector<hipStream_t> chain_streams;   // streams of the chains below the first

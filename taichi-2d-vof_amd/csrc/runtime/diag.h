@@ -25,9 +25,10 @@ void dbg_tm(vof2d_ctx* h) {
   const TbPlan tp{nullptr, nullptr, 0, 0, 0, 0, 0};
   const unsigned pairs = (unsigned)(row_chunks(rows) * ntf);
   h->tm_segments_last = row_used_segments(rows);
+  step_wrote_F(h->state);   // (the probe writes the twin of F, with values of its own: no zero map holds over it)
   launch_block(h, kTM, k_tm<T, V, YFIRST, false, true, ABL>, dim3(pairs), 128u, 0, h->g, L<T>::C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
                (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
-               F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, fRHS), h->d_courant + 3, tp, rows);
+               F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, fRHS), h->d_courant + 3, tp, rows, ZeroMaps{nullptr, 0, 0, 0});
 }
 
 }  // namespace

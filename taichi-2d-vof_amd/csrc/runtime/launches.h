@@ -105,12 +105,34 @@ inline bool buffer_stores_ok(const vof2d_ctx* h) {
   return h->buf_stores && (h->g.ny % 2 == 0) && (size_t)h->field_elems * h->esz < ((size_t)1 << 31) - (1u << 20);
 }
 
+// k_tm's zero maps (kernels/fused_tm.h): knob "f_zero_map" 1: wherever allowed -- a full domain without a communicator whose k_tm
+// runs the buffer-store form --, 0: never, -1 (the default): where allowed AND it was measured to pay: the share of exact-zero cells
+// the batch-form rule counted is at least kTmGasShare (4096^2 rising bubble, 2 % gas: every row pays for its flags and next to none
+// is skipped, + 1.3 %) on a grid of kTmAlwaysCells or more (4096^2 dam-break - 4.3 %, 8192^2 - 8.4 %; 2048^2, whose F and twin stay
+// in the last-level cache, + 0.8 %: profiles/f_zero_map_ab.txt).  What a handle's batch graphs were captured with is h->fzmap_active
+// (fzmap_prepare, runtime/schedule.h).
+constexpr double kTmGasShare = 0.5;   // k_tm from this share of exact-zero cells of F on (tm_choice_by_rule, runtime/schedule.h)
+constexpr long kTmAlwaysCells = 16000000L;   // ... and whatever F holds from this many cells on (the measurements behind it: "launches" below)
+// (a handle that gave out a pointer to F or its twin, vof_field_view, keeps none: a write through the pointer cannot be seen)
+inline size_t fzmap_bytes(const vof2d_ctx* h) {   // of one map: (nx + 2) rows of tiles + 2 words -- the marches request the words of one row past the last they load
+  const int ntf = h->d.dtype == VOF_F64 ? TmGeom<VecWidth<double>::V>::tiles(h->g.ny) : TmGeom<VecWidth<float>::V>::tiles(h->g.ny);
+  return (size_t)(h->g.nx + 2) * (size_t)(ntf + 2) * sizeof(unsigned);
+}
+// the allocation: four rows of padding (the march's one load reaches four rows back from a destination word), the map of the F array, the map of its twin
+inline size_t fzmap_pad(const vof2d_ctx* h) { return fzmap_bytes(h) / (size_t)(h->g.nx + 2) * 4; }
+inline size_t fzmap_offset(const vof2d_ctx* h, int array) { return fzmap_pad(h) + (size_t)array * fzmap_bytes(h); }
+inline size_t fzmap_alloc_bytes(const vof2d_ctx* h) { return fzmap_offset(h, 2); }
+inline bool fzmap_allowed(const vof2d_ctx* h) {
+  if (h->f_view_given || fzmap_alloc_bytes(h) >= ((size_t)1 << 30)) return false;
+  if (h->f_zero_map == 0 || !(h->g.wall_lo && h->g.wall_hi) || h->comm || !buffer_stores_ok(h) || !(h->buf_stores & 4)) return false;
+  return h->f_zero_map > 0 || (h->gas_share >= kTmGasShare && (long)(h->g.ihi - h->g.ilo + 1) * h->g.ny >= kTmAlwaysCells);
+}
+
 // ------------------------------------------------------------------ launches
-// From this many cells on a full domain runs the pair kernels whatever it holds (the rule of vof_step, runtime/schedule.h).  Re-measured
+// kTmAlwaysCells (above, beside the zero maps' rule): from this many cells on a full domain runs the pair kernels whatever it holds (the rule of vof_step, runtime/schedule.h).  Re-measured
 // with the kernels of round 6 (profiles/r06_forms_sweep.txt, ms/step pairs / chains on the rising bubble, 2 % gas): fp64 2048^2 0.253 / 0.227,
 // 2560^2 0.325 / 0.312, 3072^2 0.405 / 0.411, 4096^2 0.592 / 0.614; fp32 2560^2 0.199 / 0.190, 3072^2 0.246 / 0.243, 4096^2 0.352 / 0.365
 // (round 5, before the branch-free division tier: ties at 4096^2, hence 20 M then); 5120^2 0.78-0.83 / 0.89-0.92, 8192^2 1.67-1.71 / 2.17-2.20
-constexpr long kTmAlwaysCells = 16000000L;
 constexpr long kTbPlanWaves = 16384;   // waves of a k_jacobi_tb launch the work plan can describe
 // which kernel a work plan is for: the step's Jacobi launches are k_jacobi_tb's, or (the k_tm forms where the handle allows:
 // jacobi_pair_ok) k_jacobi_pair's -- the tile columns, chunk lengths and wave counts differ (L<T>::tb_plan)
@@ -413,10 +435,27 @@ struct L {
   // rows [first, last] and, in the same launch, [first2, last2] (a strip's two edge bands: two segments of rows_forced-row chunks);
   // store_uv: the last k_tm of a batch; rhs_id: the array the next step's rhs goes to (fRHS, or fKAPPA where the caller alternates
   // the two: enqueue_steps_tm)
-  static void tm(vof2d_ctx* h, bool y_first, bool store_uv, int adapt_par, PlanFor plan_for, int rhs_id, int first = 1, int last = 0, int rows_forced = 0, int first2 = 1, int last2 = 0) {
+  // zero_maps: the launch keeps and uses the zero maps of F and its twin where the handle runs with them (h->fzmap_active; the caller
+  // has cleared them if they were stale: fzmap_clear_if_stale, runtime/schedule.h) -- the ZMAP instantiation; every other launch is today's kernel
+  static void tm(vof2d_ctx* h, bool y_first, bool store_uv, int adapt_par, PlanFor plan_for, int rhs_id, int first = 1, int last = 0, int rows_forced = 0, int first2 = 1, int last2 = 0,
+                 bool zero_maps = false) {
     if (last < first) { first = h->g.ilo; last = h->g.ihi; }
     const int ntf = TmGeom<V>::tiles(h->g.ny);
     const TbPlan tp = tb_plan(h, adapt_par, plan_for);
+    if (zero_maps && h->fzmap_active) {
+      // each map belongs to its array, not to the view: the bit that picks the F pointers picks the maps
+      const int cur = (h->views.bits() & FieldViews::kF) ? 1 : 0;
+      const ZeroMaps zm{h->buf.fzmap.as<unsigned>(), (int)fzmap_offset(h, cur), (int)fzmap_offset(h, cur ^ 1), ntf + 2};
+      dispatch([&](auto YF, auto UV) {
+        const RowSegments rows = tm_chunk_rows(h, first, last, ntf, resident(h, k_tm<T, V, YF(), UV(), true, 0, true>, 128));
+        const unsigned pairs = (unsigned)(row_chunks(rows) * ntf) + (tp.masks ? 1u : 0u);
+        h->tm_segments_last = row_used_segments(rows);
+        launch_block(h, UV() ? kTMUV : kTM, k_tm<T, V, YF(), UV(), true, 0, true>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
+                     (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
+                     F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, rhs_id), h->d_courant, tp, rows, zm);
+      }, y_first, store_uv);
+      return;
+    }
     // pair chunks: a whole number of residency rounds, just filled (6 pairs per CU: 24 KB of LDS each) -- a launch that needs a
     // little more than k rounds pays for k + 1 --, as many rounds as keep the chunks near 50 rows (one round of 100-row
     // chunks: every step of every pair takes 3.3 us instead of 1.9).  4096^2, 112-column tiles, us per launch: 40 rows
@@ -429,8 +468,15 @@ struct L {
       h->tm_segments_last = row_used_segments(rows);
       launch_block(h, UV() ? kTMUV : kTM, k_tm<T, V, YF(), UV(), BS()>, dim3(pairs), 128u, 0, h->g, C(h), (const T*)F_<T>(h, fF), F_<T>(h, fF2), ntf,
                    (const T*)F_<T>(h, fUS), (const T*)F_<T>(h, fVS), (const T*)F_<T>(h, fP), F_<T>(h, fU), F_<T>(h, fV),
-                   F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, rhs_id), h->d_courant, tp, rows);
+                   F_<T>(h, fMX), F_<T>(h, fMY), F_<T>(h, rhs_id), h->d_courant, tp, rows, ZeroMaps{nullptr, 0, 0, 0});
     }, y_first, store_uv, buffer_stores_ok(h) && (h->buf_stores & 4));
+  }
+  // the counters of the zero map of array `cur` (0: the F array of creation, 1: its twin) into buf.fzmap_cnt: one thread per word
+  static void fzmap_check(vof2d_ctx* h, int cur) {
+    const int ntf = TmGeom<V>::tiles(h->g.ny);
+    const long words = (long)h->g.nx * ntf;
+    launch(h, kOther, k_fzmap_check<T, V>, dim3((unsigned)((words + 255) / 256)), 0, h->g, (const T*)h->views.table()[fF], ntf,
+           h->buf.fzmap.as<const unsigned>(fzmap_offset(h, cur)), h->buf.fzmap_cnt.as<unsigned long long>());
   }
   // ---- conjugate gradients (kernels/cg.h)
   // sum of ap over the interior, in double, of the values the kernels form in T: ap depends on the position through

@@ -192,7 +192,7 @@ inline bool tm_eligible(const vof2d_ctx* h) {
 // 4096^2 dam-break 0.601 / 0.576 / 0.547, 8192^2 2.27 / 2.31 / 1.93, but 4096^2 rising bubble 0.682 / 0.612 / 0.808 -- mostly
 // liquid --, 4096^2 fp32 0.364 / 0.337 / 0.361, 3072^2 0.351 / 0.346 / 0.346, 2048^2 0.168 / - / 0.188) -- the form is chosen by
 // a rule on the state (fuse_tm = -1, the default: decide_batch_form_by_rule) or, for exploration, by timing both (fuse_tm = -2).
-constexpr double kTmGasShare = 0.5;   // k_tm from this share of exact-zero cells of F on
+// k_tm from the share kTmGasShare (runtime/launches.h) of exact-zero cells of F on
 // ... and on grids of kTmAlwaysCells and more whatever they hold (runtime/launches.h); both precisions
 // ... and in fp32 where the grid is too small for the chains (below 6 M cells the alternative is the plain one-chain sequence, and an
 // fp32 pair needs half the LDS of an fp64 one: all pairs of a 2048^2 launch are resident at once) -- rising bubble fp32 2048^2
@@ -321,6 +321,30 @@ void batch_jacobi(vof2d_ctx* h, int par, int tb_par) {
     h->views.swap_P();
   }
 }
+// k_tm's zero maps in front of a batch, in two parts, both outside any capture (the captured batches never need a memset).
+// fzmap_prepare, in front of the captures: whether the handle runs with maps at all (fzmap_allowed, runtime/launches.h), decided
+// batch by batch, and the first time the allocation of both, reserved zeroed.  A handle that cannot have them (no memory) runs
+// without: never an error of vof_step.  fzmap_clear_if_stale, where a batch is about to be launched and nowhere else: both maps
+// cleared if something else has written F or its twin since the last batch (fzmap_take_stale, runtime/state.h); a clear that
+// fails is the call's error, and the batch is not launched.
+void fzmap_prepare(vof2d_ctx* h) {
+  bool want = fzmap_allowed(h);
+  if (want && h->buf.fzmap.reserve(h, fzmap_alloc_bytes(h), "no memory for the zero maps", true) != VOF_OK) want = false;
+  // the batch graphs bake in which instantiation of k_tm they launch: a handle that changes sides (the rule saw another F, the
+  // knob was one that does not drop the graphs) captures them again
+  if (want != h->fzmap_active) {
+    h->graphs.clear_kind(gBatch);
+    h->fzmap_active = want;
+    step_wrote_F(h->state);
+  }
+}
+int fzmap_clear_if_stale(vof2d_ctx* h) {
+  if (!h->fzmap_active) { step_wrote_F(h->state); return VOF_OK; }   // (k_tm without maps writes F like any other step)
+  if (!h->state.fzmap_stale) return VOF_OK;
+  HIPCHK(h, hipMemsetAsync(h->buf.fzmap.p, 0, fzmap_alloc_bytes(h), h->stream));   // (a batch must not run on maps that could not be cleared: the bit stays set)
+  (void)fzmap_take_stale(h->state);
+  return VOF_OK;
+}
 template <typename T>
 void enqueue_steps_tm(vof2d_ctx* h, int64_t first_step, int K) {
   const PlanFor plan_for = L<T>::plan_for_tm(h);
@@ -328,7 +352,7 @@ void enqueue_steps_tm(vof2d_ctx* h, int64_t first_step, int K) {
     const int64_t istep = first_step + k;
     const int par = (int)(istep & 1);
     batch_jacobi<T>(h, par, par);
-    L<T>::tm(h, istep % 2 == 0, /*store_uv=*/k == K - 1, par ^ 1, plan_for, /*rhs_id=*/fKAPPA);   // (swap_SR alternates rhs with the kappa array)
+    L<T>::tm(h, istep % 2 == 0, /*store_uv=*/k == K - 1, par ^ 1, plan_for, /*rhs_id=*/fKAPPA, 1, 0, 0, 1, 0, /*zero_maps=*/true);   // (swap_SR alternates rhs with the kappa array)
     h->views.swap_SR();
     h->views.swap_F();
   }

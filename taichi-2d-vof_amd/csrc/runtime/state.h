@@ -17,6 +17,8 @@ struct FieldState {
   bool alt_dirty = false;        // a verb or a field write left something in mx / my (the second u*, v* pair of the k_tm forms): cleared at the head of a strip call (tm5_head)
   bool ahead = false;            // u*, v*, rhs hold the predictor of step istep + 1 (the chained k_tm batches; settle_ahead)
   int next_phase = 0;            // the phase vof_step_phase takes next; not 0: a phased step is in progress
+  bool fzmap_stale = true;       // F or its twin was written by something that keeps no zero map (anything but a k_tm launch of a batch that
+                                 // does): a flag may stand over cells that are no longer zeros -- both maps are cleared before the next such batch
 };
 
 // ---- fields written other than by a step.  Field `id` was written from outside: by the host (vof_set_rows, vof_set_init_F)
@@ -24,6 +26,7 @@ struct FieldState {
 // is the halo exchange and says nothing; on a full domain the rows' neighbours' ghost cells may no longer mirror them -- and
 // the twin of F is never named alone).  True if F changed: the caller forgets the batch form the rule chose (forget_batch_form).
 inline bool field_written(FieldState& s, int id, bool full_domain, bool rows_only_inside) {
+  if (id == fF || id == fF2) s.fzmap_stale = true;   // (either array, named alone or not: a map belongs to its array)
   if (rows_only_inside && !full_domain) return false;
   const bool f = id == fF || (id == fF2 && !rows_only_inside);
   if (f) s.f_ghosts_dirty = true;
@@ -33,7 +36,7 @@ inline bool field_written(FieldState& s, int id, bool full_domain, bool rows_onl
 }
 // ... and by a verb, per class of verb
 inline void bc_applied(FieldState& s) { s.f_ghosts_dirty = s.uv_ghosts_dirty = s.ghosts_virtual = false; }   // vof_set_BC: the launch a fused step left out
-inline void verb_wrote_F(FieldState& s) { s.f_ghosts_dirty = true; }     // the FCT sweeps, vof_post_process_f (F is advanced, not replaced: the batch form stays)
+inline void verb_wrote_F(FieldState& s) { s.f_ghosts_dirty = s.fzmap_stale = true; }     // the FCT sweeps, vof_post_process_f (F is advanced, not replaced: the batch form stays)
 inline void verb_wrote_uv(FieldState& s) { s.uv_ghosts_dirty = true; }   // vof_update_uv
 inline void verb_wrote_alt(FieldState& s) { s.alt_dirty = true; }        // vof_get_normal_young, vof_advect_upwind: mx, my
 
@@ -57,6 +60,17 @@ inline StepPlan plan_step(const FieldState& s, StepCaps c) {
 inline void finish_step(FieldState& s, StepPlan p) {
   s.f_ghosts_dirty = s.uv_ghosts_dirty = false;
   s.ghosts_virtual = p.virt;
+}
+
+// ---- k_tm's zero maps (kernels/fused_tm.h).  The invariant: a flag is 1 only if the last write to that segment of that array was a
+// k_tm store (or skipped store) of zeros.  Every other writer of F or its twin -- a field write, a verb (above), a step in any form
+// but the k_tm batches that keep the maps -- leaves the bit set; the one place that enqueues such a batch asks fzmap_take_stale first
+// and clears both maps where it says so.
+inline void step_wrote_F(FieldState& s) { s.fzmap_stale = true; }   // k_transport, the sweeps of a phased or eager step, k_tm without maps
+inline bool fzmap_take_stale(FieldState& s) {
+  const bool stale = s.fzmap_stale;
+  s.fzmap_stale = false;
+  return stale;
 }
 
 // ---- the phases of a step (vof_step_phase): 0, 1, 2 in this order; every other kind of step waits for phase 2

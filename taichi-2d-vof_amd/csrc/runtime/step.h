@@ -143,6 +143,7 @@ int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
   const int par = (int)(h->istep & 1);
   bool timed = false;
   int variant = batch_form(h, true, remaining, &timed);
+  if (variant) fzmap_prepare(h);   // (in front of the captures too: a graph bakes in whether the handle has its zero maps)
   auto batch = [&](int form, int b) { return h->graphs.find(graph_key(h, gBatch, batch_variant(form, b, h->istep))); };
   if (h->batching && !batch(variant, 0)) {
     build_step_batches(h, variant);
@@ -168,7 +169,9 @@ int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
       if (h->state.ahead) h->tm_chained += 1;
       else DISPATCH_T(h, enqueue_tm_head<double>(h, par), enqueue_tm_head<float>(h, par));
       h->state.ahead = true;
-    } else h->state.ahead = false;
+    } else { h->state.ahead = false; step_wrote_F(h->state); }
+    if (variant)
+      if (const int rc = fzmap_clear_if_stale(h)) return rc;
     if (hipGraphLaunch(exec, h->stream) != hipSuccess) return fail(h, VOF_EHIP, "hipGraphLaunch of a step batch");
     if (time_it) {
       if (hipEventRecord(t.ev[2 * t.n + 1], h->stream) == hipSuccess) t.n += 1;
@@ -186,6 +189,7 @@ int run_step_batch(vof2d_ctx* h, int64_t remaining, int* ran) {
 // views: graph_key).  The two-kernel transport swaps the pair twice per step, the fused one once.
 int run_step_graph(vof2d_ctx* h, bool virt) {
   h->state.ahead = false;   // (this step forms its own predictor, into the host's view of u*, v*, rhs)
+  step_wrote_F(h->state);
   hipGraphExec_t& exec = h->graphs.slot(graph_key(h, gStep, (int)(h->istep & 1)));
   int rc;
   if (!exec && (rc = capture_or_fail(h, /*upload=*/true, &exec, "the step graph", [&] {
@@ -202,6 +206,7 @@ int run_step_graph(vof2d_ctx* h, bool virt) {
 // created with VOF_FLAG_NO_GRAPH.  mg: the steps of vof_step_mg.
 int run_step_eager(vof2d_ctx* h, bool lean, bool virt, const StepMg* mg) {
   h->state.ahead = false;   // (see run_step_graph)
+  step_wrote_F(h->state);
   DISPATCH_T(h, enqueue_step<double>(h, h->istep, lean, virt, mg), enqueue_step<float>(h, h->istep, lean, virt, mg));
   return ensure_ok(h);
 }
@@ -239,6 +244,7 @@ int step_n(vof2d_ctx* h, int64_t nsteps) {
 // the key (at most GraphStore::kCap of them stay), and the graphs go with every other when a knob changes (destroy_graphs).
 int run_step_mg_graph(vof2d_ctx* h, bool virt, const StepMg& mg) {
   h->state.ahead = false;   // (see run_step_graph; settled in front of the loop: step_mg_n)
+  step_wrote_F(h->state);
   hipGraphExec_t& exec = h->graphs.slot(graph_key(h, gStepMg, (mg.cycles * 2 + mg.criterion) * 2 + (int)(h->istep & 1)));
   int rc;
   if (!exec && (rc = capture_or_fail(h, /*upload=*/true, &exec, "the multigrid step graph", [&] {
@@ -291,6 +297,7 @@ int step_groups_n(vof2d_ctx* h, int64_t nsteps, int64_t every, int cycles, int c
 
 // One phase of a step (vof_step_phase: the caller has checked the order of the phases)
 int step_phase(vof2d_ctx* h, int phase) {
+  if (phase != 0) step_wrote_F(h->state);
   if (h->d.flags & VOF_FLAG_NO_GRAPH) {
     DISPATCH_T(h, enqueue_phase<double>(h, phase, h->istep), enqueue_phase<float>(h, phase, h->istep));
     return ensure_ok(h);
@@ -327,6 +334,8 @@ int profile_steps(vof2d_ctx* h, int64_t nsteps) {
       for (int b = vof2d_ctx::kStepBatches - 1; b >= 0; --b)
         if (nsteps - done >= batch_steps(h, 1, b) && 1 + batch_steps(h, 1, b) * per_tm_step <= vof2d_ctx::kMaxTimed && batch_steps(h, 1, b) > K) K = batch_steps(h, 1, b);
       if (1 + K * per_tm_step > vof2d_ctx::kMaxTimed) { h->timed = -1; return fail(h, VOF_ESTATE, "a k_tm batch of two steps has more launches than the profiling event pool"); }
+      fzmap_prepare(h);
+      if (const int rc = fzmap_clear_if_stale(h)) { h->timed = -1; return rc; }
       if (!h->state.ahead) DISPATCH_T(h, enqueue_tm_head<double>(h, (int)((h->istep + 1) & 1)), enqueue_tm_head<float>(h, (int)((h->istep + 1) & 1)));
       h->state.ahead = true;
       DISPATCH_T(h, enqueue_steps_tm<double>(h, h->istep + 1, K), enqueue_steps_tm<float>(h, h->istep + 1, K));
@@ -339,6 +348,7 @@ int profile_steps(vof2d_ctx* h, int64_t nsteps) {
       h->state.ahead = false;   // (cleared in front of settle_ghosts, unlike step_loop: no copy of a predictor formed ahead, no ensure_ok per step)
       const StepPlan p = plan_step(h->state, step_caps(h, false));
       if (!p.virt) settle_ghosts(h);
+      step_wrote_F(h->state);
       DISPATCH_T(h, enqueue_step<double>(h, h->istep, p.lean, p.virt), enqueue_step<float>(h, h->istep, p.lean, p.virt));
       finish_step(h->state, p);
       ++batch;

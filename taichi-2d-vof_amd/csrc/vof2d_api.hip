@@ -69,7 +69,7 @@ const Knob kKnobs[] = {
   KNOB("fctx_corr_rows", fctx_corr_rows, false), KNOB("band_rows", band_rows, false), KNOB("rows_per_wave", rows_override, false),
   KNOB("fuse_transport", fuse_transport, false), KNOB("virtual_ghosts", virtual_ghosts, false), KNOB("buffer_stores", buf_stores, false),
   KNOB("overlap_halves", halves, false), KNOB("batch_steps", step_batch[0], false), KNOB("fuse_tm", fuse_tm, false),
-  KNOB("tm_rows", tm_rows, false), KNOB("tm_taper", tm_taper, true),
+  KNOB("tm_rows", tm_rows, false), KNOB("tm_taper", tm_taper, true), KNOB("f_zero_map", f_zero_map, true),
   KNOB("tm_tail_at1", tm_tail_at[0], false), KNOB("tm_tail_at2", tm_tail_at[1], false), KNOB("tm_tail_at3", tm_tail_at[2], false),
   KNOB("tm_tail_rows1", tm_tail_rows[0], false), KNOB("tm_tail_rows2", tm_tail_rows[1], false), KNOB("tm_tail_rows3", tm_tail_rows[2], false),
   KNOB("jacobi_pair", jpair, false), KNOB("jacobi_pair_rows", jpair_rows, false),
@@ -720,6 +720,9 @@ int vof_field_view(vof2d_handle h, const char* name, void** base, int64_t* pitch
   settle_ghosts(h);
   int id = field_id(name);
   if (id < 0) return fail(h, VOF_EINVAL, "unknown field name");
+  // the caller may write through the pointer at any time, unseen: a handle that gave out F or its twin keeps no zero maps from here on
+  // (fzmap_allowed; the next batch captures its graphs without them)
+  if (id == fF || id == fF2) { h->f_view_given = true; step_wrote_F(h->state); }
   if (base) *base = h->fld[id];
   if (pitch) *pitch = h->g.pitch;
   if (col0) *col0 = h->g.col0;
@@ -823,6 +826,7 @@ int vof_set_param(vof2d_handle h, const char* name, double value) {
     if (knob == &h->step_batch[0]) *knob = *knob < 4 ? 4 : (*knob & ~1);   // an even number of steps (see step.h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     destroy_graphs(h);
+    step_wrote_F(h->state);   // (a knob may switch k_tm's zero maps off and on again: what they say is given up)
     return VOF_OK;
   }
   return fail(h, VOF_EINVAL, "unknown or read-only parameter");
@@ -879,6 +883,22 @@ int vof_get_counter(vof2d_handle h, const char* name, int64_t* value) {
   if (!strcmp(name, "tm_segments")) {   // row segments of the last k_tm launch enqueued (1: no tail; kernels/row_segments.h)
     *value = h->tm_segments_last;
     return VOF_OK;
+  }
+  if (!strcmp(name, "fzmap_flagged") || !strcmp(name, "fzmap_wrong")) {
+    // k_tm's zero map of the current F, counted on demand (k_fzmap_check, kernels/fused_tm.h): the segments flagged, and those of
+    // them whose cells are not all +0 bit for bit -- 0 unless the bookkeeping of runtime/state.h has a hole.  0 / 0 without maps.
+    *value = 0;
+    if (!h->fzmap_active) return VOF_OK;
+    settle_ghosts(h);
+    if (h->state.fzmap_stale) return VOF_OK;   // (the maps are cleared before they are looked at again: nothing is flagged)
+    if (const int rc = h->buf.fzmap_cnt.reserve(h, 2 * sizeof(unsigned long long), "no memory for the zero-map counters")) return rc;
+    unsigned long long v[2] = {0, 0};
+    HIPCHK(h, hipMemsetAsync(h->buf.fzmap_cnt.p, 0, sizeof(v), h->stream));
+    const int cur = (h->views.bits() & FieldViews::kF) ? 1 : 0;
+    DISPATCH_T(h, L<double>::fzmap_check(h, cur), L<float>::fzmap_check(h, cur));
+    if (const int rc = read_back(h, v, h->buf.fzmap_cnt.p, sizeof(v))) return rc;
+    *value = (int64_t)v[!strcmp(name, "fzmap_wrong") ? 1 : 0];
+    return ensure_ok(h);
   }
   if (!strcmp(name, "tm_chained_batches")) {   // k_tm batches that found the predictor of their first step in place
     *value = h->tm_chained;
@@ -1039,6 +1059,7 @@ int vof_step_tm_piece(vof2d_handle h, int32_t piece) {
   if (!mode5_ok(h)) return fail(h, VOF_ESTATE, "the pair kernels need the fused transport and five-sweep Jacobi launches");
   if (!clean_ghosts(h->state)) return fail(h, VOF_ESTATE, "the first step after set_init_F / set_field runs through vof_step");
   (void)settle_ahead(h);   // (a full domain that ran chained k_tm batches: its u*, v*, rhs are the last step's from here on)
+  if (piece != 0) step_wrote_F(h->state);
   if (piece == 0) {
     DISPATCH_T(h, tm5_head<double>(h), tm5_head<float>(h));
   } else if (piece == 1) {
@@ -1061,6 +1082,7 @@ int vof_step_exchange(vof2d_handle h, int64_t nsteps, int32_t overlap) {
   if (!h || nsteps < 0 || overlap < 0 || overlap > 5 || overlap == 2) return VOF_EINVAL;   // (2 was retired: never worth it)
   if (!h->comm) return fail(h, VOF_ESTATE, "vof_comm_init has not been called");
   if (const int rc = check_no_phased_step(h)) return rc;
+  step_wrote_F(h->state);
   HIPCHK(h, hipSetDevice(h->device));
   (void)settle_ahead(h);   // (see vof_step_tm_piece)
   return overlap == 5 ? step_exchange_mode5(h, nsteps) : step_exchange(h, nsteps, overlap);

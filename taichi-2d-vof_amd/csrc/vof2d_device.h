@@ -76,6 +76,17 @@ struct Geom {
   int ntj;               // column tiles of 64*V columns covering j = 1 .. ny
 };
 
+// k_tm's zero maps (kernels/fused_tm.h): one 32-bit word per (interior row i, k_tm tile column tj) of F (src, read)
+// and of its twin (dst, written), at [(i - 1) * stride + tj + 1], stride = tiles + 2 (the words of tiles -1 and `tiles` stay 0).
+// 1: the columns tile tj stores in row i of that array hold the bit pattern of +0.0 in every cell; 0: unknown.  Both maps lie in one
+// allocation, at byte offsets src and dst >= 4 * stride * 4 behind base (one buffer descriptor and one load per row in the march, whose
+// lanes reach four rows back from a word).  Null base: no maps.
+struct ZeroMaps {
+  unsigned* base;
+  int src, dst;
+  int stride;
+};
+
 // Constants rounded once from Python-double folded values.
 template <typename T>
 struct Consts {

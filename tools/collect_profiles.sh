@@ -27,12 +27,13 @@ timeout 900 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_I
 unset VOF2D_OVERLAP_HALVES
 timeout 900 rocprofv3 --kernel-trace --output-format csv -d $OUT/${T}_long2 -- python3 tools/bound_run.py --steps 1000 > $OUT/${T}_long2.log 2>&1
 export VOF2D_OVERLAP_HALVES=0 VOF2D_FUSE_TM=1
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${T}_long3 -- python3 tools/bound_run.py --steps 1000 > $OUT/${T}_long3.log 2>&1
-timeout 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/${T}_tmfetch -- python3 tools/bound_run.py --steps 60 > $OUT/${T}_tmfetch.log 2>&1
-timeout 900 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/${T}_tmwrite -- python3 tools/bound_run.py --steps 60 > $OUT/${T}_tmwrite.log 2>&1
+# (a handle whose form is forced never counts its gas and keeps no zero maps by default: f_zero_map=1 makes these passes the ZMAP kernels bench.py runs on the dam-break)
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${T}_long3 -- python3 tools/bound_run.py --steps 1000 --param f_zero_map=1 > $OUT/${T}_long3.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/${T}_tmfetch -- python3 tools/bound_run.py --steps 60 --param f_zero_map=1 > $OUT/${T}_tmfetch.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/${T}_tmwrite -- python3 tools/bound_run.py --steps 60 --param f_zero_map=1 > $OUT/${T}_tmwrite.log 2>&1
 unset VOF2D_OVERLAP_HALVES VOF2D_FUSE_TM
 python3 tools/summarize_overlap_trace.py $T one-chain=$OUT/${T}_long chains=$OUT/${T}_long2 k_tm=$OUT/${T}_long3 --cmd "rocprofv3 --kernel-trace -- python3 tools/bound_run.py --steps 1000 (VOF2D_OVERLAP_HALVES=0 VOF2D_FUSE_TM=0 for the one-chain run, VOF2D_FUSE_TM=0 for chains, VOF2D_OVERLAP_HALVES=0 VOF2D_FUSE_TM=1 for k_tm)"
-python3 tools/summarize_profiles.py ${T}_tm "$(find $OUT/${T}_long3 -name '*kernel_stats.csv' | head -1)" "$(find $OUT/${T}_tmfetch -name '*counter_collection.csv' | head -1)" "$(find $OUT/${T}_tmwrite -name '*counter_collection.csv' | head -1)" --tm-json --cmd "VOF2D_OVERLAP_HALVES=0 VOF2D_FUSE_TM=1 rocprofv3 --kernel-trace --stats --output-format csv -- python3 tools/bound_run.py --steps 1000"
+python3 tools/summarize_profiles.py ${T}_tm "$(find $OUT/${T}_long3 -name '*kernel_stats.csv' | head -1)" "$(find $OUT/${T}_tmfetch -name '*counter_collection.csv' | head -1)" "$(find $OUT/${T}_tmwrite -name '*counter_collection.csv' | head -1)" --tm-json --cmd "VOF2D_OVERLAP_HALVES=0 VOF2D_FUSE_TM=1 rocprofv3 --kernel-trace --stats --output-format csv -- python3 tools/bound_run.py --steps 1000 --param f_zero_map=1"
 # summaries, here: profiles/<tag>_*.md and profiles/jacobi_pmc.json (with the hash of the sources just profiled)
 f() { find $OUT/${T}_$1 -name "*$2" | head -1; }
 python3 tools/summarize_profiles.py $T "$(f stats kernel_stats.csv)" "$(f fetch counter_collection.csv)" "$(f write counter_collection.csv)" --cmd "VOF2D_OVERLAP_HALVES=0 rocprofv3 --kernel-trace --stats --output-format csv -- $B"
