@@ -791,6 +791,51 @@ int vof_field_view(vof2d_handle h, const char* name, void** base, int64_t* pitch
  * on src so far, and everything enqueued on src or dst afterwards follows the copy. */
 int vof_copy_rows(vof2d_handle dst, vof2d_handle src, const char* name, int32_t g0, int32_t g1);
 
+/* ---- a state carried onto a finer or coarser grid (extension; kernels/regrid.h) ----
+ * vof_regrid reads F, u, v, p of src and writes them into dst, a handle of another nx x ny (and, if it likes, another dtype, dt,
+ * jacobi_iters and material constants) over the same Lx x Ly: a flow spun up on a cheap grid goes on on a fine one, a fine run is
+ * coarsened to compare resolutions.  Both are whole-domain handles on one device; each keeps its dtype: every operand is converted
+ * to double on load, all arithmetic is in double, a result is rounded once, on store.
+ *   direction   refinement: dst.nx = rx src.nx and dst.ny = ry src.ny; coarsening: src.nx = rx dst.nx and src.ny = ry dst.ny; rx, ry
+ *               integers in [1, VOF_REGRID_MAX_FACTOR]; rx = ry = 1 is a copy (a conversion between the dtypes)
+ *   refining    source cell (I, J), child (k, m), is the cell i = (I-1) rx + 1 + k, j = (J-1) ry + 1 + m of dst.  u: linear along i
+ *               between the faces I and I + 1 of row J, the same for every m (v likewise along j): every child has its parent's
+ *               discrete divergence.  p: bilinear between the source cell centres, ghost cells included.  F: the parent's value --
+ *               or, with VOF_REGRID_PLIC, in every cell vof_interface gives a segment for at this eps, the share of the child's
+ *               rectangle under the cell's PLIC line, which keeps the interface one cell of dst wide and the parent's volume to
+ *               a few ulp
+ *   coarsening  F, p: the mean of the rx ry children; u: the mean of the ry fine faces on the coarse face, v of the rx: the coarse
+ *               divergence is the mean of the fine ones
+ *               (the expressions and their order: kernels/regrid.h; tests/_regrid_np.py restates them)
+ *   src         is read as vof_get_field would return it now (pending ghost cells and a chained batch are settled first) and is
+ *               otherwise unchanged: its next steps give the bits they would have given
+ *   dst         the interior of F, its twin, u, v, p; then the launch of vof_set_BC; istep = src's.  From there dst is, in every
+ *               readable field after any number of steps, what vof_set_field of the four arrays, vof_set_BC and vof_set_istep
+ *               would have made it.  Row 0 of u and column 0 of v, which nothing reads, are stored as 0.  The Courant counter,
+ *               tracers, gauges, the dye, the statistics planes and the colour table of dst are left alone
+ *   order       asynchronous: the kernels run on dst's stream behind everything enqueued on src so far, and whatever src enqueues
+ *               next follows them.  The call waits for the device only if summary != NULL
+ *   summary     VOF_REGRID_SUM_N doubles (may be NULL): RX, RY, DIR (+1 refined, -1 coarsened, 0 the same grid), PLIC_CELLS = the
+ *               source cells whose children came from a line, DEGENERATE = the mixed source cells without an orientation (both 0
+ *               without the flag and when coarsening), F_SRC and F_DST = the sums of (double)F over the interior of src and of
+ *               dst as stored, each in the fixed order of kernels/reduce.h on its own grid, ISTEP
+ * VOF_EINVAL, with both handles untouched: a null handle; dst == src; different devices; Lx or Ly that differ as doubles; grids
+ * refined along one axis and coarsened along the other; a ratio that is no integer or larger than VOF_REGRID_MAX_FACTOR; a flag
+ * bit outside VOF_REGRID_PLIC; with VOF_REGRID_PLIC an eps outside [0, 0.5).  VOF_ESTATE: a strip on either side; a phased step
+ * (vof_step_phase) in progress on either side. */
+#define VOF_REGRID_PLIC 1
+#define VOF_REGRID_MAX_FACTOR 16
+#define VOF_REGRID_SUM_RX 0
+#define VOF_REGRID_SUM_RY 1
+#define VOF_REGRID_SUM_DIR 2
+#define VOF_REGRID_SUM_PLIC_CELLS 3
+#define VOF_REGRID_SUM_DEGENERATE 4
+#define VOF_REGRID_SUM_F_SRC 5
+#define VOF_REGRID_SUM_F_DST 6
+#define VOF_REGRID_SUM_ISTEP 7
+#define VOF_REGRID_SUM_N 8
+int vof_regrid(vof2d_handle dst, vof2d_handle src, int32_t flags, double eps, double* summary /* VOF_REGRID_SUM_N, may be NULL */);
+
 /* ---- display fields (2dvof.py:458-492; full-domain handles only) ----
  * which: "vof" get_vof_field :458-462, "u" get_u_field :465-470, "v" get_v_field :473-478,
  * "vnorm" get_vnorm_field :481-486.  dst: the rgb_buf image, dense (2*nx, 2*ny) of the field dtype. */

@@ -54,10 +54,14 @@ constexpr int kIfacePart = 2;   // doubles per block in the partials buffer: the
 
 struct IfaceConsts { double eps, one_m_eps, cx, cy, dx, dy; };
 
-// the cell (i, j) from its 3 x 3 neighbourhood fm = row i - 1, f0 = row i, fp = row i + 1, each [j - 1, j, j + 1].
-// Returns 0: not mixed, 1: degenerate, 2: a segment (s[IF_*] filled).
-__device__ __forceinline__ int iface_cell(const IfaceConsts& c, const double (&fm)[3], const double (&f0)[3], const double (&fp)[3], int i, int j,
-                                          double (&s)[IF_N]) {
+// The line of a mixed cell in the frame of a, b >= 0: the liquid is a xi + b eta < alpha; flip_x, flip_y: the mirrors that take the
+// frame back to the cell's (mxsum < 0, mysum < 0).  What k_iface cuts into a segment and k_regrid_refine (kernels/regrid.h) into
+// the F of a cell's children.
+struct IfaceLine { double mxsum, mysum, a, b, alpha; bool flip_x, flip_y; };
+
+// the line of the cell from its 3 x 3 neighbourhood fm = row i - 1, f0 = row i, fp = row i + 1, each [j - 1, j, j + 1].
+// Returns 0: not mixed, 1: degenerate, 2: a line (l filled).
+__device__ __forceinline__ int iface_line(const IfaceConsts& c, const double (&fm)[3], const double (&f0)[3], const double (&fp)[3], IfaceLine& l) {
   const double F = f0[1];
   if (!(c.eps < F && F < c.one_m_eps)) return 0;
   const double mx1 = c.cx * (((fp[2] + fp[1]) - f0[2]) - f0[1]), my1 = c.cy * (((fp[2] - fp[1]) + f0[2]) - f0[1]);
@@ -73,10 +77,22 @@ __device__ __forceinline__ int iface_cell(const IfaceConsts& c, const double (&f
   const double Fm = F <= 0.5 ? F : 1.0 - F;
   double alpha = (2.0 * n2) * Fm < n1 ? __builtin_sqrt(((2.0 * n1) * n2) * Fm) : n2 * Fm + n1 * 0.5;
   if (F > 0.5) alpha = 1.0 - alpha;
+  l.mxsum = mxsum; l.mysum = mysum; l.a = a; l.b = b; l.alpha = alpha;
+  l.flip_x = mxsum < 0.0; l.flip_y = mysum < 0.0;
+  return 2;
+}
+
+// the cell (i, j) from the same neighbourhood.  Returns 0: not mixed, 1: degenerate, 2: a segment (s[IF_*] filled).
+__device__ __forceinline__ int iface_cell(const IfaceConsts& c, const double (&fm)[3], const double (&f0)[3], const double (&fp)[3], int i, int j,
+                                          double (&s)[IF_N]) {
+  IfaceLine l;
+  const int kind = iface_line(c, fm, f0, fp, l);
+  if (kind != 2) return kind;
+  const double mxsum = l.mxsum, mysum = l.mysum, a = l.a, b = l.b, alpha = l.alpha;
   const bool p_left = b > 0.0 && alpha <= b, q_bottom = a > 0.0 && alpha <= a;
   double pxi = p_left ? 0.0 : (alpha - b) / a, peta = p_left ? alpha / b : 1.0;
   double qxi = q_bottom ? alpha / a : 1.0, qeta = q_bottom ? 0.0 : (alpha - a) / b;
-  const bool flip_x = mxsum < 0.0, flip_y = mysum < 0.0;
+  const bool flip_x = l.flip_x, flip_y = l.flip_y;
   if (flip_x) { pxi = 1.0 - pxi; qxi = 1.0 - qxi; }
   if (flip_y) { peta = 1.0 - peta; qeta = 1.0 - qeta; }
   const double di = (double)(i - 1), dj = (double)(j - 1);

@@ -83,6 +83,7 @@ struct WorkBufs {
   DevBuf frame_recs;   // ... the pictures vof_step_frames records, their summaries behind them, grown on demand
   DevBuf stats;        // vof_stats_* (runtime/stats.h, StatsCarve): the accumulator planes -- state, not scratch: cleared by vof_stats_begin alone --, the partials and results of the summary
   DevBuf scene;        // vof_set_scene (runtime/scene.h): the shape list as k_scene reads it (room for VOF_SCENE_MAX_SHAPES records), the slots of the two counters behind it
+  DevBuf regrid;       // vof_regrid into this handle (runtime/regrid.h, RegridCarve): the counts of the refining pass, the partials of the two sums of F, the four results
   DevBuf vis;          // scratch for the display fields (vof_get_vis_field / vof_interp_velocity), grown on demand
   DevBuf red;          // device scalar of vof_comm_allreduce_max
   DevBuf fzmap;        // k_tm's zero maps (kernels/fused_tm.h): one word per (interior row, k_tm tile column) of the F array and, behind it, of its twin -- one allocation: one buffer descriptor in the march --, reserved zeroed

@@ -29,6 +29,7 @@
 //   runtime/frames.h     the colour table, the buffers, launches and copies of vof_frame, the loop of vof_step_frames
 //   runtime/stats.h      the accumulator planes, launches and copies of vof_stats_*, the loop of vof_step_stats
 //   runtime/scene.h      plain C++: what vof_set_scene refuses, the packed records; the upload, the launch of k_scene, the summary
+//   runtime/regrid.h     vof_regrid: the work buffer, the order on the two handles' streams, the launches, dst's state, the summary; with runtime/regrid_check.h, plain C++: the factors and what is refused
 //   runtime/comm.h       strips over RCCL (bound with dlopen), the steps with their exchanges
 //   runtime/selftest.h   device side of the division self-test
 //   runtime/diag.h       diagnostic build only: the vof_debug_* entry points
@@ -48,6 +49,7 @@
 #include "runtime/frames.h"
 #include "runtime/stats.h"
 #include "runtime/scene.h"
+#include "runtime/regrid.h"
 #include "runtime/comm.h"
 #include "runtime/selftest.h"
 #ifdef VOF_WAVE_TIMES
@@ -253,6 +255,19 @@ int vof_set_scene(vof2d_handle h, const double* shapes, int64_t n, int32_t sampl
   if (!h) return VOF_EINVAL;
   if (const char* const msg = scene_check(shapes, n, samples, flags)) return fail(h, VOF_EINVAL, msg);
   return scene_run(h, shapes, n, samples, flags, summary);
+}
+// ---- a state carried onto a finer or coarser grid (kernels/regrid.h, runtime/regrid.h)
+int vof_regrid(vof2d_handle dst, vof2d_handle src, int32_t flags, double eps, double* summary) {
+  if (!dst || !src) return VOF_EINVAL;
+  if (dst == src) return fail(dst, VOF_EINVAL, "vof_regrid: dst and src are the same handle");
+  if (dst->device != src->device) return fail(dst, VOF_EINVAL, "vof_regrid: the handles are on different devices");
+  RegridFactors f;
+  if (const char* const msg = regrid_check(src->d.nx, src->d.ny, src->d.Lx, src->d.Ly, dst->d.nx, dst->d.ny, dst->d.Lx, dst->d.Ly, flags, eps, &f)) return fail(dst, VOF_EINVAL, msg);
+  for (vof2d_ctx* const h : {dst, src}) {
+    const int rc = check_verb_allowed(h, "vof_regrid needs the whole domain in both handles (a strip holds part of a state)");
+    if (rc) return h == dst ? rc : fail(dst, rc, src->err);
+  }
+  return regrid_run(dst, src, f, flags, eps, summary);
 }
 int vof_set_BC(vof2d_handle h) {
   if (!h) return VOF_EINVAL;

@@ -33,6 +33,7 @@
 //   frames.h     k_frame_cols, k_frame_fold, k_frame_paint   (extension: a colour-mapped picture of F, u, v, the speed, p, the vorticity or the dye: box averages in a fixed order, a 256-entry colour table, the interface marked on top)
 //   stats.h      k_stats, k_stats_fill, k_stats_summary   (extension: per-cell running sums of F, u, v and their products, envelopes, wet time and arrival step over a run: one streaming pass per sample over the fields and planes of doubles)
 //   scene.h      k_scene   (extension: an initial state painted from an ordered list of boxes, ellipses, half-planes and triangles, S x S samples a cell as bit masks in registers)
+//   regrid.h     k_regrid_refine, k_regrid_coarsen, k_regrid_ring, k_regrid_sum, k_regrid_finish   (extension: a state carried onto a finer or coarser grid: F of a mixed cell's children from its PLIC line, u, v linear along the face normal, p bilinear; box means the other way)
 //   residual_rule.h  the residual of a criterion from the two norms of a check, for host and device
 #pragma once
 #include "kernels/common.h"
@@ -58,3 +59,4 @@
 #include "kernels/frames.h"
 #include "kernels/stats.h"
 #include "kernels/scene.h"
+#include "kernels/regrid.h"

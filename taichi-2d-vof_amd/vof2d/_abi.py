@@ -67,6 +67,11 @@ VOF_SCENE_CLEAR = 1
 VOF_SCENE_MAX_SHAPES = 1024
 VOF_SCENE_SUM_SHAPES, VOF_SCENE_SUM_SAMPLES, VOF_SCENE_SUM_PAINTED, VOF_SCENE_SUM_MIXED, VOF_SCENE_SUM_ISTEP = range(5)
 VOF_SCENE_SUM_N = 8
+# vof_regrid: the flag, the limit and the slots of the summary (vof2d/regrid.py)
+VOF_REGRID_PLIC = 1
+VOF_REGRID_MAX_FACTOR = 16
+(VOF_REGRID_SUM_RX, VOF_REGRID_SUM_RY, VOF_REGRID_SUM_DIR, VOF_REGRID_SUM_PLIC_CELLS, VOF_REGRID_SUM_DEGENERATE, VOF_REGRID_SUM_F_SRC,
+ VOF_REGRID_SUM_F_DST, VOF_REGRID_SUM_ISTEP, VOF_REGRID_SUM_N) = range(9)
 
 ERRNAMES = {VOF_EINVAL: "VOF_EINVAL", VOF_EHIP: "VOF_EHIP", VOF_ENOMEM: "VOF_ENOMEM",
             VOF_ESTATE: "VOF_ESTATE"}
@@ -174,6 +179,7 @@ SIGNATURES = {
     "field_view": (C.c_int, [H, _str, C.POINTER(C.c_void_p), C.POINTER(_i64), C.POINTER(_i64),
                              C.POINTER(_i64)]),
     "copy_rows": (C.c_int, [H, H, _str, _i32, _i32]),
+    "regrid": (C.c_int, [H, H, _i32, _dbl, C.POINTER(_dbl)]),
     "get_vis_field": (C.c_int, [H, _str, C.c_void_p, C.c_size_t]),
     "interp_velocity": (C.c_int, [H, C.c_void_p, C.c_size_t]),
     "set_param": (C.c_int, [H, _str, _dbl]),
@@ -206,7 +212,7 @@ GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_pr
             "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "curvature", "blobs",
             "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges",
             "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye", "frame_set_lut", "frame", "step_frames",
-            "stats_begin", "stats_sample", "stats_get", "stats_summary", "step_stats", "set_scene")
+            "stats_begin", "stats_sample", "stats_get", "stats_summary", "step_stats", "set_scene", "regrid")
 
 
 class Api:

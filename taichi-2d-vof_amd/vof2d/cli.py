@@ -144,6 +144,13 @@ def build_parser():
     ext.add_argument('--scene-samples', type=int, default=None, metavar='S',
                      help="sample points per cell and axis, 1, 2, 4, 8 or 16 (default: the file's \"samples\", 8 without one)")
     ext.add_argument('--resume', default=None, metavar='FILE', help='continue from a file written by --save-every')
+    ext.add_argument('--regrid-from', default=None, metavar='FILE',
+                     help='start from a file written by --save-every on ANOTHER grid (finer or coarser by integer factors of at most 16) or in '
+                          'the other precision: its state is carried onto this run\'s --nx x --ny on the device (vof_regrid), the step count '
+                          'with it; the numerics of the file (dt ...) are not enforced, differences are reported; one GPU; not with '
+                          '--resume, --scene or --gpus N')
+    ext.add_argument('--regrid-no-plic', action='store_true',
+                     help='with --regrid-from: the cells of a refined mixed cell copy its F (default: their F comes from the cell\'s PLIC line)')
     return parser
 
 
@@ -224,6 +231,14 @@ def parse_args(argv=None):
         args.scene_shapes, args.scene_samples = load_scene(args)
     elif args.scene_over_ic or args.scene_samples is not None:
         parser.error("--scene-over-ic and --scene-samples belong to --scene FILE.json: pass that too")
+    if args.regrid_from is not None:
+        for on, name, why in ((bool(args.resume), "--resume", "a checkpoint of this grid is continued as it is"),
+                              (args.scene is not None, "--scene", "the file holds the state the run starts from, and a scene would paint over it"),
+                              (args.gpus > 1, "--gpus N", "vof_regrid works on whole-domain handles")):
+            if on:
+                raise SystemExit("--regrid-from cannot be combined with %s: %s (drop one of them)" % (name, why))
+    elif args.regrid_no_plic:
+        parser.error("--regrid-no-plic belongs to --regrid-from FILE: pass that too")
     def at_least_1(*options):                        # (in this order: the first refusal is the one reported)
         for opt in options:
             if getattr(args, opt + "_every") is not None and getattr(args, opt + "_every") < 1:
@@ -438,6 +453,35 @@ class _Single:
             self.eng.set(f, fields[f])
         self.eng.istep = istep
         self.base_courant = courant                  # (the device counter restarts at zero)
+
+    def regrid_from(self, path, plic, numerics):
+        """--regrid-from: a temporary solver of the file's grid and precision takes the file's state, vof_regrid carries it onto
+        this run's, the temporary is freed.  Returns (istep, the summary, (nx, ny, dtype) of the file, the numerics the file
+        recorded with other values as {name: (file's, this run's)})."""
+        from . import regrid
+        from .solver import VOF2D
+        a = self.args
+        try:
+            z = np.load(path, allow_pickle=False)
+            snx, sny, sdtype, istep = int(z["nx"]), int(z["ny"]), str(z["dtype"]), int(z["istep"])
+            fields = {f: z[f] for f in STATE}
+        except (OSError, KeyError, ValueError) as e:
+            raise SystemExit("--regrid-from %s: not a file written by --save-every: %s" % (path, e))
+        try:
+            regrid.factors(snx, sny, a.nx, a.ny)
+        except ValueError as e:
+            raise SystemExit("--regrid-from: %s holds a %dx%d run, this one is %dx%d: %s" % (path, snx, sny, a.nx, a.ny, e))
+        differ = {k: (z["num_" + k].item(), v) for k, v in numerics.items() if "num_" + k in z.files and z["num_" + k].item() != v}
+        tmp = VOF2D(snx, sny, dtype=sdtype, coord_cast=a.coord_cast, device=a.device, jacobi_iters=a.jacobi_iters, api=self.sim.api)
+        try:
+            for f in STATE:
+                tmp.eng.set(f, fields[f])
+            tmp.istep = istep
+            summ = self.eng.regrid_from(tmp.eng, plic=plic)
+        finally:
+            tmp.close()
+        self.base_courant = int(z["courant_violations"]) if "courant_violations" in z.files else 0
+        return istep, summ, (snx, sny, sdtype), differ
 
     def advance(self, n):
         """n steps; with --tracers the tracers are advanced by K dt behind every K-th step counted from where they were seeded,
@@ -679,6 +723,16 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         drv.load(fields, istep, warn0)
         if lead:
             say(f'>>> Resumed from {args.resume} at step {istep}.')
+    if getattr(args, "regrid_from", None):
+        if world > 1:
+            raise SystemExit("--regrid-from runs on one GPU (drop --gpus)")
+        istep, summ, (snx, sny, sdtype), differ = drv.regrid_from(args.regrid_from, not args.regrid_no_plic, numerics)
+        how = {1: "refined", -1: "coarsened", 0: "copied"}[int(summ["DIR"])]
+        say(f'>>> Regridded from {args.regrid_from} ({snx} x {sny} {sdtype}) at step {istep}: {how} by ({int(summ["RX"])}, {int(summ["RY"])}), '
+            f'{int(summ["PLIC_CELLS"])} cells from a PLIC line ({int(summ["DEGENERATE"])} mixed cells without an orientation); '
+            f'volume {summ["F_SRC"] / (snx * sny):.12g} -> {summ["F_DST"] / (nx * ny):.12g} of the domain.')
+        if differ:
+            say('>>> Numerics that differ from the file\'s (not enforced): ' + ', '.join(f'{k.replace("_", "-")} {a!r} -> {b!r}' for k, (a, b) in sorted(differ.items())))
 
     # every recording option is one recorder (vof2d/recorders.py); the loop steps to the nearest stop any of them asks for
     from . import recorders

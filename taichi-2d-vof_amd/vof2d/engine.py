@@ -531,6 +531,15 @@ class Engine:
     def copy_rows_from(self, src, name, g0, g1):
         self._ck(self.api.copy_rows(self._h, src._h, name.encode(), int(g0), int(g1)), "copy_rows")
 
+    def regrid_from(self, src, plic=True, eps=1e-6, summary=True):
+        """vof_regrid: F, u, v, p of the engine src carried onto this one's grid (finer or coarser by integer factors, or the
+        same; either dtype), the boundary conditions applied, istep taken over; asynchronous unless the summary is asked for.
+        Returns the summary as a dict keyed by regrid.SUMMARY, or None."""
+        from . import regrid
+        summ = (C.c_double * _abi.VOF_REGRID_SUM_N)() if summary else None
+        self._ck(self.api.regrid(self._h, src._h, _abi.VOF_REGRID_PLIC if plic else 0, float(eps), summ), "regrid")
+        return regrid.summary_of(list(summ)) if summary else None
+
     # -- scalars --------------------------------------------------------------
     def set_param(self, name, value):
         self._ck(self.api.set_param(self._h, name.encode(), float(value)), "set_param(%s)" % name)

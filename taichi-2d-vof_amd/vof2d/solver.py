@@ -250,6 +250,23 @@ class VOF2D:
     def istep(self, v):
         self.eng.istep = v
 
+    def regrid(self, nx, ny, dtype=None, plic=True, eps=1e-6, **consts):
+        """A new VOF2D of nx x ny cells on the same device that carries this one's state (vof_regrid): finer or coarser by
+        integer factors of at most regrid.MAX_FACTOR, or the same grid in the other dtype.  The constants are copied;
+        `consts` overrides them (dt, the material constants; Lx and Ly must stay).  F of a mixed cell's children comes from
+        the cell's PLIC line unless plic=False.  The summary of the call is left in `.regrid_summary` of the new solver."""
+        from . import regrid
+        from .engine import dtype_code
+        regrid.factors(self.nx, self.ny, nx, ny)   # (ValueError in front of any allocation)
+        d = self.desc
+        kw = {k: getattr(d, k) for k in ("Lx", "Ly", "rho_l", "rho_g", "nu_l", "nu_g", "sigma", "gx", "gy", "dt")}
+        kw["sigma"] = self.eng.get_param("sigma")
+        kw.update(consts)
+        new = VOF2D(nx, ny, dtype=d.dtype if dtype is None else dtype_code(dtype), coord_cast="f32" if d.coord_cast_f32 else "none",
+                    jacobi_iters=d.jacobi_iters, device=d.device, use_graph=not (d.flags & _abi.VOF_FLAG_NO_GRAPH), api=self.api, **kw)
+        new.regrid_summary = new.eng.regrid_from(self.eng, plic=plic, eps=eps)
+        return new
+
     def step_verbs(self, nsteps=1):
         """The main loop of 2dvof.py:506-528 written verb by verb (literal schedule)."""
         for _ in range(nsteps):

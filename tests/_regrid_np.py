@@ -1,0 +1,168 @@
+"""NumPy restatement of vof_regrid for the tests, term for term in the expression order stated at the head of
+taichi-2d-vof_amd/csrc/kernels/regrid.h; the line of a mixed cell is that of kernels/interface.h (tests/_interface_np.py restates the
+same expressions up to the segment; tests/test_regrid.py holds the two together), the order of the two sums of F that of
+tests/_reduce_np.py.  It is the yardstick for bits.
+
+Arrays are dense, ghost cells included: (nx + 2, ny + 2), indexed [i, j].  Every operand is converted to float64 first, a
+result is rounded once, by astype to the destination's dtype.  Selects are np.where on exactly the kernel's comparison.
+"""
+import numpy as np
+
+from _interface_np import diag_chunk_rows
+from _reduce_np import fixed_order
+from vof2d.regrid import factors
+
+FIELDS = ("F", "u", "v", "p")
+
+
+# ---------------------------------------------------------------------------- the line of a cell (iface_line)
+def line(F, eps, dx, dy):
+    """Of every interior cell of the dense F: (kind, a, b, alpha, flip_x, flip_y), each (nx, ny); kind 0: not mixed,
+    1: degenerate, 2: a line."""
+    F = np.asarray(F).astype(np.float64)
+    nx, ny = F.shape[0] - 2, F.shape[1] - 2
+    cx, cy = -1 / (2 * dx), -1 / (2 * dy)
+
+    def f(di, dj):
+        return F[1 + di: nx + 1 + di, 1 + dj: ny + 1 + dj]
+
+    with np.errstate(all="ignore"):
+        F0 = f(0, 0)
+        mixed = (eps < F0) & (F0 < 1.0 - eps)
+        mx1 = cx * (((f(1, 1) + f(1, 0)) - f(0, 1)) - f(0, 0)); my1 = cy * (((f(1, 1) - f(1, 0)) + f(0, 1)) - f(0, 0))
+        mx2 = cx * (((f(1, 0) + f(1, -1)) - f(0, 0)) - f(0, -1)); my2 = cy * (((f(1, 0) - f(1, -1)) + f(0, 0)) - f(0, -1))
+        mx3 = cx * (((f(0, 0) + f(0, -1)) - f(-1, 0)) - f(-1, -1)); my3 = cy * (((f(0, 0) - f(0, -1)) + f(-1, 0)) - f(-1, -1))
+        mx4 = cx * (((f(0, 1) + f(0, 0)) - f(-1, 1)) - f(-1, 0)); my4 = cy * (((f(0, 1) - f(0, 0)) + f(-1, 1)) - f(-1, 0))
+        mxsum = (((mx1 + mx2) + mx3) + mx4) / 4
+        mysum = (((my1 + my2) + my3) + my4) / 4
+        degen = mixed & (np.abs(mxsum) < 1e-10) & (np.abs(mysum) < 1e-10)
+        ax, by = np.abs(mxsum) * dx, np.abs(mysum) * dy
+        s = ax + by
+        a, b = ax / s, by / s
+        n1, n2 = np.where(a < b, a, b), np.where(a < b, b, a)
+        Fm = np.where(F0 <= 0.5, F0, 1.0 - F0)
+        alpha = np.where((2.0 * n2) * Fm < n1, np.sqrt(((2.0 * n1) * n2) * Fm), n2 * Fm + n1 * 0.5)
+        alpha = np.where(F0 > 0.5, 1.0 - alpha, alpha)
+    kind = np.where(mixed, np.where(degen, 1, 2), 0)
+    return kind, a, b, alpha, mxsum < 0.0, mysum < 0.0
+
+
+def child_F(a, b, alpha, flip_x, flip_y, k, m, rx, ry):
+    """regrid_child_F: the F of child (k, m) of the cells with these lines (arrays of one shape; k, m scalars or arrays)."""
+    drx, dry = float(rx), float(ry)
+    with np.errstate(all="ignore"):
+        k1 = np.where(flip_x, rx - 1 - k, k).astype(np.float64)
+        m1 = np.where(flip_y, ry - 1 - m, m).astype(np.float64)
+        a1, b1 = a / drx, b / dry
+        al = (alpha - a * (k1 / drx)) - b * (m1 / dry)
+        s1 = a1 + b1
+        n1, n2 = np.where(a1 < b1, a1, b1), np.where(a1 < b1, b1, a1)
+        t = s1 - al
+        return np.where(al <= 0.0, 0.0,
+                        np.where(al >= s1, 1.0,
+                                 np.where(al < n1, (al * al) / ((2.0 * n1) * n2),
+                                          np.where(al <= n2, (al - n1 * 0.5) / n2, 1.0 - (t * t) / ((2.0 * n1) * n2)))))
+
+
+# ---------------------------------------------------------------------------- the operators, interior cells only
+def refine_interior(src, rx, ry, plic, eps, dx, dy):
+    """src: {"F", "u", "v", "p"} dense.  Returns ({"F", "u", "v", "p"}: float64 (rx nx, ry ny), indexed [i - 1, j - 1], before the
+    rounding of the store; the number of cells refined from a line; the degenerate cells)."""
+    F, u, v, p = (np.asarray(src[n]).astype(np.float64) for n in FIELDS)
+    nx, ny = F.shape[0] - 2, F.shape[1] - 2
+    i = np.arange(1, rx * nx + 1); j = np.arange(1, ry * ny + 1)
+    I, J = (i - 1) // rx + 1, (j - 1) // ry + 1
+    k, m = (i - 1) - (I - 1) * rx, (j - 1) - (J - 1) * ry
+    II, JJ, kk, mm = I[:, None], J[None, :], k[:, None], m[None, :]
+    drx, dry = float(rx), float(ry)
+    with np.errstate(all="ignore"):
+        u0, u1 = u[II, JJ], u[II + 1, JJ]
+        un = np.where(kk == 0, u0, u0 + (kk.astype(np.float64) / drx) * (u1 - u0))
+        v0, v1 = v[II, JJ], v[II, JJ + 1]
+        vn = np.where(mm == 0, v0, v0 + (mm.astype(np.float64) / dry) * (v1 - v0))
+        si = (k.astype(np.float64) + 0.5) / drx - 0.5
+        sj = (m.astype(np.float64) + 0.5) / dry - 0.5
+        ib, wa = np.where(si < 0.0, I - 1, I)[:, None], np.where(si < 0.0, si + 1.0, si)[:, None]
+        jb, wb = np.where(sj < 0.0, J - 1, J)[None, :], np.where(sj < 0.0, sj + 1.0, sj)[None, :]
+        lo = p[ib, jb] + wa * (p[ib + 1, jb] - p[ib, jb])
+        hi = p[ib, jb + 1] + wa * (p[ib + 1, jb + 1] - p[ib, jb + 1])
+        pn = lo + wb * (hi - lo)
+        Fn = F[II, JJ] + np.zeros((1, 1))
+        nplic = ndeg = 0
+        if plic:
+            kind, a, b, alpha, fx, fy = line(F, eps, dx, dy)
+            g = lambda x: x[II - 1, JJ - 1]
+            Fn = np.where(g(kind) == 2, child_F(g(a), g(b), g(alpha), g(fx), g(fy), kk, mm, rx, ry), Fn)
+            nplic, ndeg = int((kind == 2).sum()), int((kind == 1).sum())
+    return {"F": Fn, "u": un, "v": vn, "p": pn}, nplic, ndeg
+
+
+def pair_sum(terms):
+    """PairSum: the terms (arrays of one shape, in order) added up in pairs -- the blocks of 2^l terms that start at a multiple
+    of 2^l, a binary counter whose carries are the additions --, what is left folded from the smallest block up."""
+    s = {}
+    for n, x in enumerate(terms):
+        carry, l = x, 0
+        while (n >> l) & 1:
+            carry = s.pop(l) + carry
+            l += 1
+        s[l] = carry
+    r = None
+    for l in sorted(s):
+        r = s[l] if r is None else s[l] + r
+    return r
+
+
+def coarsen_interior(src, rx, ry):
+    """The same the other way: float64 (nx / rx, ny / ry) arrays."""
+    F, u, v, p = (np.asarray(src[n]).astype(np.float64) for n in FIELDS)
+    nx, ny = (F.shape[0] - 2) // rx, (F.shape[1] - 2) // ry
+    io, jo = ((np.arange(1, nx + 1) - 1) * rx + 1)[:, None], ((np.arange(1, ny + 1) - 1) * ry + 1)[None, :]
+    with np.errstate(all="ignore"):
+        Fn = pair_sum(F[io + k, jo + m] for k in range(rx) for m in range(ry))
+        pn = pair_sum(p[io + k, jo + m] for k in range(rx) for m in range(ry))
+        un = pair_sum(u[io, jo + m] for m in range(ry))
+        vn = pair_sum(v[io + k, jo] for k in range(rx))
+        dn = float(rx * ry)
+        return {"F": Fn / dn, "u": un / float(ry), "v": vn / float(rx), "p": pn / dn}
+
+
+# ---------------------------------------------------------------------------- the boundary launch (k_set_bc<BC_ALL>, 2dvof.py:166-189)
+def set_bc(d):
+    F, u, v, p = (d[n] for n in FIELDS)
+    nx, ny = F.shape[0] - 2, F.shape[1] - 2
+    u[:, 0] = u[:, 1]; v[:, 1] = 0; F[:, 0] = F[:, 1]; p[:, 0] = p[:, 1]
+    u[:, ny + 1] = u[:, ny]; v[:, ny + 1] = 0; F[:, ny + 1] = F[:, ny]; p[:, ny + 1] = p[:, ny]
+    u[1, :] = 0; v[0, :] = v[1, :]; F[0, :] = F[1, :]; p[0, :] = p[1, :]
+    u[nx + 1, :] = 0; v[nx + 1, :] = v[nx, :]; F[nx + 1, :] = F[nx, :]; p[nx + 1, :] = p[nx, :]
+
+
+def f_sum(F):
+    """SUM_F_SRC / SUM_F_DST of the dense F: the order of kernels/reduce.h with the chunks of vof_diagnostics and 256 threads."""
+    F = np.asarray(F)
+    nx, ny = F.shape[0] - 2, F.shape[1] - 2
+    return fixed_order(F[1:nx + 1, 1:ny + 1].astype(np.float64), diag_chunk_rows(nx, ny), 256, "add")
+
+
+def restate(src, dst_nx, dst_ny, dst_dtype, plic=True, eps=1e-6, Lx=0.1, Ly=0.1, dx=None, dy=None, istep=0):
+    """vof_regrid of the dense source arrays src = {"F", "u", "v", "p"} into a handle of dst_nx x dst_ny cells of dst_dtype.
+    dx, dy: the source's cell sizes as vof_get_param reports them (default Lx / nx, Ly / ny).  Returns (fields, summary): the
+    four dense arrays of dst as vof_get_field returns them after the call, and the summary as a dict keyed by
+    vof2d.regrid.SUMMARY."""
+    snx, sny = np.asarray(src["F"]).shape[0] - 2, np.asarray(src["F"]).shape[1] - 2
+    rx, ry, direction = factors(snx, sny, dst_nx, dst_ny)
+    dx = Lx / snx if dx is None else dx
+    dy = Ly / sny if dy is None else dy
+    nplic = ndeg = 0
+    if direction > 0:
+        inner, nplic, ndeg = refine_interior(src, rx, ry, plic, eps, dx, dy)
+    else:
+        inner = coarsen_interior(src, rx, ry)
+    out = {}
+    for n in FIELDS:
+        out[n] = np.zeros((dst_nx + 2, dst_ny + 2), dtype=dst_dtype)
+        out[n][1:dst_nx + 1, 1:dst_ny + 1] = inner[n].astype(dst_dtype)
+    set_bc(out)
+    summary = {"RX": float(rx), "RY": float(ry), "DIR": float(direction), "PLIC_CELLS": float(nplic), "DEGENERATE": float(ndeg),
+               "F_SRC": f_sum(src["F"]), "F_DST": f_sum(out["F"]), "ISTEP": float(istep)}
+    return out, summary
