@@ -328,6 +328,55 @@ int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, do
 #define VOF_CURV_SUM_ISTEP 11
 #define VOF_CURV_SUM_N 16
 int vof_curvature(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary /* VOF_CURV_SUM_N */);
+/* Extension: where the flow's energy is and which term of the scheme is moving it, reduced on the device in one pass over F, u, v, p
+ * instead of copying four fields to the host.  A row is VOF_ENERGY_N doubles (unused slots read 0) over the cells i in [1, nx], j in
+ * [1, ny] and the faces the momentum predictor updates: the u faces i in [2, nx], j in [1, ny] and the v faces i in [1, nx], j in [2, ny].
+ * Whole-domain handles only (the stencil reaches three rows of F: a strip returns VOF_ESTATE, as does a phased step in progress).  Every
+ * operand is converted to double first (one code path for both dtypes), the constants are the doubles of vof_get_param; ghost cells a
+ * fused step left virtual are settled first.  With Fc = fmin(fmax(F, 0), 1), rho = rho_g * (1 - Fc) + rho_l * Fc, nu = nu_l * Fc +
+ * nu_g * (1.0 - Fc) (:202-203) and kappa the KAPPA_CSF of vof_curvature, a u face has, in the order of operations of 2dvof.py:209-219,
+ *   w = u[i,j]   v_here (:209)   dudx, dudy (:210-211, the upwind selects)
+ *   VX = nu[i,j] (u[i-1,j] - 2 w + u[i+1,j]) dxi2   VY = nu[i,j] (u[i,j-1] - 2 w + u[i,j+1]) dyi2   AX = w dudx   AY = v_here dudy
+ *   SG = F[i,j] == F[i-1,j] ? 0 : -sigma (F[i,j] - F[i-1,j]) (kappa[i,j] + kappa[i-1,j]) / 2 / dx * 2 / (rho[i,j] + rho[i-1,j])   (the raw F)
+ *   A = VX + VY - AX - AY + gx + SG: on an f64 handle w + dt * A is, bit for bit, the predictor's u_star[i,j]
+ *   r = (rho[i,j] + rho[i-1,j]) * 0.5 (:272)   m = r w
+ * and a v face the mirror (:222-232, :277: u_here, dvdx selected on u_here > 0, dvdy on v[i,j] > 0, gy, dy, rho[i,j] + rho[i,j-1]).
+ *   ISTEP, CELLS       the handle's istep; nx * ny
+ *   KE_U, KE_V         sum over the faces of (m * w) * 0.5
+ *   P_VISC, P_ADV, P_GRAV, P_SIGMA   sums over both face kinds of m * (VX + VY), -(m * (AX + AY)), m * g, m * SG: the rate at which each
+ *                      term of the predictor feeds (or drains) the kinetic energy, per dx dy
+ *   P_PRES             sum of -(w * ((p[i,j] - p[i-1,j]) * dxi)) and of the v mirror with dyi: summed by parts, sum p * div
+ *   SUM_RHO, SUM_RHO_I, SUM_RHO_J   sum rho, rho * i, rho * j over the cells (global integer indices as doubles, as SUM_FI, SUM_FJ)
+ *   SUM_GRADF          sum over the cells of sqrt(mxsum^2 + mysum^2), Youngs' gradient of vof_interface: the interface length per dx dy
+ *   MAX_ACC_SIGMA      max |SG| over both face kinds; starts at 0, a NaN counts as +inf
+ * The full expression order is stated in csrc/kernels/energy.h; a face belongs to the cell it is the west or south face of and the sums are
+ * formed in double in the fixed order of vof_diagnostics (no atomics): the same state gives the same bits, in either build.  A NaN operand
+ * reaches exactly the sums whose terms hold it.  vof2d/energy.py forms the physical quantities.  No field, istep, counter or cached graph
+ * changes, and a vof_step* that follows gives the bits it would have given without the call.  Synchronises and copies the row to out. */
+#define VOF_ENERGY_ISTEP 0
+#define VOF_ENERGY_CELLS 1
+#define VOF_ENERGY_KE_U 2
+#define VOF_ENERGY_KE_V 3
+#define VOF_ENERGY_P_VISC 4
+#define VOF_ENERGY_P_ADV 5
+#define VOF_ENERGY_P_GRAV 6
+#define VOF_ENERGY_P_SIGMA 7
+#define VOF_ENERGY_P_PRES 8
+#define VOF_ENERGY_SUM_RHO 9
+#define VOF_ENERGY_SUM_RHO_I 10
+#define VOF_ENERGY_SUM_RHO_J 11
+#define VOF_ENERGY_SUM_GRADF 12
+#define VOF_ENERGY_MAX_ACC_SIGMA 13
+#define VOF_ENERGY_N 16
+int vof_energy(vof2d_handle h, double* out /* VOF_ENERGY_N */);
+/* Extension: nsteps steps that record a time series of those rows on the device -- the contract of vof_step_diag with vof_energy in the
+ * place of vof_diagnostics: groups of `every` steps (vof_step, or vof_step_mg with mg_cycles >= 1), row r behind group r, a remainder
+ * stepped without a row, nothing waits before the end of the call, one copy of rows x VOF_ENERGY_N doubles out.  Row r equals, bit for
+ * bit, what the loop "step `every` steps; vof_energy" yields on a twin handle, and the state ends where vof_step(nsteps) / vof_step_mg
+ * leaves it.  The argument errors are those of vof_step_diag (VOF_EINVAL); a strip handle or a phased step in progress: VOF_ESTATE; the
+ * handle is left untouched by either.  nsteps == 0 does nothing and reports 0 rows. */
+int vof_step_energy(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion,
+                    double* out, int64_t cap_rows, int64_t* rows_written);
 /* Extension: how many pieces the liquid (or the gas) is in, and what each piece is doing: connected-component labelling and per-blob
  * sums on the device instead of copying F, u, v to the host.  Cells: the handle's owned interior cells, i in [max(own_lo, 1), min(own_hi, nx)],
  * j in [1, ny]; ghost cells are never members; every operand is converted to double first (one code path for both dtypes).

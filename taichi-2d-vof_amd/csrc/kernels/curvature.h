@@ -107,6 +107,18 @@ __device__ __forceinline__ void young_unit(const CurvConsts& c, const Geom& g, c
   uy = inside ? (tiny ? sy : sy / mag) : 0.0;
 }
 
+// KAPPA_CSF of the cell (a, b) of the interior, everything gathered from F (four neighbourhoods of 3 x 3: 36 loads, issued together).
+// Shared with kernels/energy.h, which needs it at both cells of a face the interface crosses.
+template <typename T>
+__device__ __forceinline__ double kappa_csf(const CurvConsts& c, const Geom& g, const T* __restrict__ F, int a, int b) {
+  double xe, xw, yn, ys, other;
+  young_unit<T>(c, g, F, a + 1, b, xe, other);
+  young_unit<T>(c, g, F, a - 1, b, xw, other);
+  young_unit<T>(c, g, F, a, b + 1, other, yn);
+  young_unit<T>(c, g, F, a, b - 1, other, ys);
+  return -(mul_rounded(c.kx, xe - xw) + mul_rounded(c.ky, yn - ys));
+}
+
 // the cell (i, j): fm, f0, fp as in young_sums (from the march's registers), everything else gathered from F.
 // Returns 0: not mixed, 1: degenerate, 2: a row (s[CV_*] filled).
 template <typename T>
@@ -141,14 +153,9 @@ __device__ __forceinline__ int curv_cell(const CurvConsts& c, const Geom& g, con
   const double hpp = (((H[2] - mul_rounded(2.0, H[1])) + H[0]) * hs) / (ht * ht);
   const double q = 1.0 + mul_rounded(hp, hp);
   const double kappa = hpp / (q * __builtin_sqrt(q));
-  double xe, xw, yn, ys, other;
-  young_unit<T>(c, g, F, i + 1, j, xe, other);
-  young_unit<T>(c, g, F, i - 1, j, xw, other);
-  young_unit<T>(c, g, F, i, j + 1, other, yn);
-  young_unit<T>(c, g, F, i, j - 1, other, ys);
   s[CV_I] = (double)i; s[CV_J] = (double)j;
   s[CV_KAPPA] = valid ? kappa : 0.0; s[CV_VALID] = valid ? 1.0 : 0.0;
-  s[CV_AXIS] = along_i ? 1.0 : 0.0; s[CV_KAPPA_CSF] = -(mul_rounded(c.kx, xe - xw) + mul_rounded(c.ky, yn - ys));
+  s[CV_AXIS] = along_i ? 1.0 : 0.0; s[CV_KAPPA_CSF] = kappa_csf<T>(c, g, F, i, j);
   s[CV_HP] = valid ? hp : 0.0; s[CV_F] = Fc;
   return 2;
 }

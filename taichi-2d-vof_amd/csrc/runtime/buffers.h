@@ -63,6 +63,7 @@ struct WorkBufs {
   DevBuf iface_rows;   // ... the segments, VOF_IFACE_N doubles each, grown on demand
   DevBuf curv_work;    // vof_curvature (runtime/curvature.h, CurvCarve): the row counts, turned into offsets in place; the partials; the summary
   DevBuf curv_rows;    // ... the rows, VOF_CURV_N doubles each, grown on demand
+  RowBufs energy;      // vof_energy / vof_step_energy (runtime/energy.h): the partials of k_energy, rows of VOF_ENERGY_N doubles
   DevBuf blob_work;    // vof_blobs (runtime/blobs.h, BlobCarve): what the geometry fixes
   DevBuf blob_rec;     // ... grown on demand: the integer records of the blobs (kBlobRec ints each),
   DevBuf blob_off;     // the wave offsets and

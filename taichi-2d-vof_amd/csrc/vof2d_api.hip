@@ -22,6 +22,7 @@
 //   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
 //   runtime/interface.h  the buffers, launches and copies of vof_interface
 //   runtime/curvature.h  the buffers, launches and copies of vof_curvature
+//   runtime/energy.h     the launch of k_energy on the reduced-row path of vof_diagnostics, the loop of vof_step_energy
 //   runtime/blobs.h      the buffers, launches and copies of vof_blobs
 //   runtime/tracers.h    the buffers, launches and copies of vof_tracers_*, the loop of vof_step_tracers
 //   runtime/depths.h     the buffers, launches and copies of vof_depths and vof_gauges_*, the loop of vof_step_gauges
@@ -42,6 +43,7 @@
 #include "runtime/diag_reduce.h"
 #include "runtime/interface.h"
 #include "runtime/curvature.h"
+#include "runtime/energy.h"
 #include "runtime/blobs.h"
 #include "runtime/tracers.h"
 #include "runtime/depths.h"
@@ -495,6 +497,25 @@ int vof_curvature(vof2d_handle h, double eps, double* rows, int64_t cap_rows, do
   if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_curvature keeps 32-bit offsets: at most 2^31 - 1 cells");
   if (const int rc = check_verb_allowed(h, "vof_curvature needs the whole domain in one handle (curvature over row strips is not built)")) return rc;
   return curv_run(h, eps, rows, cap_rows, summary);
+}
+
+// ---- the energy budget of the flow (kernels/energy.h, runtime/energy.h)
+int vof_energy(vof2d_handle h, double* out) {
+  if (!h || !out) return VOF_EINVAL;
+  if (const int rc = check_verb_allowed(h, "vof_energy needs the whole domain in one handle (the energy budget over row strips is not built)")) return rc;
+  int rc = reduced_prepare(h, kEnergyVerb, 1);
+  if (rc) return rc;
+  if ((rc = energy_enqueue(h, 0))) return rc;
+  return read_back(h, out, h->buf.energy.rows.p, VOF_ENERGY_N * sizeof(double));
+}
+int vof_step_energy(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycles, int32_t criterion, double* out, int64_t cap_rows,
+                    int64_t* rows_written) {
+  if (const int rc = check_step_args(h, nsteps, every, mg_cycles, criterion)) return rc;
+  if (cap_rows < nsteps / every) return fail(h, VOF_EINVAL, "cap_rows is smaller than nsteps / every");
+  if (!out && nsteps / every > 0) return fail(h, VOF_EINVAL, "out is NULL and at least one row is due");
+  if (const int rc = check_verb_allowed(h, "vof_step_energy needs the whole domain in one handle (the energy budget over row strips is not built)")) return rc;
+  if (no_steps(nsteps, rows_written)) return VOF_OK;
+  return step_energy_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
 }
 
 // ---- droplets and bubbles, labelled and measured (kernels/blobs.h, runtime/blobs.h)

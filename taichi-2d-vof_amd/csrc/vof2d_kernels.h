@@ -26,6 +26,7 @@
 //   diag.h       k_diag   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
 //   interface.h  k_iface, k_iface_scan   (extension: the interface as PLIC segments, counted, scanned and emitted in (i, j) order)
 //   curvature.h  k_curv, k_curv_scan   (extension: height-function curvature of every mixed cell beside the solver's own CSF curvature, counted, scanned and emitted like the segments)
+//   energy.h     k_energy   (extension: the energy budget -- face kinetic energy, density moments, the interface measure and the power of every term of the momentum predictor, evaluated face by face in double with kappa gathered at the interface, in one fixed-order pass over F, u, v, p)
 //   blobs.h      k_blob_init, k_blob_merge, k_blob_flatten, k_blob_number, k_blob_label, k_blob_stats, k_blob_summary, k_blob_plan, k_blob_sums, k_blob_rows   (extension: droplets and bubbles labelled by union-find, numbered by first cell, measured in a fixed order)
 //   tracers.h    k_tracer_advance, k_tracer_sample, k_tracer_finish   (extension: passive particles, one per lane: bilinear gather on the staggered grid, midpoint rule, walls)
 //   depths.h     k_depths, k_depths_fold, k_depths_finish, k_gauge_sample   (extension: both marginals of F, the top of the liquid per row and the front in one pass over F; fixed sensors that sample u, v, F, p and read them)
@@ -52,6 +53,7 @@
 #include "kernels/diag.h"
 #include "kernels/interface.h"
 #include "kernels/curvature.h"
+#include "kernels/energy.h"
 #include "kernels/blobs.h"
 #include "kernels/tracers.h"
 #include "kernels/depths.h"

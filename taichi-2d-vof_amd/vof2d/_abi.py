@@ -24,6 +24,10 @@ VOF_CURV_I, VOF_CURV_J, VOF_CURV_KAPPA, VOF_CURV_VALID, VOF_CURV_AXIS, VOF_CURV_
 (VOF_CURV_SUM_ROWS, VOF_CURV_SUM_DEGENERATE, VOF_CURV_SUM_VALID, VOF_CURV_SUM_K, VOF_CURV_SUM_K2, VOF_CURV_SUM_MIN_K, VOF_CURV_SUM_MAX_K,
  VOF_CURV_SUM_CSF, VOF_CURV_SUM_CSF2, VOF_CURV_SUM_MIN_CSF, VOF_CURV_SUM_MAX_CSF, VOF_CURV_SUM_ISTEP) = range(12)
 VOF_CURV_SUM_N = 16
+# vof_energy: the slots of a row (vof2d/energy.py)
+(VOF_ENERGY_ISTEP, VOF_ENERGY_CELLS, VOF_ENERGY_KE_U, VOF_ENERGY_KE_V, VOF_ENERGY_P_VISC, VOF_ENERGY_P_ADV, VOF_ENERGY_P_GRAV, VOF_ENERGY_P_SIGMA,
+ VOF_ENERGY_P_PRES, VOF_ENERGY_SUM_RHO, VOF_ENERGY_SUM_RHO_I, VOF_ENERGY_SUM_RHO_J, VOF_ENERGY_SUM_GRADF, VOF_ENERGY_MAX_ACC_SIGMA) = range(14)
+VOF_ENERGY_N = 16
 # vof_blobs: the phases, the slots of a blob's row and of the summary (vof2d/blobs.py)
 VOF_BLOB_LIQUID, VOF_BLOB_GAS = 0, 1
 (VOF_BLOB_I0, VOF_BLOB_J0, VOF_BLOB_CELLS, VOF_BLOB_IMIN, VOF_BLOB_IMAX, VOF_BLOB_JMIN, VOF_BLOB_JMAX, VOF_BLOB_SUM_W, VOF_BLOB_SUM_WI,
@@ -150,6 +154,8 @@ SIGNATURES = {
     "step_diag": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
     "interface": (C.c_int, [H, _dbl, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
     "curvature": (C.c_int, [H, _dbl, C.POINTER(_dbl), _i64, C.POINTER(_dbl)]),
+    "energy": (C.c_int, [H, C.POINTER(_dbl)]),
+    "step_energy": (C.c_int, [H, _i64, _i64, _i32, _i32, C.POINTER(_dbl), _i64, C.POINTER(_i64)]),
     "blobs": (C.c_int, [H, _i32, _dbl, C.POINTER(_dbl), _i64, C.POINTER(_i32), C.c_size_t, C.POINTER(_dbl)]),
     "tracers_set": (C.c_int, [H, C.POINTER(_dbl), _i64]),
     "tracers_advance": (C.c_int, [H, _dbl]),
@@ -209,7 +215,7 @@ SIGNATURES = {
 # entry points that only the GPU library implements (timing / profiling on a HIP stream)
 GPU_ONLY = ("timer_start", "timer_stop", "time_jacobi", "profile_steps", "get_profile", "reset_profile",
             "selftest_division", "comm_get_unique_id", "comm_init", "comm_exchange", "step_exchange", "step_tm_piece", "comm_destroy",
-            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "curvature", "blobs",
+            "comm_allreduce_max", "comm_info", "solve_p_cg", "solve_p_mg", "step_mg", "diagnostics", "step_diag", "interface", "curvature", "energy", "step_energy", "blobs",
             "tracers_set", "tracers_advance", "tracers_get", "step_tracers", "depths", "gauges_set", "gauges_get", "step_gauges",
             "dye_set", "dye_get", "dye_advance", "dye_stats", "step_dye", "frame_set_lut", "frame", "step_frames",
             "stats_begin", "stats_sample", "stats_get", "stats_summary", "step_stats", "set_scene", "regrid")

@@ -68,6 +68,10 @@ def build_parser():
                           'rms divergence of u, v, max |u|, max |v|, CFL number, min and max F, reduced on the device '
                           '(vof_step_diag; with --jacobi-tol, --verbs or --gpus N vof_diagnostics at the multiples of N); the '
                           'status line then reports volume, div_max and cfl')
+    ext.add_argument('--energy-every', type=int, default=None, metavar='N',
+                     help='every N steps append a row to data/energy.csv: kinetic, potential and surface energy, their sum, and the rate at '
+                          'which viscosity, the upwind advection, gravity, surface tension and the pressure gradient feed the kinetic energy -- '
+                          'the momentum predictor\'s own terms evaluated face by face in double and reduced on the device (vof_energy); one GPU')
     ext.add_argument('--interface-every', type=int, default=None, metavar='N',
                      help='every N steps write data/interface_NNNNNN.npy -- the interface as one PLIC segment per mixed cell, '
                           'rows of i, j, x0, y0, x1, y1, nx, ny extracted on the device (vof_interface) -- and append istep, '
@@ -243,9 +247,11 @@ def parse_args(argv=None):
         for opt in options:
             if getattr(args, opt + "_every") is not None and getattr(args, opt + "_every") < 1:
                 parser.error("--%s-every needs N >= 1" % opt)
-    at_least_1("diag", "interface", "blobs", "curvature")
+    at_least_1("diag", "interface", "blobs", "curvature", "energy")
     if args.curvature_every is not None and args.gpus > 1:
         parser.error("--curvature-every runs on one GPU (curvature over row strips is not built): drop --gpus")
+    if args.energy_every is not None and args.gpus > 1:
+        parser.error("--energy-every runs on one GPU (the energy budget over row strips is not built): drop --gpus")
     if not 0.0 < args.blobs_threshold < 1.0:
         parser.error("--blobs-threshold needs 0 < T < 1")
     if args.tracers < 0:
@@ -682,6 +688,8 @@ def run(args, api=None, comm=None, rank=None, world=None, out=None):
         raise SystemExit("--pressure-solver %s runs on one GPU (drop --gpus)" % args.pressure_solver)
     if world > 1 and getattr(args, "mg_cycles", 0) > 0:
         raise SystemExit("--mg-cycles runs on one GPU (drop --gpus)")
+    if world > 1 and getattr(args, "energy_every", None):
+        raise SystemExit("--energy-every runs on one GPU (the energy budget over row strips is not built): drop --gpus")
     if world > 1 and world != args.gpus:
         raise SystemExit("--gpus %d but the launcher started %d ranks" % (args.gpus, world))
     if api is None:

@@ -247,6 +247,26 @@ class Engine:
                                 lambda ptr, cap: self.api.curvature(self._h, float(eps), ptr, cap, summ))
         return rows, curvature.summary_of(list(summ))
 
+    def energy(self):
+        """vof_energy: the energy budget in one fixed-order pass over F, u, v, p -- face kinetic energy, density moments, the
+        interface measure and the power of every term of the momentum predictor; whole-domain handles only.  The raw row as a
+        dict keyed by energy.NAMES (the physical quantities: energy.derive)."""
+        from . import energy
+        row = (C.c_double * _abi.VOF_ENERGY_N)()
+        self._ck(self.api.energy(self._h, row), "energy")
+        return energy.raw_of(list(row))
+
+    def step_energy(self, nsteps, every, mg_cycles=0, criterion="rel"):
+        """vof_step_energy: nsteps steps (of vof_step; of vof_step_mg with mg_cycles >= 1), a row of the energy budget recorded on
+        the device behind every `every` of them, one read-back at the end; returns the (rows, VOF_ENERGY_N) float64 array."""
+        crit = criterion_code(criterion)
+        rows = _due(int(nsteps), int(every))
+        out = np.zeros((rows, _abi.VOF_ENERGY_N), dtype=np.float64)
+        done = C.c_int64()
+        self._ck(self.api.step_energy(self._h, int(nsteps), int(every), int(mg_cycles), crit,
+                                      out.ctypes.data_as(C.POINTER(C.c_double)) if rows else None, rows, C.byref(done)), "step_energy")
+        return out[:done.value]
+
     def blobs(self, phase="liquid", threshold=0.5, labels=False):
         """vof_blobs: the connected pieces of the liquid (F >= threshold) or of the gas (F < threshold) on the owned interior
         rows, labelled and measured on the device; returns (rows, summary[, labels]): an (n, VOF_BLOB_N) float64 array in

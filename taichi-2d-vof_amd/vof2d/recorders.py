@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from . import blobs, cli, curvature, diag, dye, frames, gauges, stats, tracers
+from . import blobs, cli, curvature, diag, dye, energy, frames, gauges, stats, tracers
 
 NSTEP = 100  # Interval to update output                       (2dvof.py:497)
 
@@ -85,6 +85,23 @@ class Diag(Recorder):
             derived = [diag.derive(raw, run.dx, run.dy, run.dt, run.nx, run.ny) for raw in rows]
             append(self.path, (csv_row(int(raw["ISTEP"]), run.dt, d, diag.DERIVED) for raw, d in zip(rows, derived)))
             run.diag_last = derived[-1]              # (the status line reports it)
+
+
+class Energy(Recorder):
+    """--energy-every: the energy budget (vof_energy) is read between calls, like the interface; one GPU (cli.run refuses strips)."""
+    path, header = 'data/energy.csv', ','.join(('istep', 'time') + energy.DERIVED)
+
+    def setup(self, run):
+        if not hasattr(run.api, "energy"):
+            raise SystemExit("--energy-every needs the energy verb of the HIP library (vof_energy): this backend has none")
+        super().setup(run)
+        eng = run.eng
+        self.consts = (eng.get_param("gx"), eng.get_param("gy"), eng.get_param("sigma"))
+
+    def after(self, i):
+        if due(i, self.every):
+            run = self.run
+            append(self.path, [csv_row(i, run.dt, energy.derive(run.eng.energy(), run.dx, run.dy, *self.consts), energy.DERIVED)])
 
 
 class Interface(Recorder):
@@ -356,11 +373,11 @@ class Display(Recorder):
 
 
 def recorders_of(args, drv, world):
-    """The recorders the options ask for, in the order they act at a stop.  The curvature, tracers, gauges, frames and statistics run on one GPU;
+    """The recorders the options ask for, in the order they act at a stop.  The energy budget, curvature, tracers, gauges, frames and statistics run on one GPU;
     strips get the rest (the dye refuses them)."""
     opt = lambda name: getattr(args, name, None) or 0
     one = world == 1
-    every = [Diag(drv.diag_every, stop=not drv.diag_in_advance), Interface(opt("interface_every")), Curvature(opt("curvature_every") if one else 0), Blobs(opt("blobs_every")),
+    every = [Diag(drv.diag_every, stop=not drv.diag_in_advance), Energy(opt("energy_every")), Interface(opt("interface_every")), Curvature(opt("curvature_every") if one else 0), Blobs(opt("blobs_every")),
              Tracers(save=opt("tracers_save_every"), on=one and opt("tracers")),
              Gauges(opt("gauges_every"), stop=not getattr(drv, "gauges_in_advance", False), on=one and (opt("gauge") or opt("gauges_file") or opt("gauges_every"))),
              Depths(opt("depths_every")),

@@ -147,6 +147,10 @@ class VOF2D:
         """Height-function curvature of every mixed cell beside the solver's own, on the device (vof_curvature): (rows, summary), vof2d/curvature.py."""
         return self.eng.curvature(eps)
 
+    def energy(self):
+        """The raw row of vof_energy as a dict (vof2d/energy.py: NAMES, derive, rates)."""
+        return self.eng.energy()
+
     def blobs(self, phase="liquid", threshold=0.5, labels=False):
         """Droplets or bubbles labelled and measured on the device (vof_blobs): (rows, summary[, labels]), vof2d/blobs.py."""
         return self.eng.blobs(phase, threshold, labels)
@@ -241,6 +245,10 @@ class VOF2D:
     def step_diag(self, nsteps, every, mg_cycles=0, criterion="rel"):
         """nsteps steps with a row of diagnostics recorded on the device every `every` steps (vof_step_diag)."""
         return self.eng.step_diag(nsteps, every, mg_cycles, criterion)
+
+    def step_energy(self, nsteps, every, mg_cycles=0, criterion="rel"):
+        """nsteps steps with a row of the energy budget recorded on the device every `every` steps (vof_step_energy)."""
+        return self.eng.step_energy(nsteps, every, mg_cycles, criterion)
 
     @property
     def istep(self):
