@@ -28,7 +28,7 @@
 // was linked.  Nothing is flattened in the merge launch; k_blob_flatten starts behind the launch boundary that makes
 // every link visible, and its own stores replace a parent by the root, again an ancestor.
 //
-// NUMBERING: k_iface_scan (kernels/interface.h, one block) turns the root counts into exclusive offsets; a root's rank
+// NUMBERING: k_cell_rows_scan (kernels/cell_rows.h, one block) turns the root counts into exclusive offsets; a root's rank
 // within its (row, tile) in column order (ballot + mbcnt) plus the offset is its blob index (k_blob_number, which also
 // starts the blob's integer record); k_blob_label writes index[root(cell)] over parent: the labels.
 // INTEGER RECORD per blob (kBlobRec ints: first key, cells, imin, imax, jmin, jmax) by 32-bit integer atomics, whose
@@ -48,7 +48,7 @@
 //   3. lanes -> wave by wave_fold of kernels/reduce.h; one partial of kBlobSums doubles per wave (k_blob_sums);
 //   4. one wave per blob folds the blob's partials: lane l starts from 0 and takes partials l, l + 64, ... in that
 //      order, then wave_fold again (k_blob_rows, which also writes the row).
-// Cost of the sum pass: the sum of the box areas (in waves: k_blob_plan, scanned by k_iface_scan); a blob whose box is
+// Cost of the sum pass: the sum of the box areas (in waves: k_blob_plan, scanned by k_cell_rows_scan); a blob whose box is
 // most of the domain is spread over (rows / kBlobRows) x tiles waves like any pass over the grid.
 // No contraction (-ffp-contract=off): each term is the bits of the line above.
 #pragma once
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void k_blob_flatten(Geom g, int R, int* __rest
 }
 
 // ------------------------------------------------------------------ roots -> blob indices, the start of the records
-// cnt: the exclusive offsets k_iface_scan left there.  index[key of a root] = its blob index.
+// cnt: the exclusive offsets k_cell_rows_scan left there.  index[key of a root] = its blob index.
 template <int V>
 __global__ __launch_bounds__(256) void k_blob_number(Geom g, int R, const int* __restrict__ parent, const int* __restrict__ cnt, int* __restrict__ index,
                                                       int* __restrict__ rec) {

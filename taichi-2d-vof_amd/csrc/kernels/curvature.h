@@ -1,4 +1,4 @@
-// kernels/curvature.h -- height-function interface curvature on the device (k_curv, k_curv_scan): Youngs' sums pick the axis, 7 x 3 heights, the solver's own CSF curvature beside it, an ordered compaction
+// kernels/curvature.h -- height-function interface curvature on the device (CurvVerb of kernels/cell_rows.h): Youngs' sums pick the axis, 7 x 3 heights, the solver's own CSF curvature beside it
 //
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
@@ -37,23 +37,17 @@
 // No contraction: each term is the bits of the line above in either build -- every product whose result an addition or subtraction
 // takes goes through mul_rounded (kernels/cells.h).
 //
-// Order of the rows: ascending (i, j), i first.  Three launches, no atomics (the shape of kernels/interface.h):
-//   k_curv<EMIT = false>   a wave marches its 64 * V columns over its chunk of rows with the rows i - 1, i, i + 1 of F in registers and
-//                          skips, wave-uniformly, a row of its tile without a mixed cell; the lanes that hold a mixed cell gather the
-//                          rest of their stencils (7 x 3 heights, the plus-shaped 5 x 5 of KAPPA_CSF) with clamped-index loads of
-//                          rows the march has just streamed.  It writes the number of rows of every (row, column tile) into
-//                          cnt[(i - 1) * ntj + tile]; the sums and extrema go through the reduction of kernels/reduce.h
-//   k_curv_scan            one block: cnt -> exclusive offsets in place (scan_counts of kernels/interface.h), and the summary
-//   k_curv<EMIT = true>    recomputes the cells and stores row k of a (row, tile) at row offset[(row, tile)] + k of the output (ballot +
-//                          mbcnt over the lanes' V cells); rows from `cap` on are not stored
+// The rows, in ascending (i, j), come out of the three launches of kernels/cell_rows.h (count, scan, emit), CurvVerb below being the verb.  The
+// march hands curv_cell the rows i - 1, i, i + 1 of F from its registers; the lanes that hold a mixed cell gather the rest of their stencils
+// (7 x 3 heights, the plus-shaped 5 x 5 of KAPPA_CSF) with clamped-index loads of rows the march has just streamed.
 // The reduced values, CVP_NS sums then CVP_NM maxima: a lane adds, row by row, column by column, 1 per degenerate cell, 1 per VALID row,
 // KAPPA and KAPPA * KAPPA of every VALID row, KAPPA_CSF and KAPPA_CSF * KAPPA_CSF of every row, and takes the maxima of -KAPPA, KAPPA
 // (VALID rows), -KAPPA_CSF, KAPPA_CSF (all rows) with "a NaN counts as +inf" (diag_max); from there the reduction of
-// kernels/reduce.h, folded by k_curv_scan (one block of kCurvScanThreads threads).  A minimum is the negated maximum of the
+// kernels/reduce.h, folded by the scan (one block of 1024 threads).  A minimum is the negated maximum of the
 // negatives.  With no operand a sum reads 0, a maximum what the fold starts from, -inf, and a minimum +inf.
 #pragma once
 #include "cells.h"
-#include "interface.h"
+#include "cell_rows.h"
 
 namespace vof {
 
@@ -64,7 +58,6 @@ enum : int { CVS_ROWS = 0, CVS_DEGENERATE, CVS_VALID, CVS_SUM_K, CVS_SUM_K2, CVS
 // the reduced values: CVP_NS sums, then CVP_NM maxima
 enum : int { CVP_DEGENERATE = 0, CVP_VALID, CVP_SUM_K, CVP_SUM_K2, CVP_SUM_CSF, CVP_SUM_CSF2, CVP_NS = 6,
               CVP_NEG_MIN_K = 6, CVP_MAX_K, CVP_NEG_MIN_CSF, CVP_MAX_CSF, CVP_N = 10, CVP_NM = CVP_N - CVP_NS };
-constexpr int kCurvScanThreads = 1024;
 
 struct CurvConsts { double eps, one_m_eps, cx, cy, dx, dy, kx, ky; };
 
@@ -160,132 +153,59 @@ __device__ __forceinline__ int curv_cell(const CurvConsts& c, const Geom& g, con
   return 2;
 }
 
-// ------------------------------------------------------------------ the pass over F: count (+ the reduced values), or emit
-// cnt: EMIT = false, written: rows per (row, tile); EMIT = true, read: the exclusive offsets k_curv_scan left there.
-// part: CVP_N doubles per block -- EMIT = false only.  rows: the output, `cap` rows of CV_N doubles -- EMIT = true only.
-template <typename T, int V, bool EMIT>
-__global__ __launch_bounds__(256) void k_curv(Geom g, const T* __restrict__ F, int R, CurvConsts c, int* __restrict__ cnt, double* __restrict__ part,
-                                               double* __restrict__ rows, long long cap) {
-  int j0, ra, rb;
-  const bool active = cell_tile<V>(g, R, j0, ra, rb);
-  constexpr double NONE = -__builtin_huge_val();
-  double acc[CVP_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, NONE, NONE, NONE, NONE};
-  int ndeg = 0, nvalid = 0;   // (integers until the lanes are folded: one register each, the same values)
-  if (active) {
-    const int ny = g.ny;
-    const int64_t pitch = g.pitch;
-    const int lane = threadIdx.x & 63;
-    const int tile = (j0 - 1) / (64 * V);   // (wave-uniform)
-    size_t o = at(g, ra, j0);
-    Row<T, V> wm, w0, wp;
-    load_row<T, V>(wm, F + o - pitch);
-    load_row<T, V>(w0, F + o);
-    for (int i = ra; i <= rb; ++i) {
-      load_row<T, V>(wp, F + o + pitch);
-      bool cand[V];
-      bool any = false;
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        const double f = (double)w0.c[q];
-        cand[q] = j0 + q <= ny && c.eps < f && f < c.one_m_eps;
-        any = any || cand[q];
+// ------------------------------------------------------------------ the verb of kernels/cell_rows.h
+struct CurvVerb {
+  enum : int { ROW_N = CV_N, SUM_N = CVS_N, NS = CVP_NS, NM = CVP_NM };
+  using Consts = CurvConsts;
+  template <typename T>
+  static __device__ __forceinline__ int cell(const CurvConsts& c, const Geom& g, const T* __restrict__ F, const double (&fm)[3], const double (&f0)[3],
+                                             const double (&fp)[3], int i, int j, double (&s)[CV_N]) {
+    return curv_cell<T>(c, g, F, fm, f0, fp, i, j, s);
+  }
+  struct Tally {
+    static constexpr double NONE = -__builtin_huge_val();
+    double acc[CVP_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, NONE, NONE, NONE, NONE};
+    int ndeg = 0, nvalid = 0;
+    __device__ __forceinline__ void row(const double (&s)[CV_N]) {
+      const double kc = s[CV_KAPPA_CSF];
+      acc[CVP_SUM_CSF] += kc;
+      acc[CVP_SUM_CSF2] += mul_rounded(kc, kc);
+      acc[CVP_NEG_MIN_CSF] = diag_max(acc[CVP_NEG_MIN_CSF], -kc);
+      acc[CVP_MAX_CSF] = diag_max(acc[CVP_MAX_CSF], kc);
+      if (s[CV_VALID] != 0.0) {
+        const double k = s[CV_KAPPA];
+        ++nvalid;
+        acc[CVP_SUM_K] += k;
+        acc[CVP_SUM_K2] += mul_rounded(k, k);
+        acc[CVP_NEG_MIN_K] = diag_max(acc[CVP_NEG_MIN_K], -k);
+        acc[CVP_MAX_K] = diag_max(acc[CVP_MAX_K], k);
       }
-      int total = 0;
-      if (__builtin_amdgcn_ballot_w64(any) != 0ull) {   // (wave-uniform skip: most rows of most tiles hold no mixed cell)
-        const long long base = EMIT ? (long long)cnt[(size_t)(i - g.ilo) * g.ntj + tile] : 0ll;
-        int before = 0;   // rows of this grid row in the lanes below this one
-        int kind[V];
-        double row[V][CV_N];
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          kind[q] = 0;
-          if (cand[q]) {
-            const double fm[3] = {(double)left_of(wm, q), (double)wm.c[q], (double)right_of(wm, q)};
-            const double f0[3] = {(double)left_of(w0, q), (double)w0.c[q], (double)right_of(w0, q)};
-            const double fp[3] = {(double)left_of(wp, q), (double)wp.c[q], (double)right_of(wp, q)};
-            kind[q] = curv_cell<T>(c, g, F, fm, f0, fp, i, j0 + q, row[q]);
-          }
-          const unsigned long long b = __builtin_amdgcn_ballot_w64(kind[q] == 2);
-          before += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-          total += __builtin_popcountll(b);
-        }
-        int rank = before;   // of the lane's first row within the grid row's tile, in column order
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          if (kind[q] == 2) {
-            if constexpr (EMIT) {
-              const long long k = base + rank;
-              if (k < cap) {
-                Pack<double, 2>* dst = reinterpret_cast<Pack<double, 2>*>(rows + (size_t)k * CV_N);
-#pragma unroll
-                for (int n = 0; n < CV_N / 2; ++n) dst[n] = Pack<double, 2>{{row[q][2 * n], row[q][2 * n + 1]}};
-              }
-            } else {
-              const double kc = row[q][CV_KAPPA_CSF];
-              acc[CVP_SUM_CSF] += kc;
-              acc[CVP_SUM_CSF2] += mul_rounded(kc, kc);
-              acc[CVP_NEG_MIN_CSF] = diag_max(acc[CVP_NEG_MIN_CSF], -kc);
-              acc[CVP_MAX_CSF] = diag_max(acc[CVP_MAX_CSF], kc);
-              if (row[q][CV_VALID] != 0.0) {
-                const double k = row[q][CV_KAPPA];
-                ++nvalid;
-                acc[CVP_SUM_K] += k;
-                acc[CVP_SUM_K2] += mul_rounded(k, k);
-                acc[CVP_NEG_MIN_K] = diag_max(acc[CVP_NEG_MIN_K], -k);
-                acc[CVP_MAX_K] = diag_max(acc[CVP_MAX_K], k);
-              }
-            }
-            ++rank;
-          } else if (!EMIT && kind[q] == 1) {
-            ++ndeg;
-          }
-        }
-      }
-      if (!EMIT && lane == 0) cnt[(size_t)(i - g.ilo) * g.ntj + tile] = total;
-      wm = w0;
-      w0 = wp;
-      o += pitch;
+    }
+    __device__ __forceinline__ void degenerate() { ++ndeg; }
+    __device__ __forceinline__ void publish(double* __restrict__ part) {
+      acc[CVP_DEGENERATE] = (double)ndeg;
+      acc[CVP_VALID] = (double)nvalid;
+      block_publish<CVP_NS, CVP_NM>(acc, part);
+    }
+  };
+  // (the slots between CVS_MAX_CSF and CVS_ISTEP, and behind it: 0)
+  static __device__ __forceinline__ double summary(int t, double nrows, const double (&red)[CVP_N], double istep) {
+    switch (t) {
+      case CVS_ROWS: return nrows;
+      case CVS_DEGENERATE: return red[CVP_DEGENERATE];
+      case CVS_VALID: return red[CVP_VALID];
+      case CVS_SUM_K: return red[CVP_SUM_K];
+      case CVS_SUM_K2: return red[CVP_SUM_K2];
+      case CVS_MIN_K: return -red[CVP_NEG_MIN_K];
+      case CVS_MAX_K: return red[CVP_MAX_K];
+      case CVS_SUM_CSF: return red[CVP_SUM_CSF];
+      case CVS_SUM_CSF2: return red[CVP_SUM_CSF2];
+      case CVS_MIN_CSF: return -red[CVP_NEG_MIN_CSF];
+      case CVS_MAX_CSF: return red[CVP_MAX_CSF];
+      case CVS_ISTEP: return istep;
+      default: return 0.0;
     }
   }
-  if constexpr (!EMIT) {
-    acc[CVP_DEGENERATE] = (double)ndeg;
-    acc[CVP_VALID] = (double)nvalid;
-    block_publish<CVP_NS, CVP_NM>(acc, part);
-  }
-}
-
-// ------------------------------------------------------------------ counts -> exclusive offsets, block partials -> summary
-// ONE block of kCurvScanThreads threads: scan_counts (kernels/interface.h), fold_partials (kernels/reduce.h), and threads
-// 0 .. CVS_N - 1 store one slot of the summary each (the unused ones 0).  The launch boundary in front of it is what makes the
-// counts and partials of every block visible.
-__global__ __launch_bounds__(kCurvScanThreads) void k_curv_scan(int* __restrict__ cnt, long long n, const double* __restrict__ part, int nblocks,
-                                                                 double* __restrict__ summary, double istep) {
-  constexpr int NT = kCurvScanThreads;
-  __shared__ long long wsum[NT / 64 + 1];
-  __shared__ double red[NT][CVP_N];
-  const int t = threadIdx.x;
-  const double nrows = (double)scan_counts<NT>(cnt, n, wsum);
-  constexpr double NONE = -__builtin_huge_val();
-  const double init[CVP_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, NONE, NONE, NONE, NONE};
-  fold_partials<NT, CVP_NS, CVP_NM>(part, nblocks, init, red);
-  if (t >= CVS_N) return;
-  double x = 0.0;
-  switch (t) {
-    case CVS_ROWS: x = nrows; break;
-    case CVS_DEGENERATE: x = red[0][CVP_DEGENERATE]; break;
-    case CVS_VALID: x = red[0][CVP_VALID]; break;
-    case CVS_SUM_K: x = red[0][CVP_SUM_K]; break;
-    case CVS_SUM_K2: x = red[0][CVP_SUM_K2]; break;
-    case CVS_MIN_K: x = -red[0][CVP_NEG_MIN_K]; break;
-    case CVS_MAX_K: x = red[0][CVP_MAX_K]; break;
-    case CVS_SUM_CSF: x = red[0][CVP_SUM_CSF]; break;
-    case CVS_SUM_CSF2: x = red[0][CVP_SUM_CSF2]; break;
-    case CVS_MIN_CSF: x = -red[0][CVP_NEG_MIN_CSF]; break;
-    case CVS_MAX_CSF: x = red[0][CVP_MAX_CSF]; break;
-    case CVS_ISTEP: x = istep; break;
-    default: break;
-  }
-  summary[t] = x;
-}
+};
 
 }  // namespace vof

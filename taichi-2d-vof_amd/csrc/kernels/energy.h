@@ -41,7 +41,7 @@
 // one block of 256 threads) into the row kEnergyRow describes.  No atomics, no LDS beyond the reduction.
 //
 // The march: a wave keeps the rows i - 1, i, i + 1 of F, u and v and the rows i - 1, i of p in registers and rotates them (four array
-// passes); j -+ 1 come from the rows' edge elements, as in k_curv.  The lanes that hold a face with F[i,j] != F[i-1,j] or F[i,j] != F[i,j-1]
+// passes); j -+ 1 come from the rows' edge elements, as in k_cell_rows (kernels/cell_rows.h).  The lanes that hold a face with F[i,j] != F[i-1,j] or F[i,j] != F[i,j-1]
 // gather kappa of the face's two cells with the clamped loads of young_unit (rows the march has just streamed: L2 hits); a row of the
 // tile without such a face skips the gather wave-uniformly.  Every face gathers for itself: taking the kappa the
 // lane formed a row earlier, or the one the lane below holds, was measured and lost (profiles/energy.md).

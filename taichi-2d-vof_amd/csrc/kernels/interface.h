@@ -1,4 +1,4 @@
-// kernels/interface.h -- PLIC interface segments extracted on the device (k_iface, k_iface_scan; scan_counts): Youngs' normal, the line in the cell, an ordered compaction
+// kernels/interface.h -- PLIC interface segments extracted on the device (IfaceVerb of kernels/cell_rows.h): Youngs' normal, the line in the cell
 //
 // Part of the gfx950 kernel set of the 2-D VOF hot path (see vof2d_kernels.h for the conventions:
 // reference line citations, expression order, one wave = 64*V columns marching along i).
@@ -28,34 +28,25 @@
 //   ddx = X1 - X0    ddy = Y1 - Y0    len = sqrt(ddx * ddx + ddy * ddy)
 // No contraction (-ffp-contract=off): each term is the bits of the line above.
 //
-// Order of the rows: ascending (i, j), i first.  Three launches, no atomics:
-//   k_iface<EMIT = false>  a wave marches its 64 * V columns over its chunk of rows with the rows i - 1, i, i + 1 of F in
-//                          registers (each row of F is loaded once per chunk, plus two lead-in rows) and writes the number of
-//                          segments of every (row, column tile) into cnt[(i - g.ilo) * ntj + tile]; the lengths and the
-//                          degenerate count go through the reduction of kernels/reduce.h into one partial per block
-//   k_iface_scan           one block: cnt -> exclusive offsets in place (thread t owns a run of consecutive entries; the
-//                          runs' totals are scanned through LDS), and the summary
-//   k_iface<EMIT = true>   recomputes the cells and stores segment k of a (row, tile) at row offset[(row, tile)] + k of
-//                          the output, k being the segment's rank within the wave in column order (ballot + mbcnt over
-//                          the lanes' V cells); rows from `cap` on are not stored
+// The rows, in ascending (i, j), come out of the three launches of kernels/cell_rows.h (count, scan, emit), IfaceVerb below being the verb.
 // Order of the LENGTH sum, fixed: a lane adds the lengths of its cells row by row, column by column; from there the
-// reduction of kernels/reduce.h, two sums wide: one partial of kIfacePart doubles per block, folded by k_iface_scan (one
+// reduction of kernels/reduce.h, two sums wide: one partial of kIfacePart doubles per block, folded by the scan (one
 // block of 1024 threads).  The degenerate count travels the same way as a double (exact).
 #pragma once
 #include "cells.h"
+#include "cell_rows.h"
 
 namespace vof {
 
 // slots of a row and of the summary (= VOF_IFACE_* of include/vof2d.h)
 enum : int { IF_I = 0, IF_J, IF_X0, IF_Y0, IF_X1, IF_Y1, IF_NX, IF_NY, IF_N = 8 };
 enum : int { IFS_SEGMENTS = 0, IFS_DEGENERATE, IFS_LENGTH, IFS_ISTEP, IFS_N = 4 };
-constexpr int kIfaceScanThreads = 1024;
 constexpr int kIfacePart = 2;   // doubles per block in the partials buffer: the length, the degenerate cells
 
 struct IfaceConsts { double eps, one_m_eps, cx, cy, dx, dy; };
 
 // The line of a mixed cell in the frame of a, b >= 0: the liquid is a xi + b eta < alpha; flip_x, flip_y: the mirrors that take the
-// frame back to the cell's (mxsum < 0, mysum < 0).  What k_iface cuts into a segment and k_regrid_refine (kernels/regrid.h) into
+// frame back to the cell's (mxsum < 0, mysum < 0).  What iface_cell cuts into a segment and k_regrid_refine (kernels/regrid.h) into
 // the F of a cell's children.
 struct IfaceLine { double mxsum, mysum, a, b, alpha; bool flip_x, flip_y; };
 
@@ -106,138 +97,32 @@ __device__ __forceinline__ int iface_cell(const IfaceConsts& c, const double (&f
   return 2;
 }
 
-// ------------------------------------------------------------------ the pass over F: count (+ length), or emit
-// cnt: EMIT = false, written: segments per (row, tile); EMIT = true, read: the exclusive offsets k_iface_scan left there.
-// part: kIfacePart doubles per block (slot 0: length, slot 1: degenerate cells) -- EMIT = false only.
-// rows: the output, `cap` rows of IF_N doubles -- EMIT = true only.
-template <typename T, int V, bool EMIT>
-__global__ __launch_bounds__(256) void k_iface(Geom g, const T* __restrict__ F, int R, IfaceConsts c, int* __restrict__ cnt, double* __restrict__ part,
-                                                double* __restrict__ rows, long long cap) {
-  int j0, ra, rb;
-  const bool active = cell_tile<V>(g, R, j0, ra, rb);
-  double acc[kIfacePart] = {0.0, 0.0};
-  int ndeg = 0;   // the lane's degenerate cells (an integer until the lanes are folded: one register, the same value)
-  if (active) {
-    const int ny = g.ny;
-    const int64_t pitch = g.pitch;
-    const int lane = threadIdx.x & 63;
-    const int tile = (j0 - 1) / (64 * V);   // (wave-uniform)
-    size_t o = at(g, ra, j0);
-    Row<T, V> wm, w0, wp;
-    load_row<T, V>(wm, F + o - pitch);
-    load_row<T, V>(w0, F + o);
-    for (int i = ra; i <= rb; ++i) {
-      load_row<T, V>(wp, F + o + pitch);
-      // which of the lane's cells are candidates (wave-uniform skip: most waves see no interface at all)
-      bool cand[V];
-      bool any = false;
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        const double f = (double)w0.c[q];
-        cand[q] = j0 + q <= ny && c.eps < f && f < c.one_m_eps;
-        any = any || cand[q];
-      }
-      int total = 0;
-      if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
-        const long long base = EMIT ? (long long)cnt[(size_t)(i - g.ilo) * g.ntj + tile] : 0ll;
-        int before = 0;   // segments of this row in the lanes below this one
-        int kind[V];
-        double seg[V][IF_N];
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          kind[q] = 0;
-          if (cand[q]) {
-            const double fm[3] = {(double)left_of(wm, q), (double)wm.c[q], (double)right_of(wm, q)};
-            const double f0[3] = {(double)left_of(w0, q), (double)w0.c[q], (double)right_of(w0, q)};
-            const double fp[3] = {(double)left_of(wp, q), (double)wp.c[q], (double)right_of(wp, q)};
-            kind[q] = iface_cell(c, fm, f0, fp, i, j0 + q, seg[q]);
-          }
-          const unsigned long long b = __builtin_amdgcn_ballot_w64(kind[q] == 2);
-          before += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-          total += __builtin_popcountll(b);
-        }
-        int rank = before;   // of the lane's first segment within the row's tile, in column order
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          if (kind[q] == 2) {
-            if constexpr (EMIT) {
-              const long long k = base + rank;
-              if (k < cap) {
-                Pack<double, 2>* dst = reinterpret_cast<Pack<double, 2>*>(rows + (size_t)k * IF_N);
-#pragma unroll
-                for (int m = 0; m < IF_N / 2; ++m) dst[m] = Pack<double, 2>{{seg[q][2 * m], seg[q][2 * m + 1]}};
-              }
-            } else {
-              const double ddx = seg[q][IF_X1] - seg[q][IF_X0], ddy = seg[q][IF_Y1] - seg[q][IF_Y0];
-              acc[0] += __builtin_sqrt(ddx * ddx + ddy * ddy);
-            }
-            ++rank;
-          } else if (!EMIT && kind[q] == 1) {
-            ++ndeg;
-          }
-        }
-      }
-      if (!EMIT && lane == 0) cnt[(size_t)(i - g.ilo) * g.ntj + tile] = total;
-      wm = w0;
-      w0 = wp;
-      o += pitch;
+// ------------------------------------------------------------------ the verb of kernels/cell_rows.h
+// The reduced values: slot 0 the length, slot 1 the degenerate cells (as a double: exact).
+struct IfaceVerb {
+  enum : int { ROW_N = IF_N, SUM_N = IFS_N, NS = kIfacePart, NM = 0 };
+  using Consts = IfaceConsts;
+  template <typename T>
+  static __device__ __forceinline__ int cell(const IfaceConsts& c, const Geom&, const T*, const double (&fm)[3], const double (&f0)[3],
+                                             const double (&fp)[3], int i, int j, double (&s)[IF_N]) {
+    return iface_cell(c, fm, f0, fp, i, j, s);
+  }
+  struct Tally {
+    double acc[kIfacePart] = {0.0, 0.0};
+    int ndeg = 0;
+    __device__ __forceinline__ void row(const double (&s)[IF_N]) {
+      const double ddx = s[IF_X1] - s[IF_X0], ddy = s[IF_Y1] - s[IF_Y0];
+      acc[0] += __builtin_sqrt(ddx * ddx + ddy * ddy);
     }
+    __device__ __forceinline__ void degenerate() { ++ndeg; }
+    __device__ __forceinline__ void publish(double* __restrict__ part) {
+      acc[1] = (double)ndeg;
+      block_publish<kIfacePart, 0>(acc, part);
+    }
+  };
+  static __device__ __forceinline__ double summary(int t, double segments, const double (&red)[kIfacePart], double istep) {
+    return t == IFS_SEGMENTS ? segments : t == IFS_DEGENERATE ? red[1] : t == IFS_LENGTH ? red[0] : istep;
   }
-  if constexpr (!EMIT) {
-    acc[1] = (double)ndeg;
-    block_publish<kIfacePart, 0>(acc, part);
-  }
-}
-
-// ------------------------------------------------------------------ counts -> exclusive offsets, block partials -> summary
-// Every thread of a ONE-block kernel of NT threads calls it (k_iface_scan, k_curv_scan of kernels/curvature.h).  Thread t owns the entries
-// [t * run, (t + 1) * run) of cnt (run = ceil(n / threads)): it adds them up, the block scans the threads' totals (waves by __shfl_up,
-// the NT / 64 wave totals by thread 0 through LDS), and the thread writes its entries' exclusive offsets back.  Returns the total of all
-// entries to every thread.  wsum: NT / 64 + 1 words of LDS.
-template <int NT>
-__device__ __forceinline__ long long scan_counts(int* __restrict__ cnt, long long n, long long* wsum) {
-  constexpr int NW = NT / 64;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const long long run = (n + NT - 1) / NT;
-  const long long e0 = (long long)t * run, e1 = e0 + run < n ? e0 + run : n;
-  long long mine = 0;
-  for (long long e = e0; e < e1; ++e) mine += cnt[e];
-  long long incl = mine;   // inclusive scan over the wave's lanes
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const long long up = __shfl_up(incl, s, 64);
-    if (lane >= s) incl += up;
-  }
-  if (lane == 63) wsum[wave + 1] = incl;
-  __syncthreads();
-  if (t == 0) {
-    wsum[0] = 0;
-    for (int w = 1; w <= NW; ++w) wsum[w] += wsum[w - 1];
-  }
-  __syncthreads();
-  long long off = wsum[wave] + incl - mine;
-  for (long long e = e0; e < e1; ++e) {
-    const int k = cnt[e];
-    cnt[e] = (int)off;
-    off += k;
-  }
-  return wsum[NW];
-}
-
-// ONE block of kIfaceScanThreads threads: scan_counts, then the partials (fold_partials of kernels/reduce.h), and threads
-// 0 .. IFS_N - 1 store one slot of the summary each.  The launch boundary in front of it is what makes the counts and partials of
-// every block visible.
-__global__ __launch_bounds__(kIfaceScanThreads) void k_iface_scan(int* __restrict__ cnt, long long n, const double* __restrict__ part, int nblocks,
-                                                                   double* __restrict__ summary, double istep) {
-  constexpr int NT = kIfaceScanThreads;
-  __shared__ long long wsum[NT / 64 + 1];
-  __shared__ double red[NT][kIfacePart];
-  const int t = threadIdx.x;
-  const double segments = (double)scan_counts<NT>(cnt, n, wsum);
-  const double zero[kIfacePart] = {0.0, 0.0};
-  fold_partials<NT, kIfacePart, 0>(part, nblocks, zero, red);
-  if (t >= IFS_N) return;
-  summary[t] = t == IFS_SEGMENTS ? segments : t == IFS_DEGENERATE ? red[0][1] : t == IFS_LENGTH ? red[0][0] : istep;
-}
+};
 
 }  // namespace vof

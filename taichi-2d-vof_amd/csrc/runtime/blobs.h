@@ -1,8 +1,8 @@
-// runtime/blobs.h -- vof_blobs: the handle's buffers, the launches of the k_blob_* kernels and of k_iface_scan, the copies out
+// runtime/blobs.h -- vof_blobs: the handle's buffers, the launches of the k_blob_* kernels and of the scan of kernels/cell_rows.h, the copies out
 //
 // Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
-#include "interface.h"
+#include "cell_rows.h"
 
 namespace {
 
@@ -22,9 +22,9 @@ int blobs_prepare(vof2d_ctx* h) {
 }
 constexpr const char* kBlobNoMem = "vof_blobs: no memory for its work buffers";   // (the buffers grown on demand)
 
-// k_iface_scan on n counts: exclusive offsets in place, the total into blob_sum[4]
+// the scan of kernels/cell_rows.h (vof_interface's, without partials) on n counts: exclusive offsets in place, the total into blob_sum[4]
 inline void blob_scan(vof2d_ctx* h, int* cnt, int64_t n) {
-  launch_block(h, kOther, k_iface_scan, dim3(1), (unsigned)kIfaceScanThreads, 0, cnt, (long long)n, (const double*)h->blob_sum, 0, h->blob_sum + 4, 0.0);
+  launch_block(h, kOther, k_cell_rows_scan<IfaceVerb>, dim3(1), (unsigned)kScanThreads, 0, cnt, (long long)n, (const double*)h->blob_sum, 0, h->blob_sum + 4, 0.0);
 }
 
 template <typename T>
@@ -32,7 +32,7 @@ void blob_label_launch(vof2d_ctx* h, int phase, double thr) {
   constexpr int V = VecWidth<T>::V;
   const Reported rep = reported(h);
   const Geom& g = rep.g;
-  const int R = iface_chunk(h);
+  const int R = cell_rows_chunk(h);
   const dim3 nb(rep.blocks(R));
   int* const lab = h->buf.blob_work.as<int>();
   launch(h, kOther, k_blob_init<T, V>, nb, 0, g, (const T*)F_<T>(h, fF), R, phase, thr, lab);
@@ -45,7 +45,7 @@ void blob_number_launch(vof2d_ctx* h, int64_t nblobs) {
   constexpr int V = VecWidth<T>::V;
   const Reported rep = reported(h);
   const Geom& g = rep.g;
-  const int R = iface_chunk(h);
+  const int R = cell_rows_chunk(h);
   const dim3 nb(rep.blocks(R));
   int* const lab = h->buf.blob_work.as<int>();
   int* const rec = h->buf.blob_rec.as<int>();

@@ -47,10 +47,11 @@ struct DevBuf {
   }
 };
 
+struct CellRowBufs { DevBuf work, rows; };   // a verb that emits a row per interface cell (runtime/cell_rows.h): the row counts, turned into offsets in place, the partials, the summary (CellRowsCarve); the rows, grown on demand
 struct RowBufs { DevBuf part, rows; };   // a verb that reduces the reported cells to rows (runtime/diag_reduce.h): one partial per block of its pass; the rows recorded on the device
 
 // Every work buffer of a handle: allocated by the first call that needs it (the first two: vof_create), kept until
-// vof_destroy.  Nothing but DevBufs (a RowBufs is two), so that they are released as one flat range: one added here is released too.
+// vof_destroy.  Nothing but DevBufs (a RowBufs or a CellRowBufs is two), so that they are released as one flat range: one added here is released too.
 struct WorkBufs {
   DevBuf courant;      // device counters: [0] courant, [1] max|p_new - p| bits, [2] max|p_new| bits (residual solve), [3] exact-zero cells of F
   DevBuf tbmask;       // work plan of k_jacobi_tb (TbPlan): 2 x TB_BANDS mask words, then the plan (1 + waves entries)
@@ -59,10 +60,8 @@ struct WorkBufs {
   DevBuf mg_arena;     // vof_solve_p_mg (MgCarve): the levels below the grid, the work arrays and scalars of the coarsest-level solve
   DevBuf mg_rec;       // vof_step_mg: the residual record (kernels/mg.h, MGR_*)
   RowBufs diag;        // vof_diagnostics / vof_step_diag (runtime/diag_reduce.h): the partials of k_diag, rows of VOF_DIAG_N doubles
-  DevBuf iface_work;   // vof_interface (runtime/interface.h, IfaceCarve): the segment counts, turned into offsets in place; the partials; the summary
-  DevBuf iface_rows;   // ... the segments, VOF_IFACE_N doubles each, grown on demand
-  DevBuf curv_work;    // vof_curvature (runtime/curvature.h, CurvCarve): the row counts, turned into offsets in place; the partials; the summary
-  DevBuf curv_rows;    // ... the rows, VOF_CURV_N doubles each, grown on demand
+  CellRowBufs iface;   // vof_interface (runtime/cell_rows.h): segments of VOF_IFACE_N doubles
+  CellRowBufs curv;    // vof_curvature (runtime/cell_rows.h): rows of VOF_CURV_N doubles
   RowBufs energy;      // vof_energy / vof_step_energy (runtime/energy.h): the partials of k_energy, rows of VOF_ENERGY_N doubles
   DevBuf blob_work;    // vof_blobs (runtime/blobs.h, BlobCarve): what the geometry fixes
   DevBuf blob_rec;     // ... grown on demand: the integer records of the blobs (kBlobRec ints each),
@@ -94,6 +93,6 @@ struct WorkBufs {
   DevBuf* end() { return begin() + sizeof(WorkBufs) / sizeof(DevBuf); }
   void release() { for (DevBuf* b = begin(); b != end(); ++b) b->release(); }
 };
-static_assert(sizeof(RowBufs) == 2 * sizeof(DevBuf) && sizeof(WorkBufs) % sizeof(DevBuf) == 0, "WorkBufs is walked as one array");
+static_assert(sizeof(RowBufs) == 2 * sizeof(DevBuf) && sizeof(CellRowBufs) == 2 * sizeof(DevBuf) && sizeof(WorkBufs) % sizeof(DevBuf) == 0, "WorkBufs is walked as one array");
 
 }  // namespace

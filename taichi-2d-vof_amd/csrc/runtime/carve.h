@@ -46,17 +46,9 @@ inline MgCarve carve_mg(const std::vector<size_t>& level_bytes, size_t scalars) 
   return c;
 }
 
-// vof_interface: the count of every (row, column tile) and one spare int; the block partials and the summary
-struct IfaceCarve { size_t cnt, part, total; };
-inline IfaceCarve carve_iface(size_t entries, size_t doubles) {
-  Carve a;
-  const size_t cnt = a.ints(entries + 1), part = a.doubles(doubles);
-  return {cnt, part, a.total};
-}
-
-// vof_curvature: the count of every (row, column tile) and one spare int; the block partials; the summary
-struct CurvCarve { size_t cnt, part, sum, total; };
-inline CurvCarve carve_curv(size_t entries, size_t part_doubles, size_t summary_doubles) {
+// vof_interface, vof_curvature (runtime/cell_rows.h): the count of every (row, column tile) and one spare int; the block partials; the summary
+struct CellRowsCarve { size_t cnt, part, sum, total; };
+inline CellRowsCarve carve_cell_rows(size_t entries, size_t part_doubles, size_t summary_doubles) {
   Carve a;
   const size_t cnt = a.ints(entries + 1), part = a.doubles(part_doubles), sum = a.doubles(summary_doubles);
   return {cnt, part, sum, a.total};

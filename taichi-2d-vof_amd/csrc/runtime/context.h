@@ -192,7 +192,6 @@ struct vof2d_ctx {
   int mg_levels = -1;           // knob "mg_levels": cap on the depth of a cycle (-1: none)
   int mg_graph = 1;             // knob "mg_graph": 0 launches every kernel of a cycle itself instead of replaying the captured cycle
   int mg_coarse_block = 0;      // knob "mg_coarse_block": the coarsest-level solve as one launch of one workgroup (k_mg_coarse_block) where the level is small enough
-  double* iface_part = nullptr;   // vof_interface (runtime/interface.h): the block partials, then the summary, behind the counts in buf.iface_work
   // vof_blobs (runtime/blobs.h): the blob index of every root, the root counts, the 8 doubles behind the labels in buf.blob_work
   int* blob_idx = nullptr;
   int* blob_cnt = nullptr;

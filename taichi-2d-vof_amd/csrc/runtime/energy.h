@@ -2,7 +2,7 @@
 //
 // Part of the host-side runtime of libvof2d_hip.so (the include order: vof2d_api.hip).  Everything here has internal linkage.
 #pragma once
-#include "curvature.h"
+#include "cell_rows.h"
 
 namespace {
 

@@ -20,8 +20,7 @@
 //   runtime/multigrid.h  the work arrays of the CG and multigrid solves, the hierarchy, one V-cycle and its graph, the driver loop of both
 //   runtime/step.h       which form of the batch graphs a handle runs; a step in a batch, from its graph, eagerly; the steps of vof_step_mg
 //   runtime/diag_reduce.h  the buffers and launches of vof_diagnostics, the loop of vof_step_diag
-//   runtime/interface.h  the buffers, launches and copies of vof_interface
-//   runtime/curvature.h  the buffers, launches and copies of vof_curvature
+//   runtime/cell_rows.h  the buffers, launches and copies of vof_interface and vof_curvature
 //   runtime/energy.h     the launch of k_energy on the reduced-row path of vof_diagnostics, the loop of vof_step_energy
 //   runtime/blobs.h      the buffers, launches and copies of vof_blobs
 //   runtime/tracers.h    the buffers, launches and copies of vof_tracers_*, the loop of vof_step_tracers
@@ -41,8 +40,7 @@
 #include "runtime/multigrid.h"
 #include "runtime/step.h"
 #include "runtime/diag_reduce.h"
-#include "runtime/interface.h"
-#include "runtime/curvature.h"
+#include "runtime/cell_rows.h"
 #include "runtime/energy.h"
 #include "runtime/blobs.h"
 #include "runtime/tracers.h"
@@ -480,23 +478,26 @@ int vof_step_diag(vof2d_handle h, int64_t nsteps, int64_t every, int32_t mg_cycl
   return step_diag_n(h, nsteps, every, mg_cycles, criterion, out, rows_written);
 }
 
-// ---- the interface as PLIC segments (kernels/interface.h, runtime/interface.h)
-int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary) {
+// ---- a row per interface cell (kernels/cell_rows.h, runtime/cell_rows.h)
+namespace {
+// what both verbs refuse, in this order; too_many_cells names the verb
+int check_cell_rows_args(vof2d_ctx* h, double eps, const double* rows, int64_t cap_rows, const double* summary, const char* too_many_cells) {
   if (!h || !summary) return VOF_EINVAL;
   if (!(eps >= 0.0 && eps < 0.5)) return fail(h, VOF_EINVAL, "eps must lie in [0, 0.5)");
   if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
-  if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_interface keeps 32-bit offsets: at most 2^31 - 1 cells");
-  return iface_run(h, eps, rows, cap_rows, summary);
+  return (int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX ? fail(h, VOF_EINVAL, too_many_cells) : VOF_OK;
 }
-
-// ---- height-function curvature beside the solver's own (kernels/curvature.h, runtime/curvature.h)
+}  // namespace
+// the interface as PLIC segments (kernels/interface.h)
+int vof_interface(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary) {
+  if (const int rc = check_cell_rows_args(h, eps, rows, cap_rows, summary, "vof_interface keeps 32-bit offsets: at most 2^31 - 1 cells")) return rc;
+  return cell_rows_run(h, kIfaceRows, eps, rows, cap_rows, summary);
+}
+// height-function curvature beside the solver's own (kernels/curvature.h)
 int vof_curvature(vof2d_handle h, double eps, double* rows, int64_t cap_rows, double* summary) {
-  if (!h || !summary) return VOF_EINVAL;
-  if (!(eps >= 0.0 && eps < 0.5)) return fail(h, VOF_EINVAL, "eps must lie in [0, 0.5)");
-  if (cap_rows < 0 || (!rows && cap_rows > 0)) return fail(h, VOF_EINVAL, "rows is NULL with cap_rows > 0, or cap_rows < 0");
-  if ((int64_t)h->d.nx * h->d.ny > (int64_t)INT32_MAX) return fail(h, VOF_EINVAL, "vof_curvature keeps 32-bit offsets: at most 2^31 - 1 cells");
+  if (const int rc = check_cell_rows_args(h, eps, rows, cap_rows, summary, "vof_curvature keeps 32-bit offsets: at most 2^31 - 1 cells")) return rc;
   if (const int rc = check_verb_allowed(h, "vof_curvature needs the whole domain in one handle (curvature over row strips is not built)")) return rc;
-  return curv_run(h, eps, rows, cap_rows, summary);
+  return cell_rows_run(h, kCurvRows, eps, rows, cap_rows, summary);
 }
 
 // ---- the energy budget of the flow (kernels/energy.h, runtime/energy.h)

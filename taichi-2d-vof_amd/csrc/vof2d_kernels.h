@@ -24,8 +24,9 @@
 //   cg.h         k_cg_apply, k_cg_update, k_cg_residual   (extension: conjugate gradients on the pressure equation)
 //   mg.h         k_mg_smooth, k_mg_restrict, k_mg_prolong, k_mg_coarse_block, k_mg_step_record  (extension: geometric multigrid on the same equation)
 //   diag.h       k_diag   (extension: volume, centroid, kinetic energy, divergence, extrema in one fixed-order pass)
-//   interface.h  k_iface, k_iface_scan   (extension: the interface as PLIC segments, counted, scanned and emitted in (i, j) order)
-//   curvature.h  k_curv, k_curv_scan   (extension: height-function curvature of every mixed cell beside the solver's own CSF curvature, counted, scanned and emitted like the segments)
+//   cell_rows.h  k_cell_rows, k_cell_rows_scan; scan_counts   (what the two families below share: a row per interface cell, counted, scanned and emitted in (i, j) order)
+//   interface.h  IfaceVerb   (extension: the interface as PLIC segments)
+//   curvature.h  CurvVerb   (extension: height-function curvature of every mixed cell beside the solver's own CSF curvature)
 //   energy.h     k_energy   (extension: the energy budget -- face kinetic energy, density moments, the interface measure and the power of every term of the momentum predictor, evaluated face by face in double with kappa gathered at the interface, in one fixed-order pass over F, u, v, p)
 //   blobs.h      k_blob_init, k_blob_merge, k_blob_flatten, k_blob_number, k_blob_label, k_blob_stats, k_blob_summary, k_blob_plan, k_blob_sums, k_blob_rows   (extension: droplets and bubbles labelled by union-find, numbered by first cell, measured in a fixed order)
 //   tracers.h    k_tracer_advance, k_tracer_sample, k_tracer_finish   (extension: passive particles, one per lane: bilinear gather on the staggered grid, midpoint rule, walls)
@@ -51,6 +52,7 @@
 #include "kernels/cg.h"
 #include "kernels/mg.h"
 #include "kernels/diag.h"
+#include "kernels/cell_rows.h"
 #include "kernels/interface.h"
 #include "kernels/curvature.h"
 #include "kernels/energy.h"

@@ -11,7 +11,7 @@ import numpy as np
 from _interface_np import chunk_rows
 from _reduce_np import fixed_order
 
-SCAN_THREADS = 1024   # kCurvScanThreads
+SCAN_THREADS = 1024   # kScanThreads of kernels/cell_rows.h
 I, J, KAPPA, VALID, AXIS, KAPPA_CSF, HP, FVAL = range(8)
 SUMMARY = ("ROWS", "DEGENERATE", "VALID", "SUM_K", "SUM_K2", "MIN_K", "MAX_K", "SUM_CSF", "SUM_CSF2", "MIN_CSF", "MAX_CSF")
 

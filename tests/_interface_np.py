@@ -11,11 +11,11 @@ import numpy as np
 
 from _reduce_np import TILE, fixed_order
 
-SCAN_THREADS = 1024   # kIfaceScanThreads
+SCAN_THREADS = 1024   # kScanThreads of kernels/cell_rows.h
 
 
 def chunk_rows(nx, ny, row_lo=0, row_hi=None, rmin=4, rmax=32):
-    """iface_chunk of runtime/interface.h: the cells-per-wave rule on the rows the handle can compute."""
+    """cell_rows_chunk of runtime/cell_rows.h: the cells-per-wave rule on the rows the handle can compute."""
     row_hi = nx + 1 if row_hi is None else row_hi
     rows = min(nx, row_hi - 1) - max(1, row_lo + 1) + 1
     ntj = (ny + TILE - 1) // TILE
@@ -33,7 +33,7 @@ def diag_chunk_rows(nx, ny, row_lo=0, row_hi=None):
 
 def length_sum(L, R):
     """The LENGTH of the kernels from the per-cell lengths L (rows lo .. hi, columns 1 .. ny; 0 where there is no segment):
-    the order of kernels/reduce.h with the 1024 threads of k_iface_scan."""
+    the order of kernels/reduce.h with the 1024 threads of k_cell_rows_scan."""
     return fixed_order(L, R, SCAN_THREADS, "add")
 
 

@@ -10,9 +10,9 @@ Grids sit on and beside the boundaries of the extension kernels (csrc/vof2d_devi
   ny   64 V = 128 columns a wave (cell_tile, V = 2 for both dtypes), four waves a block (k_stats and every pass of reduced_rows):
        128 k + {-1, 0, 1}, k = 1 .. 4; the 112-column stride of k_dye (TransportGeom): 112, 113; the 256-column blocks of k_scene over
        j = 0 .. ny + 1: ny + 2 = 255, 256, 257; fewer than 64 columns: one wave with idle lanes
-  nx   the chunk lengths the cells-per-wave rule gives small grids -- 2 (diag_chunk, depths, frames, stats), 4 (iface_chunk) -- and the
+  nx   the chunk lengths the cells-per-wave rule gives small grids -- 2 (diag_chunk, depths, frames, stats), 4 (cell_rows_chunk) -- and the
        32 rows of kBlobRows, on and beside them, odd and even; 3, the smallest vof_create takes; 1025 x 6 and 2051 x 3: more (row, tile)
-       entries than k_iface_scan has threads (1024), and 257 blocks of partials for the 256 folding threads of k_row_finish
+       entries than k_cell_rows_scan has threads (1024), and 257 blocks of partials for the 256 folding threads of k_row_finish
 
 Field kinds: "flow" (an -ic state after a few steps), "lattice" (multiples of 1/4 or 1/8 in blocks of cells, so that neighbours are
 equal: a == b, axis-aligned normals, F == 0.5), "edges" (every value drawn from the verbs' thresholds and their floating-point
@@ -532,7 +532,7 @@ def grid_classes(c, g):
     c["grid: the smallest nx"] += int(nx == 3)
     ntj = -(-ny // TILE)                                             # column tiles; a pass has one wave per (chunk, tile), four waves a block
     blocks = -(-(-(-nx // inp.diag_chunk_rows(nx, ny)) * ntj) // 4)  # of k_diag and its kin: one partial each, folded by the 256 threads of k_row_finish
-    c["grid: more entries than scan threads"] += int(nx * ntj > inp.SCAN_THREADS)      # (row, tile) entries of k_iface_scan
+    c["grid: more entries than scan threads"] += int(nx * ntj > inp.SCAN_THREADS)      # (row, tile) entries of k_cell_rows_scan
     c["grid: more blocks than folding threads"] += int(blocks > 256)
     c["grid: nx odd" if nx % 2 else "grid: nx even"] += 1
     for R in (4, 32):

@@ -1,6 +1,6 @@
 // Stand-alone check (host compiler, no HIP) of the cells a handle reports (ReportedRows, runtime/rows.h) and of the arenas of
 // the verbs (runtime/carve.h) against what the runtime computed before they existed: diag_rows_of, iface_entries, blob_cells
-// and the blocks of their launches; the offsets and totals of iface_prepare, blobs_prepare, cg_prepare and mg_prepare,
+// and the blocks of their launches; the offsets and totals of iface_prepare (now cell_rows_prepare), blobs_prepare, cg_prepare and mg_prepare,
 // written out below.  Exit status 0 and "ok" on success; the first failing checks are printed otherwise.
 #include <cstdio>
 #include <vector>
@@ -69,12 +69,13 @@ static void check_handle(const Handle& h, bool whole) {
   for (int it = 0; it <= 20; it += 5)
     CHECK(strip_rows(h.row_lo, h.row_hi, h.own_lo, h.own_hi, h.nx, it).owned.first == lo && strip_rows(h.row_lo, h.row_hi, h.own_lo, h.own_hi, h.nx, it).owned.last == hi, CTX);
 
-  // ---- iface_prepare: ints, then doubles
+  // ---- cell_rows_prepare with the widths of vof_interface: ints, then doubles
   {
     const size_t ints = ((size_t)entries + 2) & ~(size_t)1, dbl = (size_t)iface_blocks * kIfacePart + IFS_N;
-    const IfaceCarve c = carve_iface((size_t)rep.entries(), (size_t)rep.blocks(iface_chunk) * kIfacePart + IFS_N);
+    const CellRowsCarve c = carve_cell_rows((size_t)rep.entries(), (size_t)rep.blocks(iface_chunk) * kIfacePart, IFS_N);
     CHECK(c.cnt == 0 && c.part == ints * sizeof(int) && c.total == ints * sizeof(int) + dbl * sizeof(double), CTX);
     CHECK(c.part % 8 == 0 && c.part >= ((size_t)entries + 1) * sizeof(int), CTX);
+    CHECK(c.sum == c.part + (size_t)iface_blocks * kIfacePart * sizeof(double), CTX);   // the summary directly behind the partials
   }
   // ---- blobs_prepare
   {

@@ -157,12 +157,12 @@ def test_the_kernel_header_stands_alone(tmp_path):
     if tkh.HIPCC is None:
         pytest.skip("hipcc is not installed")
     tkh.test_header_compiles_alone(tmp_path, "curvature.h")
-    assert {"cells.h", "interface.h"} <= set(tkh.includes("curvature.h"))      # mul_rounded and the reduction; scan_counts
+    assert {"cells.h", "cell_rows.h"} <= set(tkh.includes("curvature.h"))      # mul_rounded and the reduction; the count, scan and emit passes
 
 
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g")], ids=["plain", "asan-ubsan"])
 def test_the_arena_layout(tmp_path, flags):
-    """carve_curv of runtime/carve.h is plain C++: tests/host/curv_carve_check.cpp, compiled with the host compiler and run stand-alone."""
+    """carve_cell_rows of runtime/carve.h is plain C++: tests/host/curv_carve_check.cpp, compiled with the host compiler and run stand-alone."""
     import os
     import subprocess
     from test_rows_geometry import CSRC, ROOT, host_compiler

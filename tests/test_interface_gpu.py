@@ -87,7 +87,7 @@ def test_small_rectangular_and_three_tiles_f64(hip_api, nx, ny, ic, kw):
 
 def test_more_partials_than_scan_threads_f64(hip_api):
     """3277 x 513, the drop over the pool at step 0: five column tiles (the last one a single column) and 4-row chunks, the
-    fewest rows for which the count pass has more blocks than k_iface_scan has threads -- 820 chunks x 5 tiles = 4100 waves =
+    fewest rows for which the count pass has more blocks than k_cell_rows_scan has threads -- 820 chunks x 5 tiles = 4100 waves =
     1025 blocks, one row less gives 1024 -- so thread 0 folds two partials.  Everything with ==."""
     nx, ny = 3277, 513
     R = inp.chunk_rows(nx, ny)

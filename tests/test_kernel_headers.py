@@ -14,7 +14,7 @@ KERNELS = os.path.join(ROOT, "taichi-2d-vof_amd", "csrc", "kernels")
 HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-Wall",
          "-Wno-unused-function"]          # FLAGS of csrc/Makefile
-HEADERS = ["march.h", "row_segments.h", "reduce.h", "cells.h", "cg.h", "mg.h", "diag.h", "interface.h", "blobs.h", "tracers.h", "depths.h", "dye.h", "frames.h", "stats.h",
+HEADERS = ["march.h", "row_segments.h", "reduce.h", "cells.h", "cg.h", "mg.h", "diag.h", "cell_rows.h", "interface.h", "blobs.h", "tracers.h", "depths.h", "dye.h", "frames.h", "stats.h",
            "scene.h"]
 
 
@@ -37,9 +37,9 @@ def test_no_family_is_included_for_a_helper(header):
 
 
 def test_the_shared_helpers_come_from_cells_h():
-    for header in ("cg.h", "diag.h", "interface.h", "depths.h", "blobs.h", "frames.h", "stats.h", "scene.h"):
+    for header in ("cg.h", "diag.h", "cell_rows.h", "interface.h", "depths.h", "blobs.h", "frames.h", "stats.h", "scene.h"):
         assert "cells.h" in includes(header), header
-    for header in ("diag.h", "interface.h", "depths.h"):
+    for header in ("diag.h", "cell_rows.h", "interface.h", "depths.h"):
         assert "cg.h" not in includes(header), header
     assert includes("cells.h") == ["reduce.h"] and "tracers.h" in includes("depths.h")
 
