@@ -87,7 +87,7 @@ def refine_interior(src, rx, ry, plic, eps, dx, dy):
         lo = p[ib, jb] + wa * (p[ib + 1, jb] - p[ib, jb])
         hi = p[ib, jb + 1] + wa * (p[ib + 1, jb + 1] - p[ib, jb + 1])
         pn = lo + wb * (hi - lo)
-        Fn = F[II, JJ] + np.zeros((1, 1))
+        Fn = F[II, JJ].copy()                        # (the parent's value as it is: adding a zero would turn a -0 into +0)
         nplic = ndeg = 0
         if plic:
             kind, a, b, alpha, fx, fy = line(F, eps, dx, dy)

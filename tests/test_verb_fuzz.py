@@ -7,7 +7,9 @@ and stand in the assertion messages: this test fixes the size of the slice from 
 
 The restatements themselves are judged on the new inputs (lattice and edge fields, where ties are the rule) by the
 definition-level judges of tests/test_*.py, taken to those fields: the PLIC line that cuts off the area F, the naive statistics,
-a second labelling, the depth of a column counted cell by cell, the colour index by the header's words one pixel at a time.
+a second labelling, the depth of a column counted cell by cell, the colour index by the header's words one pixel at a time; for
+vof_regrid the range, volume and order of a cell's children, the selects at k == 0 and the pair sums against math.fsum, for vof_curvature
+every row again in Python doubles, for vof_energy the reference's predictor on lattice fields and SG one face at a time.
 """
 import collections
 import math
@@ -16,9 +18,12 @@ import numpy as np
 import pytest
 
 import _blobs_np as bnp
+import _curvature_np as cnp
 import _depths_np as dpn
+import _energy_np as enp
 import _frames_np as fnp
 import _interface_np as inp
+import _regrid_np as rnp
 import _scene_np as scn
 import _stats_np as stn
 import _tracers_np as tnp
@@ -32,10 +37,10 @@ def census(api):
     if not _CENSUS:
         c = collections.Counter()
         consts = {}
-        for leg in "ABC":
+        for leg in "ABCD":
             for seed in vf.slice_seeds(leg):
                 case = vf.DRAW[leg](seed)
-                g = case["grid"]
+                g = case["src" if leg == "D" else "grid"]
                 key = (g["nx"], g["ny"], g["dtype"], g["cast"], tuple(sorted(g["kw"].items())))
                 if key not in consts:
                     e = vf.make(api, g)
@@ -46,6 +51,8 @@ def census(api):
                     vf.census_a(c, case, vf.fields_of(api, case), k, vf.positions_of(case, k)[0])
                 elif leg == "B":
                     vf.census_b(c, case)
+                elif leg == "D":
+                    vf.census_d(c, case, vf.fields_d(api, case), k)
                 else:
                     vf.census_c(c, case, k, vf.scene_of(case, k))
         _CENSUS["c"] = c
@@ -59,8 +66,33 @@ def need(c, names, what):
     assert not missing, "%s the slice does not reach: %s; the counts: %s" % (what, missing, {n: c[n] for n in names})
 
 
+# draw_a, draw_b and draw_c of three committed seeds as they were before the second stream existed (recorded from the parent of the
+# commit that added the stream): every key of that day keeps its value; the operations the second stream inserts into leg B stand at case["inserted"]
+DRAWN_BEFORE = {
+    ("A", 20261023): {'leg': 'A', 'seed': 20261023, 'grid': {'nx': 17, 'ny': 128, 'dtype': 'f64', 'cast': 'none', 'cells': 'default', 'kw': {}}, 'kind': 'edges', 'ic': 3, 'steps': 1, 'sprinkle': 'naninf', 'eps': 0.125, 'thr': 0.30000001192092896, 'level': 0.5, 'frame': {'q': 'U', 'bx': 3, 'by': 133, 'contour': False, 'symmetric': True, 'lo': 0.25, 'hi': 0.5, 'lut': False}, 'npos': 26, 'caps': {'interface': 'short', 'blobs': 'short', 'tracers': 'generous', 'gauges': 'generous', 'depths': 'generous', 'frame': 'generous'}, 'strip': {'kind': 'middle', 'rows': (5, 14), 'own': (6, 13)}},
+    ("A", 20261077): {'leg': 'A', 'seed': 20261077, 'grid': {'nx': 31, 'ny': 511, 'dtype': 'f32', 'cast': 'none', 'cells': 'square', 'kw': {'Lx': 0.1, 'Ly': 1.6483870967741936}}, 'kind': 'edges', 'ic': 2, 'steps': 0, 'sprinkle': 'none', 'eps': 0.125, 'thr': 0.5, 'level': 0.5, 'frame': {'q': 'DYE', 'bx': 36, 'by': 3, 'contour': False, 'symmetric': False, 'lo': 0.0, 'hi': 1.0, 'lut': False}, 'npos': 36, 'caps': {'interface': 'generous', 'blobs': 'exact', 'tracers': 'exact', 'gauges': 'short', 'depths': 'exact', 'frame': 'short'}, 'strip': {'kind': 'random', 'rows': (16, 27), 'own': (19, 24)}},
+    ("A", 20261140): {'leg': 'A', 'seed': 20261140, 'grid': {'nx': 15, 'ny': 255, 'dtype': 'f32', 'cast': 'f32', 'cells': 'free', 'kw': {'Lx': 0.13, 'Ly': 0.1}}, 'kind': 'edges', 'ic': 2, 'steps': 1, 'sprinkle': 'none', 'eps': 1e-06, 'thr': 0.5, 'level': 0.25, 'frame': {'q': 'SPEED', 'bx': 3, 'by': 1, 'contour': False, 'symmetric': False, 'lo': 0.0, 'hi': 0.0, 'lut': False}, 'npos': 13, 'caps': {'interface': 'zero', 'blobs': 'zero', 'tracers': 'short', 'gauges': 'exact', 'depths': 'zero', 'frame': 'zero'}, 'strip': {'kind': 'none', 'rows': (6, 9), 'own': (8, 7)}},
+    ("B", 20261023): {'leg': 'B', 'seed': 20261023, 'grid': {'nx': 17, 'ny': 128, 'dtype': 'f64', 'cast': 'none', 'cells': 'default', 'kw': {}}, 'kind': 'lattice', 'ic': 3, 'warm': 2, 'eager': False, 'eps': 1e-06, 'thr': 0.5, 'level': 0.5, 'frame': {'q': 'U', 'bx': 1, 'by': 2, 'contour': True, 'symmetric': True, 'lo': 0.0, 'hi': 1.0, 'lut': True}, 'npos': 12, 'sprinkle': 'none', 'caps': {'interface': 'short', 'blobs': 'zero', 'tracers': 'generous', 'gauges': 'generous', 'depths': 'generous', 'frame': 'short'}, 'ops': [('refused_strip', 'gauges_get'), ('refused_strip', 'step_frames'), ('overwrite', 'F', 653185922), ('readonly', 'gauges_get'), ('refused_strip', 'step_dye'), ('knob', 'dye_fused', 0), ('step_stats', 5, 3, 1, 1, 0.25, False), ('knob', 'mg_graph', 0)]},
+    ("B", 20261077): {'leg': 'B', 'seed': 20261077, 'grid': {'nx': 17, 'ny': 511, 'dtype': 'f32', 'cast': 'none', 'cells': 'square', 'kw': {'Lx': 0.1, 'Ly': 3.0058823529411764}}, 'kind': 'lattice', 'ic': 3, 'warm': 0, 'eager': True, 'eps': 9.999999974752427e-07, 'thr': 0.75, 'level': 0.5, 'frame': {'q': 'DYE', 'bx': 4, 'by': 516, 'contour': True, 'symmetric': False, 'lo': 0.0, 'hi': 0.0, 'lut': True}, 'npos': 8, 'sprinkle': 'none', 'caps': {'interface': 'exact', 'blobs': 'exact', 'tracers': 'generous', 'gauges': 'exact', 'depths': 'short', 'frame': 'zero'}, 'ops': [('set_scene', 1041839635, 2, False), ('stats_hand', 'edges', 975457223, 2, 0.5, 'nan'), ('overwrite', 'u', 572080256), ('step_gauges', 4, 3, 2)]},
+    ("B", 20261140): {'leg': 'B', 'seed': 20261140, 'grid': {'nx': 15, 'ny': 255, 'dtype': 'f32', 'cast': 'f32', 'cells': 'free', 'kw': {'Lx': 0.13, 'Ly': 0.1}}, 'kind': 'lattice', 'ic': 1, 'warm': 2, 'eager': False, 'eps': 0.125, 'thr': 0.75, 'level': 0.5, 'frame': {'q': 'F', 'bx': 1, 'by': 1, 'contour': False, 'symmetric': False, 'lo': 0.375, 'hi': 0.375, 'lut': True}, 'npos': 14, 'sprinkle': 'none', 'caps': {'interface': 'generous', 'blobs': 'zero', 'tracers': 'zero', 'gauges': 'generous', 'depths': 'generous', 'frame': 'zero'}, 'ops': [('knob', 'dye_fused', 0), ('step_tracers', 3, 2, 0, 0), ('set_scene', 459458003, 8, True), ('step_diag', 4, 1, 0), ('stats_hand', 'edges', 199222999, 3, 0.30000001192092896, 'none'), ('refused_phase', 'stats_sample')]},
+    ("C", 20261023): {'leg': 'C', 'seed': 20261023, 'grid': {'nx': 17, 'ny': 128, 'dtype': 'f64', 'cast': 'none', 'cells': 'default', 'kw': {}}, 'ic': 3, 'S': 16, 'clear': True, 'nshapes': 10, 'base': 'rough', 'shortcuts': 1, 'strip': {'kind': 'none', 'rows': (3, 6), 'own': (5, 4)}, 'steps': 2},
+    ("C", 20261077): {'leg': 'C', 'seed': 20261077, 'grid': {'nx': 31, 'ny': 511, 'dtype': 'f32', 'cast': 'none', 'cells': 'square', 'kw': {'Lx': 0.1, 'Ly': 1.6483870967741936}}, 'ic': 1, 'S': 8, 'clear': True, 'nshapes': 1, 'base': 'rough', 'shortcuts': 0, 'strip': {'kind': 'single', 'rows': (0, 4), 'own': (1, 1)}, 'steps': 2},
+    ("C", 20261140): {'leg': 'C', 'seed': 20261140, 'grid': {'nx': 15, 'ny': 255, 'dtype': 'f32', 'cast': 'f32', 'cells': 'free', 'kw': {'Lx': 0.13, 'Ly': 0.1}}, 'ic': 2, 'S': 16, 'clear': True, 'nshapes': 1, 'base': 'edges', 'shortcuts': 0, 'strip': {'kind': 'none', 'rows': (5, 10), 'own': (8, 7)}, 'steps': 2},
+}
+
+
+def test_the_committed_seeds_draw_what_they_drew_before_the_second_stream():
+    for (leg, seed), before in DRAWN_BEFORE.items():
+        case = vf.DRAW[leg](seed)
+        if leg == "B":
+            assert all(case["ops"][n][0] in vf.OPS_B2 or case["ops"][n][1] == vf.LATER for n in case["inserted"])
+            case = dict(case, ops=[op for n, op in enumerate(case["ops"]) if n not in case["inserted"]])
+        assert {k: case[k] for k in before} == before, (leg, seed)
+    assert sum(len(vf.draw_b(seed)["inserted"]) for _, seed in DRAWN_BEFORE) > 0
+
+
 def test_the_generator_is_deterministic():
-    for leg in "ABC":
+    for leg in "ABCD":
         a, b = vf.DRAW[leg](vf.SEED0 + 3), vf.DRAW[leg](vf.SEED0 + 3)
         assert a == b and vf.describe(a) == vf.describe(b)
         assert vf.DRAW[leg](vf.SEED0 + 4) != a
@@ -75,6 +107,30 @@ def test_every_tie_of_the_interface_is_reached_on_both_sides(oracle_api):
     c = census(oracle_api)
     need(c, ["%s %s" % (t, s) for t in vf.IFACE_TIES for s in ("<", "==", ">")], "comparisons of vof_interface")
     need(c, ["segments", "degenerate"], "cells of vof_interface")
+
+
+def test_every_tie_of_curvature_energy_and_regrid_is_reached_on_all_three_sides(oracle_api):
+    c = census(oracle_api)
+    # m == 0 in a row cannot be: AXIS 0 means |mxsum| dx <= |mysum| dy, so m = mysum == 0 makes both sums 0 (or a product that underflowed from
+    # below 1e-10), which is a degenerate cell, no row; AXIS 1 means |mxsum| dx > |mysum| dy >= 0; a NaN in the 3 x 3 cells reaches both sums
+    NO_TIE = "curv: m ? 0 =="
+    need(c, [n for n in ("%s %s" % (t, s) for t in vf.CURV_TIES + vf.ENERGY_TIES + vf.REGRID_TIES for s in ("<", "==", ">")) if n != NO_TIE], "comparisons of the three verbs")
+    assert c[NO_TIE] == 0, "a row of vof_curvature with m == 0: the argument above is wrong, and the flip of m >= 0 is no longer neutral"
+    need(c, ["curv: VALID rows", "curv: rows not VALID", "curv: a stencil clamped on both sides", "curv: more entries than scan threads with rows"]
+         + ["curv capacity: " + k for k in vf.CAPS], "rows and capacities of vof_curvature")
+    need(c, ["energy: a face with equal F", "energy: a face with unequal F", "energy: a face between +0 and -0", "energy: a face with a NaN F",
+             "energy: a NaN that only a select keeps out of a sum"], "faces of vof_energy")
+    need(c, ["regrid: si == 0", "regrid: sj == 0", "regrid: rx ry == 256", "regrid: a factor of 15", "regrid: a factor of 16", "regrid: terms no power of two",
+             "regrid: along i only", "regrid: along j only", "regrid: copy", "regrid: unequal factors", "regrid: a chunk that starts inside a parent",
+             "regrid: PLIC", "regrid: without PLIC", "regrid: eps = 0", "regrid: degenerate source cells", "regrid: a source with NaN", "regrid: a source with inf",
+             "regrid: refine", "regrid: coarsen", "regrid: round trip", "regrid: steps behind it",
+             "regrid: al == n1 where the two branches round apart"]
+         + ["regrid: %s to %s" % (a, b) for a in ("f64", "f32") for b in ("f64", "f32")] + ["regrid: dst " + p for p in vf.PRE_D]
+         + ["regrid: refused, " + r for r in vf.REFUSALS_D], "factors, dtypes, states and refusals of vof_regrid")
+    need(c, ["regrid: dst ny %s %d columns" % (w, vf.TILE * k) for k in (1, 2, 3, 4) for w in ("one below", "on", "one past")]
+         + ["regrid: dst ny fewer than 64 columns", "regrid: dst ny on the 112-column stride", "regrid: dst ny one past the 112-column stride"], "dst widths of vof_regrid")
+    need(c, ["op: %s of the later verbs" % o for o in vf.REFUSED_B2] + ["regrid_in: with fuse_tm and f_zero_map"], "the new refusals and knobs of leg B")
+    assert all(c["op: " + o] >= 10 for o in vf.OPS_B2), {o: c["op: " + o] for o in vf.OPS_B2}
 
 
 def test_every_other_tie_is_reached(oracle_api):
@@ -304,3 +360,155 @@ def test_samples_on_faces_and_scene_samples_on_edges_by_scalar_arithmetic():
                 liq += state == scn.LIQUID
                 keep += state == scn.KEEP
         assert (n_liq[i, j], n_keep[i, j]) == (liq, keep), (i, j)
+
+
+# ---------------------------------------------------------------------------------------------------- vof_regrid, vof_curvature, vof_energy on ties
+REGRID_FACTORS = [(2, 2), (3, 5), (16, 16), (7, 1)]
+
+
+@pytest.mark.parametrize("nx,ny,dtype,kind,eps", JUDGED)
+def test_regrid_children_keep_the_range_the_volume_and_the_order_on_ties(nx, ny, dtype, kind, eps):
+    """The children of a cell with a line lie in [0, 1], their mean is the parent's F within 32 2^-52 (the bound of tests/test_regrid.py),
+    and going along k' and m' -- away from the liquid corner, al falling -- a child's F never increases, whichever branch a tie takes."""
+    case, f = judged_case(nx, ny, dtype, kind, eps)
+    dx, dy = 0.1 / nx, 0.1 / ny
+    kind_, a, b, alpha, fx, fy = rnp.line(f["F"], eps, dx, dy)
+    row = kind_ == 2
+    F0 = f["F"].astype(np.float64)[1:-1, 1:-1][row]
+    assert row.sum() > 20
+    no = np.zeros(int(row.sum()), dtype=bool)
+    for rx, ry in REGRID_FACTORS:
+        kids = np.array([[rnp.child_F(a[row], b[row], alpha[row], fx[row], fy[row], k, m, rx, ry) for m in range(ry)] for k in range(rx)])
+        worst = float(np.abs(kids.astype(np.longdouble).mean(axis=(0, 1)) - F0).max()) / 2.0 ** -52
+        print(nx, ny, dtype, kind, eps, (rx, ry), "cells with a line", int(row.sum()), "worst |mean - F| %.2f 2^-52" % worst, "children outside [0, 1]",
+              int(((kids < 0) | (kids > 1)).sum()))
+        assert kids.min() >= 0.0 and kids.max() <= 1.0 and worst <= 32.0
+        along = np.array([[rnp.child_F(a[row], b[row], alpha[row], no, no, k, m, rx, ry) for m in range(ry)] for k in range(rx)])      # indexed [k', m']
+        assert (along[1:] <= along[:-1]).all() and (along[:, 1:] <= along[:, :-1]).all(), (rx, ry)
+
+
+def test_regrid_selects_and_sums_by_their_definitions():
+    """u and v at k == 0 and m == 0 are the lerp with weight 0 on finite fields (==: the sign of a zero is the select's to keep); pair_sum is
+    math.fsum within n 2^-52 fsum(|t|), and exact for 2^l equal terms."""
+    case, f = judged_case(9, 12, "f64", "edges", 0.125)
+    inner, _, _ = rnp.refine_interior(f, 3, 4, False, 0.0, 0.01, 0.01)
+    u, v = f["u"].astype(np.float64), f["v"].astype(np.float64)
+    for I in range(1, 10):
+        for J in range(1, 13):
+            for m in range(4):
+                assert inner["u"][(I - 1) * 3, (J - 1) * 4 + m] == u[I, J] + (0.0 / 3.0) * (u[I + 1, J] - u[I, J])
+            for k in range(3):
+                assert inner["v"][(I - 1) * 3 + k, (J - 1) * 4] == v[I, J] + (0.0 / 4.0) * (v[I, J + 1] - v[I, J])
+    rng = np.random.default_rng(3)
+    for n in (1, 3, 35, 105, 240, 256):
+        t = rng.standard_normal(n) * 10.0 ** rng.integers(-3, 4, size=n)
+        got, exact = float(rnp.pair_sum(np.float64(x) for x in t)), math.fsum(t)
+        print("pair_sum of %d terms: |d| %.3e, bound %.3e" % (n, abs(got - exact), n * 2.0 ** -52 * math.fsum(np.abs(t))))
+        assert abs(got - exact) <= n * 2.0 ** -52 * math.fsum(np.abs(t))
+    for l in range(9):
+        for x in (0.1, float(np.float32(1e-6)), -0.0, 5e-324, 1.0 / 3.0):
+            s = rnp.pair_sum(np.float64(x) for _ in range(2 ** l))
+            assert s == x * 2.0 ** l and math.copysign(1.0, s) == math.copysign(1.0, x) and (s / 2.0 ** l) == x
+
+
+def test_curvature_by_the_headers_words_on_ties():
+    """Every row of the JUDGED fields again in Python doubles, one cell at a time, from the words of include/vof2d.h and the head of
+    kernels/curvature.h: AXIS, the liquid end, VALID, hp, hpp, KAPPA, compared with ==."""
+    seen = collections.Counter()
+    for nx, ny, dtype, kind, eps in JUDGED:
+        case, fld = judged_case(nx, ny, dtype, kind, eps)
+        dx, dy = 0.1 / nx, 0.13 / ny
+        F = [[float(x) for x in r] for r in fld["F"].astype(np.float64)]
+        f = lambda ii, jj: F[min(max(ii, 0), nx + 1)][min(max(jj, 0), ny + 1)]
+        cx, cy = -1 / (2 * dx), -1 / (2 * dy)
+        rows, summ = cnp.restate(fld["F"], eps, dx, dy)
+        assert len(rows) > 0
+        for r in rows:
+            i, j = int(r[cnp.I]), int(r[cnp.J])
+            g = lambda di, dj: f(i + di, j + dj)
+            mx1 = cx * (((g(1, 1) + g(1, 0)) - g(0, 1)) - g(0, 0)); my1 = cy * (((g(1, 1) - g(1, 0)) + g(0, 1)) - g(0, 0))
+            mx2 = cx * (((g(1, 0) + g(1, -1)) - g(0, 0)) - g(0, -1)); my2 = cy * (((g(1, 0) - g(1, -1)) + g(0, 0)) - g(0, -1))
+            mx3 = cx * (((g(0, 0) + g(0, -1)) - g(-1, 0)) - g(-1, -1)); my3 = cy * (((g(0, 0) - g(0, -1)) + g(-1, 0)) - g(-1, -1))
+            mx4 = cx * (((g(0, 1) + g(0, 0)) - g(-1, 1)) - g(-1, 0)); my4 = cy * (((g(0, 1) - g(0, 0)) + g(-1, 1)) - g(-1, 0))
+            mxsum, mysum = (((mx1 + mx2) + mx3) + mx4) / 4, (((my1 + my2) + my3) + my4) / 4
+            assert eps < g(0, 0) < 1 - eps and not (abs(mxsum) < 1e-10 and abs(mysum) < 1e-10)
+            ax, by = abs(mxsum) * dx, abs(mysum) * dy
+            axis = 1 if ax > by else 0
+            m = mxsum if axis else mysum
+            tl = -3 if m >= 0 else 3
+            cell = (lambda d, t: g(t, d)) if axis else (lambda d, t: g(d, t))
+            H, valid = {}, True
+            for d in (-1, 0, 1):
+                h = cell(d, -3)
+                for t in (-2, -1, 0, 1, 2, 3):
+                    h = h + cell(d, t)
+                H[d] = h
+                valid = valid and cell(d, tl) >= 1 - eps and cell(d, -tl) <= eps
+                seen["an end cell on 1 - eps or on eps"] += int(cell(d, tl) == 1 - eps or cell(d, -tl) == eps)
+            hs, ht = (dx, dy) if axis else (dy, dx)
+            hp = ((H[1] - H[-1]) * hs) / (2 * ht)
+            hpp = (((H[1] - 2 * H[0]) + H[-1]) * hs) / (ht * ht)
+            q = 1 + hp * hp
+            kappa = hpp / (q * math.sqrt(q))
+            want = (float(valid), float(axis), kappa if valid else 0.0, hp if valid else 0.0, g(0, 0))
+            assert (r[cnp.VALID], r[cnp.AXIS], r[cnp.KAPPA], r[cnp.HP], r[cnp.FVAL]) == want, (nx, ny, kind, i, j, r, want)
+            seen["ax == by"] += int(ax == by)
+            seen["m == 0"] += int(m == 0)
+            seen["VALID"] += int(valid)
+            seen["rows"] += 1
+    print(dict(seen))
+    # (m == 0 cannot be in a row: test_every_tie_of_curvature_energy_and_regrid_is_reached_on_all_three_sides says why)
+    assert seen["ax == by"] > 0 and seen["an end cell on 1 - eps or on eps"] > 0 and seen["VALID"] > 0 and seen["m == 0"] == 0
+
+
+@pytest.mark.parametrize("nx,ny", [(33, 17), (16, 40)])
+def test_the_energy_pieces_are_the_predictor_on_lattice_fields(nx, ny):
+    """test_the_pieces_are_the_predictor of tests/test_energy.py on a lattice field with tame velocities, where w == 0, here == 0 and equal F
+    across a face are the rule: u + dt A is the oracle's u_star with ==."""
+    import vof_oracle_np as onp
+    case, _ = judged_case(nx, ny, "f64", "lattice", 1e-6)
+    f = vf.drawn_fields(case, 12, (nx + 2, ny + 2), "lattice", tame=True)         # (a seed that draws the lattice of eighths: v = 0 is on it)
+    t = onp.new_state(nx, ny, 1, np.float64, "f32")
+    for n in ("F", "u", "v", "p"):
+        getattr(t, n)[...] = f[n]
+    r = enp.restate(t.F, t.u, t.v, t.p, enp.params_of_oracle(t.prm))
+    onp.cal_nu_rho(t); onp.get_normal_young(t); onp.advect_upwind(t)
+    dt = float(t.prm.dt)
+    us = t.u[2:nx + 1, 1:ny + 1] + dt * r.uf["A"]
+    vs = t.v[1:nx + 1, 2:ny + 1] + dt * r.vf["A"]
+    c = collections.Counter()
+    vf.census_energy(c, f)
+    print({k: v for k, v in c.items() if "==" in k or "equal" in k})
+    assert c["energy: u ? 0 =="] > 0 and c["energy: v ? 0 =="] > 0 and c["energy: here ? 0 =="] > 0 and c["energy: a face with equal F"] > 0
+    assert np.array_equal(r.kappa, t.kappa[1:-1, 1:-1]) and np.array_equal(r.rho, t.rho) and np.array_equal(r.nu, t.nu)
+    assert np.array_equal(us, t.u_star[2:nx + 1, 1:ny + 1]) and np.array_equal(vs, t.v_star[1:nx + 1, 2:ny + 1])
+
+
+def test_the_surface_tension_term_one_face_at_a_time():
+    """SG of every face in Python doubles: 0 where the raw F is equal across the face -- +0 beside -0 included, a NaN kappa beside it or
+    not --, the written expression elsewhere; a NaN compared as a NaN."""
+    case, f = judged_case(9, 63, "f64", "edges", 2.0 ** -20)
+    f = vf.sprinkle(f, "nan", 4, names=("F",))
+    F = f["F"].astype(np.float64)
+    F[3, 5:9] = [0.0, -0.0, 0.0, -0.0]
+    F[5:8, 20] = [-0.0, 0.0, -0.0]
+    nx, ny = 9, 63
+    prm = dict(dx=0.1 / nx, dy=0.1 / ny, dxi=nx / 0.1, dyi=ny / 0.1, dxi2=(nx / 0.1) ** 2, dyi2=(ny / 0.1) ** 2, rho_l=1000.0, rho_g=1.0, nu_l=1e-6, nu_g=1.5e-5, sigma=0.07,
+               gx=0.0, gy=-9.8)
+    r = enp.restate(F, f["u"], f["v"], f["p"], prm)
+    kappa = np.zeros_like(F); kappa[1:-1, 1:-1] = r.kappa
+    seen = collections.Counter()
+    for faces, (di, dj), h, lo_i, lo_j in ((r.uf, (1, 0), prm["dx"], 2, 1), (r.vf, (0, 1), prm["dy"], 1, 2)):
+        for i in range(lo_i, nx + 1):
+            for j in range(lo_j, ny + 1):
+                f0, fb = float(F[i, j]), float(F[i - di, j - dj])
+                k0, kb, r0, rb = float(kappa[i, j]), float(kappa[i - di, j - dj]), float(r.rho[i, j]), float(r.rho[i - di, j - dj])
+                want = 0.0 if f0 == fb else (((((-prm["sigma"]) * (f0 - fb)) * ((k0 + kb) / 2.0)) / h) * 2) / (r0 + rb)
+                got = float(faces["SG"][i - lo_i, j - lo_j])
+                assert got == want or (got != got and want != want), (i, j, got, want)
+                seen["equal F"] += int(f0 == fb)
+                seen["+0 beside -0"] += int(f0 == 0.0 and fb == 0.0 and math.copysign(1.0, f0) != math.copysign(1.0, fb))
+                seen["equal F beside a NaN kappa"] += int(f0 == fb and (k0 != k0 or kb != kb))
+                seen["a NaN F"] += int(f0 != f0 or fb != fb)
+    print(dict(seen))
+    assert all(seen[k] > 0 for k in ("equal F", "+0 beside -0", "equal F beside a NaN kappa", "a NaN F")), dict(seen)

@@ -3,18 +3,27 @@ frame specs, capacities, strips and call sequences nobody chose, drawn from a se
 lists what is not drawn, and why).  tests/test_verb_fuzz.py judges the generators and the restatements on the CPU.
 
   leg A   the verbs that only read -- vof_diagnostics (with the reduction order), vof_interface, vof_blobs (both phases), vof_depths,
-          vof_frame, vof_dye_stats, vof_gauges_get, vof_tracers_get -- on uploaded fields, each held to its restatement by the helper
+          vof_frame, vof_dye_stats, vof_gauges_get, vof_tracers_get, vof_curvature (with the cells of vof_interface and, on f64, the
+          solver's own kappa beside it), vof_energy -- on uploaded fields, each held to its restatement by the helper
           of its own test module, then with a drawn capacity (the tail of the buffer untouched), every call twice (the same bytes),
-          on the single domain and on a drawn strip where the verb takes one
+          on the single domain and on a drawn strip where the verb takes one; where it takes none (vof_curvature, vof_energy,
+          vof_step_energy, vof_regrid with the strip as src and as dst) the strip must refuse it with VOF_ESTATE
   leg B   the verbs that keep state, in a drawn sequence on ONE handle beside a twin that runs only vof_step / vof_step_mg (and the
           writes that change the state): every vof_step_* is held to its definition -- the loop on the twin with the restatement
           applied to the twin's fields at each record --, F, u, v, p and istep are compared byte for byte after every operation, a
-          refused call leaves everything as it was
+          refused call leaves everything as it was.  vof_step_energy is held like vof_step_diag; regrid_out carries the handle's state
+          onto another grid (the restatement of the twin's fields) and must leave the handle equal to its twin; regrid_in gives handle and
+          twin the state of one drawn flow source on a divisor or multiple grid, in front of cached graphs, kept zero maps (fuse_tm and
+          f_zero_map on both, fzmap_wrong stays 0), the dye, the statistics planes, tracers and gauges, which all go on being held
   leg C   vof_set_scene against _scene_np.paint byte for byte, ghost cells included, whole domain and strip, then two steps against
           the same state uploaded
+  leg D   vof_regrid between a drawn pair of grids, dtypes and kinds of source, into a dst that is fresh, stepped or full of NaN: F, F2,
+          u, v, p with their ghost rings and the summary against _regrid_np.restate, twice; src untouched; with power-of-two factors and
+          no PLIC the way back gives the bits of u, v, F (the header's claim, no restatement in it); behind a flow source two steps
+          beside a twin fed by vof_set_field; one drawn call the header refuses, both handles as they were
 
 A fixed-seed slice runs as pytest tests; the same generators run as a campaign outside pytest (what it found: profiles/verb_fuzz.md):
-    python tests/test_verb_fuzz_gpu.py --leg A|B|C --seed S --cases N [--seconds T] [--log FILE] [--lib PATH] [--slice]
+    python tests/test_verb_fuzz_gpu.py --leg A|B|C|D --seed S --cases N [--seconds T] [--log FILE] [--lib PATH] [--slice]
         stops at the first divergence; --slice: the committed slice instead of N cases from S; --lib: another build of the library
 """
 import collections
@@ -37,14 +46,18 @@ if __name__ == "__main__":   # (campaign mode: the paths conftest.py sets up for
 import ctypes as C
 
 import _dye_np as ynp
+import _energy_np as enp
 import _frames_np as fnp
 import _interface_np as inp
+import _regrid_np as rnp
 import _scene_np as scn
 import _tracers_np as tnp
 import _verb_fuzz as vf
 import test_blobs_gpu as blobs_gpu
+import test_curvature_gpu as curv_gpu
 import test_depths_gpu as depths_gpu
 import test_diag_gpu as diag_gpu
+import test_energy_gpu as energy_gpu
 import test_frames_gpu as frames_gpu
 import test_gauges_gpu as gauges_gpu
 import test_interface_gpu as iface_gpu
@@ -52,7 +65,7 @@ import test_scene_gpu as scene_gpu
 import test_stats_gpu as stats_gpu
 import test_tracers_gpu as tracers_gpu
 from util import STATE
-from vof2d import _abi, frames
+from vof2d import _abi, curvature, frames
 from vof2d.engine import VofError
 
 DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int32)
@@ -208,8 +221,43 @@ def v_tracers(api, e, case, xy, ctx, seed, refused=()):
     return rows_with_capacity(lambda p, cap, s: api.tracers_get(e.handle, p, cap, s), rows, case["caps"]["tracers"], seed, _abi.VOF_TRACER_N, _abi.VOF_TRACER_SUM_COUNT, ctx)
 
 
+def same_or_both_nan(x, y):
+    return x == y or (x != x and y != y)
+
+
+def v_curvature(api, e, case, xy, ctx, seed):
+    """vof_curvature held to its restatement at the drawn eps (every entry that is no NaN bit for bit), its cells and order to those
+    of vof_interface, then the raw call with a drawn capacity; on an f64 handle with a finite F (leg A: no step follows) KAPPA_CSF
+    against the solver's own kappa behind vof_get_normal_young, a yardstick the restatement has no part in."""
+    eps = case["eps"]
+    nonfinite = not np.isfinite(e.get("F")).all()
+    rows, summ = curv_gpu.hold_to_restatement(e, ctx, eps=eps, nan=nonfinite)
+    assert tnp.same_bits(rows, curv_gpu.restated(e, eps)[0]), ctx + ": the rows that hold no NaN, bit for bit"
+    seg, _ = e.interface(eps)
+    assert np.array_equal(rows[:, :2], seg[:, :2]), ctx + ": the cells and the order of vof_interface"
+    n = int(summ["ROWS"])
+    cap, _ = vf.cap_of(case["cap_curv"], n, seed)
+    buf = np.full((cap + 2, _abi.VOF_CURV_N), UNTOUCHED)
+    s = (C.c_double * _abi.VOF_CURV_SUM_N)()
+    assert api.curvature(e.handle, eps, buf.ctypes.data_as(DP) if cap else None, cap, s) == 0, ctx
+    m = min(cap, n)
+    assert tnp.same_bits(buf[:m], rows[:m]) and np.all(buf[m:] == UNTOUCHED), "%s: curvature with room for %d of %d rows" % (ctx, cap, n)
+    got = curvature.summary_of(list(s))
+    assert set(got) == set(summ) and all(same_or_both_nan(got[k], summ[k]) for k in summ), "%s: the summary with room for %d rows: %r against %r" % (ctx, cap, got, summ)
+    if case["leg"] == "A" and e.np_dtype == np.float64 and not nonfinite and e.row_lo == 0 and e.row_hi == e.nx + 1:
+        e.get_normal_young()
+        own = e.get("kappa")[rows[:, 0].astype(int), rows[:, 1].astype(int)]
+        bad = np.flatnonzero(curv_gpu.bits(own) != curv_gpu.bits(rows[:, curvature.KAPPA_CSF]))
+        assert len(bad) == 0, "%s: KAPPA_CSF differs from kappa in %d rows, first %r: %r vs %r" % (ctx, len(bad), rows[bad[0], :2], rows[bad[0], curvature.KAPPA_CSF], own[bad[0]])
+    return buf.tobytes() + bytes(s)
+
+
+def v_energy(api, e, case, xy, ctx, seed):
+    return energy_gpu.vec(energy_gpu.hold_to_restatement(e, ctx, bits=True)).tobytes()
+
+
 VERBS = {"diagnostics": v_diagnostics, "interface": v_interface, "blobs": v_blobs, "depths": v_depths, "frame": v_frame, "dye_stats": v_dye_stats,
-         "gauges": v_gauges, "tracers": v_tracers}
+         "gauges": v_gauges, "tracers": v_tracers, "curvature": v_curvature, "energy": v_energy}
 
 
 def read_only(api, e, case, verbs, xy, ctx, refused=()):
@@ -238,15 +286,23 @@ def run_a(api, case, c=None):
         read_only(api, e, case, vf.verbs_of(case), xy, ctx, refused)
         if c is not None:
             vf.census_a(c, case, read_back(e, True), k, e.tracers()[0][:, :2])
+        if "energy" in vf.verbs_of(case):    # two NaNs that only a select of vof_energy keeps out of P_ADV and P_SIGMA
+            upload(e, vf.energy_planted(case, f))
+            raw = energy_gpu.hold_to_restatement(e, ctx + " energy with planted NaNs", bits=True)
+            assert np.isfinite([raw["P_ADV"], raw["P_SIGMA"], raw["MAX_ACC_SIGMA"]]).all() and raw["P_VISC"] != raw["P_VISC"], "%s: %r" % (ctx, raw)
         st = case["strip"]
         s = vf.make(api, g, rows=st["rows"], own=st["own"])
         try:
             upload(s, f)
             read_only(api, s, case, [v for v in vf.verbs_of(case) if v in vf.STRIP_VERBS], xy, "%s strip %r owning %r" % (ctx, st["rows"], st["own"]))
+            kept = state_bytes(e), state_bytes(s)
             for v, call in (("tracers_set", lambda: s.tracers_set(xy)), ("gauges_set", lambda: s.gauges_set(xy)), ("frame", lambda: s.frame("F")),
-                            ("stats_begin", lambda: s.stats_begin(3, 0.5))):
+                            ("stats_begin", lambda: s.stats_begin(3, 0.5)), ("curvature", lambda: s.curvature(case["eps"])), ("energy", s.energy),
+                            ("step_energy", lambda: s.step_energy(2, 1)), ("regrid from the strip", lambda: e.regrid_from(s, eps=case["eps"])),
+                            ("regrid into the strip", lambda: s.regrid_from(e, eps=case["eps"]))):
                 if tuple(st["rows"]) != (0, g["nx"] + 1):       # (a handle that stores every row is a whole domain, whatever it owns)
                     refused_with(call, "VOF_ESTATE", ctx + ": %s on a strip" % v)
+            assert (state_bytes(e), state_bytes(s)) == kept, ctx + ": a call refused on the strip changed a handle"
         finally:
             s.close()
     finally:
@@ -480,8 +536,41 @@ def run_b(api, case, c=None):
                 args = (1e-9, op[1], 2, op[2])
                 ra, rb = getattr(a, kind)(*args), getattr(b, kind)(*args)
                 assert np.array(ra).tobytes() == np.array(rb).tobytes(), "%s: %r against %r" % (ctx, ra, rb)
+            elif kind == "step_energy":
+                _, nsteps, every, K = op
+                rows = a.step_energy(nsteps, every, K, "rel")
+                assert rows.shape == (nsteps // every, _abi.VOF_ENERGY_N), ctx
+                for r in range(nsteps // every):
+                    step_twin(b, every, K)
+                    want = energy_gpu.vec(energy_gpu.hold_to_restatement(b, ctx + " row %d on the twin" % r, bits=True))
+                    assert rows[r].tobytes() == want.tobytes(), "%s: row %d" % (ctx, r)
+                step_twin(b, nsteps % every, K)
+            elif kind == "regrid_out":          # "src is otherwise unchanged": the comparison with the twin below
+                _, pnx, pny, dtype, plic = op
+                d = vf.make(api, dict(g, nx=pnx, ny=pny, dtype=dtype))
+                try:
+                    summ = d.regrid_from(a, plic=plic, eps=case["eps"])
+                    want, wsum = rnp.restate(read_back(b, False), pnx, pny, d.np_dtype, plic=plic, eps=case["eps"], dx=k["dx"], dy=k["dy"], istep=b.istep)
+                    held_to_regrid(d, want, summ, wsum, True, ctx)
+                finally:
+                    d.close()
+            elif kind == "regrid_in":           # what dst keeps is "left alone": hold_kept below; the eager handle and the graph-caching twin go on alike
+                _, pnx, pny, dtype, nsteps, plic, tm = op
+                src = vf.make(api, dict(g, nx=pnx, ny=pny, dtype=dtype), ic=case["ic"])
+                try:
+                    src.step(nsteps)
+                    if tm:
+                        for h in (a, b):
+                            h.set_param("fuse_tm", 1); h.set_param("f_zero_map", 1)
+                    fs = read_back(src, False)
+                    want, wsum = rnp.restate(fs, g["nx"], g["ny"], NPT, plic=plic, eps=case["eps"], dx=src.get_param("dx"), dy=src.get_param("dy"), istep=nsteps)
+                    for h in (a, b):
+                        held_to_regrid(h, want, h.regrid_from(src, plic=plic, eps=case["eps"]), wsum, True, ctx)
+                    assert tuple(src.get(n).tobytes() for n in STATE) == tuple(fs[n].tobytes() for n in STATE) and src.istep == nsteps, ctx + ": src changed"
+                finally:
+                    src.close()
             elif kind == "readonly":
-                read_only(api, a, case, ["diagnostics", "interface", "blobs", "depths", "frame"] + (["dye_stats"] if dye is not None else []), xy, ctx)
+                read_only(api, a, case, ["diagnostics", "interface", "blobs", "depths", "frame", "curvature", "energy"] + (["dye_stats"] if dye is not None else []), xy, ctx)
             elif kind == "knob":
                 for h in ((a, b) if op[1] in ("mg_nu", "mg_levels") else (a,)):
                     h.set_param(op[1], op[2])
@@ -501,8 +590,17 @@ def run_b(api, case, c=None):
                 call = {"step_diag": lambda: a.step_diag(2, 1), "step_stats": lambda: a.step_stats(2, 1), "step_dye": lambda: a.step_dye(2, 1),
                         "step_tracers": lambda: a.step_tracers(2, 1), "step_gauges": lambda: a.step_gauges(2, 1), "step_frames": lambda: a.step_frames(2, 1),
                         "stats_sample": a.stats_sample, "dye_advance": a.dye_advance, "tracers_advance": lambda: a.tracers_advance(1e-5),
-                        "gauges_get": a.gauges_get}[op[1]]
-                refused_with(call, "VOF_ESTATE", ctx)          # (what it must not have changed: the comparison with the twin below)
+                        "gauges_get": a.gauges_get, "energy": a.energy, "step_energy": lambda: a.step_energy(2, 1), "curvature": lambda: a.curvature(case["eps"]),
+                        "regrid_src": lambda: other.regrid_from(a, eps=case["eps"]), "regrid_dst": lambda: a.regrid_from(other, eps=case["eps"])}
+                other = vf.make(api, g, ic=case["ic"]) if op[1] == vf.LATER else None
+                try:
+                    kept = state_bytes(other) if other else None
+                    for name in (vf.REFUSED_B2[kind] if op[1] == vf.LATER else (op[1],)):
+                        refused_with(call[name], "VOF_ESTATE", "%s: %s" % (ctx, name))      # (what it must not have changed: the comparison with the twin below)
+                    assert other is None or state_bytes(other) == kept, ctx + ": the other handle of a refused vof_regrid changed"
+                finally:
+                    if other:
+                        other.close()
                 a.step_phase(1); a.step_phase(2)
                 b.step(1)
             elif kind == "refused_strip":
@@ -513,8 +611,9 @@ def run_b(api, case, c=None):
                     call = {"step_diag": lambda: s.step_diag(2, 1), "step_stats": lambda: s.step_stats(2, 1), "step_dye": lambda: s.step_dye(2, 1),
                             "step_tracers": lambda: s.step_tracers(2, 1), "step_gauges": lambda: s.step_gauges(2, 1), "step_frames": lambda: s.step_frames(2, 1),
                             "stats_sample": s.stats_sample, "dye_advance": s.dye_advance, "tracers_advance": lambda: s.tracers_advance(1e-5),
-                            "gauges_get": s.gauges_get}[op[1]]
-                    refused_with(call, "VOF_ESTATE", ctx)
+                            "gauges_get": s.gauges_get, "energy": s.energy, "step_energy": lambda: s.step_energy(2, 1), "curvature": lambda: s.curvature(case["eps"])}
+                    for name in (vf.REFUSED_B2[kind] if op[1] == vf.LATER else (op[1],)):
+                        refused_with(call[name], "VOF_ESTATE", "%s: %s" % (ctx, name))
                     assert state_bytes(s) == before, ctx + ": a refused call changed the strip"
                 finally:
                     s.close()
@@ -526,6 +625,7 @@ def run_b(api, case, c=None):
                 raise AssertionError("%s: %s differ between the handle and its twin" % (ctx, ", ".join(bad)))
             assert all(np.isfinite(b.get(f)).all() for f in STATE), ctx + ": the generator drew a sequence that leaves a non-finite state"
             assert a.get_counter("courant_violations") == b.get_counter("courant_violations"), ctx
+            assert a.get_counter("fzmap_wrong") == 0 and b.get_counter("fzmap_wrong") == 0, ctx + ": a kept zero map stands over a cell that is no zero"
             hold_kept(ctx + ", what the handle keeps")
         if c is not None:
             vf.census_b(c, case)
@@ -533,7 +633,103 @@ def run_b(api, case, c=None):
         a.close(); b.close()
 
 
-RUN = {"A": run_a, "B": run_b, "C": run_c}
+# ---------------------------------------------------------------------------------------------------- leg D
+def held_to_regrid(d, want, summ, wsum, finite, ctx):
+    """F, u, v, p of d with their ghost rings, F2 and the summary against the restatement: byte for byte, or, behind a source that
+    is not finite, every entry that is no NaN bit for bit and the NaNs in the same places (module docstring of tests/_verb_fuzz.py)."""
+    for n in STATE + ("F2",):
+        got, w = d.get(n), want["F" if n == "F2" else n]
+        assert got.dtype == w.dtype, ctx
+        same = got.tobytes() == w.tobytes() if finite else tnp.same_bits(got, w)
+        assert same, "%s: %s of dst differs from the restatement in %d cells" % (ctx, n, int(((got != w) & ~(np.isnan(got) & np.isnan(w))).sum()))
+    if summ is not None:
+        assert set(summ) == set(wsum) and all(same_or_both_nan(summ[q], wsum[q]) for q in wsum), "%s: the summary %r against %r" % (ctx, summ, wsum)
+    assert not d.get("u")[0].any() and not np.signbit(d.get("u")[0]).any() and not d.get("v")[:, 0].any() and not np.signbit(d.get("v")[:, 0]).any(), \
+        ctx + ": row 0 of u and column 0 of v are +0"
+
+
+def refusal_d(api, case, src, dst, ctx):
+    """The drawn call vof_regrid must refuse with VOF_EINVAL, both handles byte for byte as they were."""
+    why, gs, gd = case["refusal"], case["src"], case["grid"]
+    summ = (C.c_double * _abi.VOF_REGRID_SUM_N)()
+    PLIC = _abi.VOF_REGRID_PLIC
+    other = None
+    if why == "mixed directions":
+        shape = (2 * gs["nx"], gs["ny"] - 1) if gs["ny"] > 3 else (gs["nx"] - 1, 2 * gs["ny"])
+        other = vf.make(api, dict(gs, nx=shape[0], ny=shape[1]))
+    elif why == "no integer ratio":
+        other = vf.make(api, dict(gs, nx=2 * gs["nx"] + 1, ny=2 * gs["ny"]))
+    elif why == "a factor of 17":
+        other = vf.make(api, dict(gs, nx=17 * gs["nx"]))
+    elif why == "another Lx":
+        other = vf.make(api, dict(gd, kw=dict(gd["kw"], Lx=2.0 * dst.get_param("Lx"), Ly=dst.get_param("Ly"))))
+    try:
+        pairs = [(other, src), (src, other)] if other is not None else [(src, src)] if why == "dst == src" else [(dst, src)]
+        flags = 2 | (PLIC if case["plic"] else 0) if why.startswith("a flag bit") else PLIC if why.startswith("PLIC") else (PLIC if case["plic"] else 0)
+        eps = {"PLIC with eps 0.5": 0.5, "PLIC with a negative eps": -1e-9, "PLIC with a NaN eps": float("nan")}.get(why, case["eps"])
+        for x, y in pairs:
+            before = state_bytes(x), state_bytes(y)
+            rc = api.regrid(x.handle, y.handle, flags, eps, summ)
+            assert rc == _abi.VOF_EINVAL, "%s: %s answered %d" % (ctx, why, rc)
+            assert (state_bytes(x), state_bytes(y)) == before, "%s: the refused call (%s) changed a handle" % (ctx, why)
+    finally:
+        if other is not None:
+            other.close()
+
+
+def run_d(api, case, c=None):
+    gd, gs = case["grid"], case["src"]
+    src = vf.make(api, gs)
+    pre = case["pre"]
+    dst = vf.make(api, gd, ic=case["ic"] if pre == "stepped" else None)
+    extra = []
+    try:
+        f = vf.fields_d(api, case)
+        upload(src, f)
+        src.istep = case["istep"]
+        fs = read_back(src, False)
+        finite = all(np.isfinite(fs[n]).all() for n in STATE)
+        ctx = "seed %d %dx%d %s -> %dx%d %s %s %s%s eps %r, dst %s" % (case["seed"], gs["nx"], gs["ny"], gs["dtype"], gd["nx"], gd["ny"], gd["dtype"], case["kind"],
+                                                                   case["sprinkle"], " PLIC" if case["plic"] else "", case["eps"], pre)
+        if pre == "stepped":                 # graphs cached, ghost cells virtual
+            dst.step(3)
+        elif pre == "nan":                   # every cell of dst must come out "a function of the source alone"
+            for n in STATE:
+                dst.set(n, np.full((gd["nx"] + 2, gd["ny"] + 2), np.nan))
+        want, wsum = rnp.restate(fs, gd["nx"], gd["ny"], dst.np_dtype, plic=case["plic"], eps=case["eps"], dx=src.get_param("dx"), dy=src.get_param("dy"),
+                                 istep=case["istep"])
+        kept = state_bytes(src)
+        for again in ("", " again"):
+            summ = dst.regrid_from(src, plic=case["plic"], eps=case["eps"])
+            held_to_regrid(dst, want, summ, wsum, finite, ctx + again)
+            assert dst.istep == src.istep == case["istep"], ctx + again
+        assert state_bytes(src) == kept, ctx + ": src changed"
+        if c is not None:
+            vf.census_d(c, case, fs, vf.consts_of(src))
+        if vf.round_trip_d(case):            # u, v, F back on src's grid, on every cell and face set_BC does not overwrite
+            back = vf.make(api, gs)
+            extra.append(back)
+            back.regrid_from(dst, plic=False, eps=case["eps"])
+            nx, ny = gs["nx"], gs["ny"]
+            for n, (i0, j0) in (("F", (1, 1)), ("u", (2, 1)), ("v", (1, 2))):
+                got, w = back.get(n)[i0:nx + 1, j0:ny + 1], fs[n][i0:nx + 1, j0:ny + 1]
+                assert got.tobytes() == w.tobytes(), "%s: %s does not return from the round trip in %d cells" % (ctx, n, int((got != w).sum()))
+        if vf.steps_d(case):                 # (flow sources only: module docstring of tests/_verb_fuzz.py)
+            twin = vf.make(api, gd)
+            extra.append(twin)
+            for n in STATE:
+                twin.set(n, want[n])
+            twin.set_BC()
+            twin.istep = case["istep"]
+            dst.step(vf.steps_d(case)); twin.step(vf.steps_d(case))
+            assert state_bytes(dst) == state_bytes(twin), ctx + ": two steps behind vof_regrid against a twin fed by vof_set_field"
+        refusal_d(api, case, src, dst, ctx)
+    finally:
+        for h in [src, dst] + extra:
+            h.close()
+
+
+RUN = {"A": run_a, "B": run_b, "C": run_c, "D": run_d}
 
 
 def run_case(api, leg, seed, c=None):
@@ -574,10 +770,16 @@ def test_set_scene_equals_the_restatement(hip_api, k):
     run_slice(hip_api, "C", k)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", range(vf.TESTS["D"]))
+def test_regrid_between_drawn_grids_equals_the_restatement(hip_api, k):
+    run_slice(hip_api, "D", k)
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=["A", "B", "C"], required=True)
+    ap.add_argument("--leg", choices=["A", "B", "C", "D"], required=True)
     ap.add_argument("--seed", type=int, default=vf.SEED0 + 100000)
     ap.add_argument("--cases", type=int, default=100)
     ap.add_argument("--seconds", type=float, default=0.0, help="stop after this much wall time (0: run all cases)")
